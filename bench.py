@@ -14,14 +14,16 @@ A "step" = one smoothing pass over the (T x N) sample grid = ONE kernel launch o
 --gpus N every rank holds its own N samples per timestep (weak scaling) and the (T,P) f64
 statistics are all-reduced (RCCL) inside every step, followed by the solve launch -- the three
 launches replayed as one HIP graph.  One process per GPU; N>1 is launched by
-torch.distributed.run.  Prints ONE JSON line on rank 0 (stdout carries nothing else).
+torch.distributed.run.  Prints ONE JSON line of headline figures on rank 0 (stdout carries nothing else;
+result_line); --full-report FILE writes the full report as well.  --dump-outputs DIR writes what the last timed
+step computed (A_t, B_t, c_t) as .npy files.
 
 iLQR iterations / s of the contact workloads are measured on the optimisation the reference's script
 performs ("ilqr_loop": 20 iterations per episode, every one re-linearised around the previous result with
 fresh device-drawn samples, bounds re-centred, first tail warm-started from the previous descent);
 "ilqr_first_iter_per_s" is the first iteration alone, repeated from a cold start.
 
-Sub-reports of the default single-GPU run (all in the same JSON line):
+Sub-reports of the default single-GPU run (in the full report; the line carries their rates):
   "sweep_N"             the metric's workload at N = 1e3 and 1e5 (north_star's N points)
   "first_order"         the reference's planar-hand gradient mode (planar_hand_setup.py:28)
   "pgs_contact_solver"  the opt-in approximate step-QP solver (50 projected sweeps + polish)
@@ -399,6 +401,33 @@ def roofline(w, N, k_ms, nm):
     return r
 
 
+# The printed line carries the headline figures only: a reader of the run's log keeps its last ~2 KB, and the
+# full report (sub-reports, formulas, prose; ~24 KB) would leave that reader a fragment that does not parse.
+LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "timed_region_s",
+             "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "ilqr_iters_per_s",
+             "ms_per_ilqr_iter", "ilqr_first_iter_per_s", "ilqr_iters_per_s_public_api")
+SUB_REPORTS = ("first_order", "pgs_contact_solver", "general_kernel", "pendulum", "quadrotor", "box_pivoting")
+
+
+def result_line(out):
+    """The JSON line bench.py prints, from the full report `out`: its headline keys, the roofline's bound and
+    share, the iLQR loop's outcome, and every sub-report by its headline rate alone."""
+    line = {k: out[k] for k in LINE_KEYS if k in out}
+    line["roofline"] = {k: out["roofline"][k] for k in ("bound", "achieved", "peak", "unit", "frac")}
+    if out.get("ilqr_loop"):
+        line["ilqr_loop"] = {k: out["ilqr_loop"][k] for k in ("descends", "qp_converged_last_iteration",
+                                                              "cost_first_iteration", "cost_last")}
+    if "sweep_N" in out:
+        line["sweep_N"] = {n: r["value"] for n, r in out["sweep_N"].items()}
+    for k in SUB_REPORTS:
+        if k in out:
+            line[k] = out[k]["value"]
+    if "cpu_baseline" in out:
+        cb = out["cpu_baseline"]
+        line["cpu_baseline"] = {"value": cb["value"], "pool": cb.get("pool", {}).get("value")}
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -429,6 +458,12 @@ def main():
                          "reads the other ranks' statistics out of IPC-mapped device memory in one small launch")
     ap.add_argument("--force-unfused", action="store_true",
                     help="one GPU: time the multi-GPU step (accumulate + all-reduce + solve) with a 1-rank RCCL group")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (A_t, B_t, c_t: float64) as "
+                         "DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output")
+    ap.add_argument("--full-report", metavar="FILE", default=None,
+                    help="also write the full report (every sub-report in detail) as JSON to FILE; the printed line "
+                         "carries its headline figures")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20000 if args.workload == "pendulum" else 2000
@@ -571,8 +606,9 @@ def main():
         return dict(du_lo=torch.full((w.T, m), -wd, dtype=dev.F64, device=x_trj.device),
                     du_hi=torch.full((w.T, m), wd, dtype=dev.F64, device=x_trj.device))
 
-    def run(w, N, steps, warmup, loop_iters=20):
-        """Times the smoothing step and the full iLQR iteration of workload `w`."""
+    def run(w, N, steps, warmup, loop_iters=20, dump=None):
+        """Times the smoothing step and the full iLQR iteration of workload `w`.  `dump` (a dict): receives the
+        host copies of what the last timed smoothing step returned."""
         dm = w.system.dm()
         n, m, T, MODE = dm.n, dm.m, w.T, w.mode
         Q, Qd, R = dev.to_dev(w.Q), dev.to_dev(w.Qd), dev.to_dev(w.R)
@@ -689,6 +725,8 @@ def main():
             descent_run()
 
         el, ev_ms = timed(smooth_step, steps, warmup)
+        if dump is not None:        # before the iLQR timing below launches the step again
+            dump.update({k: tv[k].cpu().numpy() for k in ("At", "Bt", "ct")})
         it_steps = max(1, steps // (20 if contact else 4))
         el_it, _ = timed(ilqr_step, it_steps, max(1, it_steps // 10))
         el_it *= steps / it_steps
@@ -920,7 +958,14 @@ def main():
     w = Workload(args.workload, args.T, args.mode, contact_solver=args.contact_solver)
     N, T = args.N, w.T
     contact = w.bounds is not None
-    el, el_it, k_mean, nm, loop = run(w, N, args.steps, args.warmup)
+    dumped = {} if args.dump_outputs else None
+    el, el_it, k_mean, nm, loop = run(w, N, args.steps, args.warmup, dump=dumped)
+    if dumped is not None and sum(a.nbytes for a in dumped.values()) > 64 << 20:
+        raise SystemExit("--dump-outputs: the outputs exceed 64 MB at T=%d" % T)      # (the same on every rank)
+    if dumped is not None and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, a in dumped.items():
+            np.save(os.path.join(args.dump_outputs, k + ".npy"), a)
     out = {
         "metric": "rollouts*timesteps/s (randomized-smoothing pass) + iLQR-iters/s",
         "value": world * N * T * args.steps / el,
@@ -1025,7 +1070,10 @@ def main():
     if rank == 0:
         if cpu_base is not None:
             out["cpu_baseline"] = cpu_base
-        json_out.write(json.dumps(out) + "\n")
+        if args.full_report:
+            with open(args.full_report, "w") as f:
+                f.write(json.dumps(out) + "\n")
+        json_out.write(json.dumps(result_line(out)) + "\n")
         json_out.flush()
     if os.environ.get("IRS_PRINT_STAMPS"):      # diagnostic library only (tools/stamp_descent.sh): phases of the LAST descent
         from irs_mpc_amd import _lib

@@ -274,6 +274,30 @@ def copy_box_pushing_data():
     print("copied box_pushing_exact.csv")
 
 
+# ---- the names the reference's analytic example scripts import (data: module, name pairs) -----------
+# tests/test_cabi_cpu.py::test_compat_shim_resolves_the_reference_scripts_imports checks that examples/compat
+# resolves every one of them
+def scan_script_imports():
+    import json
+    import re
+    pat = re.compile(r"^from\s+(irs_lqr(?:\.\w+)*|\w+_dynamics)\s+import\s+(.+)$")
+    wanted = set()
+    for sysname in ("pendulum", "quadrotor", "bicycle", "three_cart"):
+        d = os.path.join(REF, "examples", sysname)
+        for fn in sorted(os.listdir(d)):
+            if not fn.endswith(".py") or fn.endswith("_dynamics.py") or "animation" in fn or "drake" in fn \
+                    or "simulation" in fn or fn == "pendulum_nn.py":
+                continue
+            for line in open(os.path.join(d, fn)):
+                mm = pat.match(line.strip())
+                if mm:
+                    wanted |= {(mm.group(1), nm.strip()) for nm in mm.group(2).split(",")}
+    with open(os.path.join(HERE, "reference_script_imports.json"), "w") as f:
+        f.write("[\n" + ",\n".join(" " + json.dumps(list(p)) for p in sorted(wanted)) + "\n]\n")
+    print("wrote reference_script_imports.json (%d names)" % len(wanted))
+
+
 if __name__ == "__main__":
     main()
     copy_box_pushing_data()
+    scan_script_imports()

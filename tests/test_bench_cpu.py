@@ -72,3 +72,22 @@ def test_flop_model_of_the_uniform_geometry_kernel():
     f1, _ = bench.contact_flops_per_sample("ug", 50, True)
     assert f1 == f - 88 + 8
     assert bench.ISSUE_CYCLES == 2 and bench.ISSUE_CYCLES_ONE_WAVE == 4
+
+
+def test_result_line_is_compact_and_keeps_the_headline():
+    """bench.py prints result_line(full report): it must stay readable from the last 2 KB of a log -- the full
+    report of a default run (profiles/r03i_bench.json, ~24 KB) is not -- and carry the headline figures."""
+    import json
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r03i_bench.json")))
+    text = json.dumps(bench.result_line(full))
+    assert len(text) < 1700, len(text)
+    line = json.loads(text)
+    for k in ("value", "unit", "steps", "n_gpus", "ms_per_step", "scaling", "config", "ilqr_iters_per_s",
+              "ilqr_iters_per_s_public_api"):
+        assert line[k] == full[k], k
+    assert line["roofline"]["frac"] == full["roofline"]["frac"]
+    assert line["ilqr_loop"]["cost_last"] == full["ilqr_loop"]["cost_last"]
+    assert line["sweep_N"] == {n: r["value"] for n, r in full["sweep_N"].items()}
+    assert all(line[k] == full[k]["value"] for k in bench.SUB_REPORTS)
+    assert line["cpu_baseline"]["value"] == full["cpu_baseline"]["value"]

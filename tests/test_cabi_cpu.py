@@ -125,12 +125,12 @@ def test_no_gpu_fails_loudly():
 def test_compat_shim_resolves_the_reference_scripts_imports():
     """f4: examples/compat lets the TEXT of the reference's analytic example scripts run with only sys.path
     changed -- every `from irs_lqr... import ...` / `from <system>_dynamics import ...` line of those scripts must
-    resolve to a device-backed twin.  The names are listed here (read off examples/{pendulum,quadrotor,bicycle,
-    three_cart}/*.py of the reference); when the reference tree is present (this container, not the GPU box) its
-    scripts are scanned as well so that the list cannot go stale."""
+    resolve to a device-backed twin.  The names are listed here, together with the import lines scanned from
+    examples/{pendulum,quadrotor,bicycle,three_cart}/*.py of the reference and stored in
+    tests/golden/reference_script_imports.json (tests/golden/make_fixtures.py)."""
     import importlib
+    import json
     import os
-    import re
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     shim = os.path.join(root, "examples", "compat")
@@ -142,18 +142,9 @@ def test_compat_shim_resolves_the_reference_scripts_imports():
                ("irs_lqr.irs_lqr_quasistatic", "IrsLqrQuasistatic"), ("irs_lqr.irs_lqr_quasistatic", "IrsLqrQuasistaticParameters"),
                ("irs_lqr.tv_lqr", "solve_tvlqr"), ("irs_lqr.tv_lqr", "get_solver"),
                ("irs_lqr.dynamical_system", "DynamicalSystem")}
-    ref = "/root/reference/examples"
-    if os.path.isdir(ref):
-        pat = re.compile(r"^from\s+(irs_lqr(?:\.\w+)*|\w+_dynamics)\s+import\s+(.+)$")
-        for sysname in ("pendulum", "quadrotor", "bicycle", "three_cart"):
-            for fn in sorted(os.listdir(os.path.join(ref, sysname))):
-                if not fn.endswith(".py") or fn.endswith("_dynamics.py") or "animation" in fn or "drake" in fn \
-                        or "simulation" in fn or fn == "pendulum_nn.py":
-                    continue
-                for line in open(os.path.join(ref, sysname, fn)):
-                    mm = pat.match(line.strip())
-                    if mm:
-                        wanted |= {(mm.group(1), nm.strip()) for nm in mm.group(2).split(",")}
+    scanned = json.load(open(os.path.join(root, "tests", "golden", "reference_script_imports.json")))
+    assert len(scanned) >= 11
+    wanted |= {(mod, name) for mod, name in scanned}
     sys.path.insert(0, shim)
     try:
         for mod in [m for m in sys.modules if m == "irs_lqr" or m.startswith("irs_lqr.")]:

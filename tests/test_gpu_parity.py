@@ -1271,6 +1271,31 @@ def test_bench_two_ranks_peer_exchange_on_one_gpu():
     assert out["config"]["collective"].startswith("peer") and "one HIP graph" in out["config"]["step"]
 
 
+def test_bench_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """bench.py --dump-outputs DIR: A_t, B_t, c_t of the last timed step as float64 .npy files, bit for bit the same
+    in two runs with the same arguments (seeded inputs, fixed-order sums)."""
+    import json
+    import subprocess
+    import sys
+    T, dumps = 8, []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+               "--T", str(T), "--N", "1000", "--no-secondary", "--no-cpu-baseline", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == 7, r.stdout[-1000:]
+        dumps.append({k: np.load(d / (k + ".npy")) for k in ("At", "Bt", "ct")})
+        assert sorted(os.listdir(d)) == ["At.npy", "Bt.npy", "ct.npy"]
+    a, b = dumps
+    n = a["At"].shape[1]
+    assert a["At"].shape == (T, n, n) and a["Bt"].shape == (T, n, 4) and a["ct"].shape == (T, n)
+    for k in a:
+        assert a[k].dtype == np.float64 and np.isfinite(a[k]).all() and np.abs(a[k]).max() > 0, k
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_peer_exchange_one_rank_step_equals_the_two_stage_path(amd):
     """One rank: accumulate -> exchange launch -> solve (eager, and replayed from the library's HIP graph) == the
     two-stage path, bit for bit (as test_collective_step_inside_the_library for the RCCL step); the counters count."""
