@@ -273,7 +273,8 @@ int irs_tvlqr_descent(int model, const double *params, int n_params, int T,
  * over-relaxation, stop at max(primal, dual residual) < eps or max_iter.
  * info (3) DEV int32: [0] t+1 of a non-PD Hessian (0 ok), [1] most ADMM iterations any tail
  * needed, [2] number of tails that stopped at max_iter.  One launch; the factorisation lives
- * in LDS, so T is limited (irs_tvlqr_box_lds_bytes(model,T) <= ~160 KB).                 */
+ * in LDS, so T is limited (irs_tvlqr_box_lds_bytes(model,T) <= ~160 KB); irs_tvlqr_box_descent_wsx
+ * runs longer horizons with the factor records in a workspace in HBM.                      */
 int irs_tvlqr_box_descent(int model, const double *params, int n_params, int T,
                           const double *At, const double *Bt, const double *ct,
                           const double *Q, const double *Qd, const double *R, double alpha_R,
@@ -282,6 +283,31 @@ int irs_tvlqr_box_descent(int model, const double *params, int n_params, int T,
                           double rho, double relax, int max_iter, double eps,
                           double *x_new, double *u_new, int *info, void *stream);
 size_t irs_tvlqr_box_lds_bytes(int model, int T);
+
+/* The bounded TV-LQR beyond the LDS horizon.  The kernel keeps one factor record per time step (the Riccati
+ * factorisation every ADMM iteration sweeps) and the ADMM vectors.  With the records in a caller workspace in HBM
+ * only the vectors stay in LDS: the horizon is limited by irs_tvlqr_box_hbm_lds_bytes(model, T, du) <= ~160 KB
+ * instead (quadrotor T <= 357, bicycle T <= 867; position-controlled form, du = 1: planar hand T <= 383, box
+ * pivoting T <= 679).  The sweeps stage the records back through LDS two steps ahead of use; the results are
+ * bit-identical to the on-chip path.
+ * irs_tvlqr_box_workspace_bytes: the record bytes when the records do not fit LDS, 0 when they do (or when the
+ * model has no such form).  du = 0: the plain form of irs_tvlqr_box_descent; du = 1: the position-controlled
+ * form (irs_quasistatic_box_descent solver 1, irs_tvlqr_box_solve with position_controlled = 1).  Neither query
+ * touches the GPU.                                                                                             */
+size_t irs_tvlqr_box_workspace_bytes(int model, int T, int du);
+size_t irs_tvlqr_box_hbm_lds_bytes(int model, int T, int du);
+/* irs_tvlqr_box_descent / irs_tvlqr_box_solve with a workspace: DEV, 256-byte aligned, >= the record bytes of
+ * this horizon (BoxLayout stride x T, rounded up to 256; irs_tvlqr_box_workspace_bytes where the records do not
+ * fit LDS).  A workspace that is given is used, even where the records would fit on chip; NULL = the entry
+ * without it.  IRS_ERR_WORKSPACE if it is too small.                                                           */
+int irs_tvlqr_box_descent_wsx(int model, const double *params, int n_params, int T,
+                              const double *At, const double *Bt, const double *ct,
+                              const double *Q, const double *Qd, const double *R, double alpha_R,
+                              const double *xd_trj, const double *x0,
+                              const double *xlo, const double *xhi, const double *ulo, const double *uhi,
+                              double rho, double relax, int max_iter, double eps,
+                              double *x_new, double *u_new, int *info, void *workspace, size_t workspace_bytes,
+                              void *stream);
 
 /* IrsLqrQuasistatic.local_descent after get_TV_matrices (irs_lqr/irs_lqr_quasistatic.py:286-345)
  * for a position-controlled model (one with indices_u_into_x, e.g. IRS_MODEL_PLANAR_HAND): T tail
@@ -355,6 +381,15 @@ int irs_tvlqr_box_solve(int model, const double *params, int n_params, int T,
                         const double *du_lo, const double *du_hi,
                         double rho, double relax, int max_iter, double eps,
                         double *x_star, double *u_star, int *info, void *stream);
+int irs_tvlqr_box_solve_wsx(int model, const double *params, int n_params, int T,
+                            const double *At, const double *Bt, const double *ct,
+                            const double *Q, const double *Qd, const double *R, double alpha_R,
+                            const double *xd_trj, const double *x0, int position_controlled,
+                            const double *x_lo, const double *x_hi, const double *u_lo, const double *u_hi,
+                            const double *du_lo, const double *du_hi,
+                            double rho, double relax, int max_iter, double eps,
+                            double *x_star, double *u_star, int *info, void *workspace, size_t workspace_bytes,
+                            void *stream);
 /* IrsLqrZeroOrder.compute_least_squares (irs_lqr/irs_lqr_zero_order.py:27-36) stand-alone: dxdu (N, n+m),
  * deltaf (N, n) DEV f64 -> A (n,n), B (n,m) with [A | B] = lstsq(dxdu, deltaf)[0]'.  Normal equations in f64,
  * Jacobi-scaled Cholesky (the solve the sample pass ends with).  info (1): 0, the failed pivot (1-based: a
@@ -362,9 +397,11 @@ int irs_tvlqr_box_solve(int model, const double *params, int n_params, int T,
 int irs_least_squares(int n, int m, int N, const double *dxdu, const double *deltaf, double *A, double *B,
                       int *info, void *stream);
 /* The same with a device workspace for horizons whose per-step records do not fit the 160 KB of LDS
- * (solver 3 / 0): `workspace` DEV, at least irs_quasistatic_descent_workspace_bytes(model, T, solver)
- * bytes (0 = none needed: pass NULL); uninitialised scratch, no state is kept in it between calls.  The
- * reference has no horizon limit (irs_lqr_quasistatic.py:325-345).                                    */
+ * (solver 3 / 0, and solver 1: the ADMM's factor records, up to irs_tvlqr_box_hbm_lds_bytes(model, T, 1)
+ * <= ~160 KB): `workspace` DEV, 256-byte aligned, at least irs_quasistatic_descent_workspace_bytes(model, T,
+ * solver) bytes (0 = none needed: pass NULL); uninitialised scratch, no state is kept in it between calls.
+ * Where the records fit LDS the workspace is not used.  The reference has no horizon limit
+ * (irs_lqr_quasistatic.py:325-345).                                                                    */
 int irs_quasistatic_box_descent_wsx(int model, const double *params, int n_params, int T,
                                     const double *At, const double *Bt, const double *ct,
                                     const double *Q, const double *Qd, const double *R,
@@ -451,7 +488,8 @@ int irs_descent_run(const irs_descent_call *call, void *stream);
  * sigma / iter^p, examples/pendulum/pendulum_zero_order.py:38-43); Philox iteration counter of descent i = iter0 + i.
  * info_hist (n_descents, 8) DEV int32 per descent: [0] Riccati info (t+1 of a non-PD Hessian), [1] number of
  * timesteps whose smoothing solve failed, [2] 1 = some tail's unconstrained plan left the box (the bounded descent
- * ran), [3..5] its info (irs_tvlqr_box_descent), [6] 1 = it was needed but the horizon does not fit its kernel.
+ * ran), [3..5] its info (irs_tvlqr_box_descent), [6] 1 = it was needed but the horizon does not fit its kernel
+ * (beyond the LDS horizon its factor records live at the end of the scratch; [6] only past the HBM form's limit).
  * scratch: DEV, >= irs_iterate_scratch_bytes(model, mode, T, N).  timing (optional, HOST out): per-phase device
  * time summed over the descents -- timing mode synchronises after every descent; NULL = fully asynchronous.   */
 #define IRS_ITERATE_EXACT 3

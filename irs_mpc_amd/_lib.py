@@ -128,6 +128,11 @@ SIGNATURES["irs_tvlqr_box_descent"] = (c_int, [c_int, POINTER(c_double), c_int, 
                                                c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_double, c_double, c_int,
                                                c_double, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_tvlqr_box_lds_bytes"] = (c_size_t, [c_int, c_int])
+SIGNATURES["irs_tvlqr_box_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int])
+SIGNATURES["irs_tvlqr_box_hbm_lds_bytes"] = (c_size_t, [c_int, c_int, c_int])
+SIGNATURES["irs_tvlqr_box_descent_wsx"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                   c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_double, c_double, c_int,
+                                                   c_double, _dp, _dp, _dp, _dp, c_size_t, c_void_p])
 SIGNATURES["irs_quasistatic_box_descent"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
                                                      _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, c_int, c_double, c_double,
                                                      c_int, c_double, _dp, _dp, _dp, _dp, c_void_p])
@@ -143,6 +148,9 @@ SIGNATURES["irs_quasistatic_descent_workspace_bytes"] = (c_size_t, [c_int, c_int
 SIGNATURES["irs_tvlqr_box_solve"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_double,
                                              _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_double, c_double, c_int,
                                              c_double, _dp, _dp, _dp, c_void_p])
+SIGNATURES["irs_tvlqr_box_solve_wsx"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                 c_double, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_double,
+                                                 c_double, c_int, c_double, _dp, _dp, _dp, _dp, c_size_t, c_void_p])
 SIGNATURES["irs_least_squares"] = (c_int, [c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_smooth_run"] = (c_int, [POINTER(SmoothCall), c_void_p])
 SIGNATURES["irs_descent_run"] = (c_int, [POINTER(DescentCall), c_void_p])

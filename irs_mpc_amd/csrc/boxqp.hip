@@ -23,7 +23,13 @@
 // (x bounds; u bounds = bounds on the u_prev block one step later) and on v.  The augmented
 // matrices are never materialised: accessors below read (A,B,c) directly.
 //
-// One wave, f64, everything in (dynamic) LDS: a latency-bound chain like the Riccati pass.
+// One wave, f64: a latency-bound chain like the Riccati pass.  The ADMM vectors and the scratch live in
+// (dynamic) LDS.  The T factor records live there too while they fit (HBM = false); beyond that -- or when the
+// caller asks for it -- they live in a caller workspace in HBM (HBM = true, same source): the factorisation
+// builds each record in an LDS slot and stores it once, and the sweeps, whose record addresses are known in
+// advance, stage them back through a 3-slot LDS ring two steps ahead of use (global_load_dwordx4 into
+// registers, ds_write_b128 one step before the record is needed).  The arithmetic and its order are the same
+// on both paths: they give bit-identical results.
 #include "boxqp.hpp"
 
 namespace {
@@ -48,10 +54,18 @@ struct BoxLayout {
         // factor records + qx_T + wx,yx,zx (T+1,N) + wu,yu,zu,k (T,M) + scratch
         return (size_t)T * S + N + 3 * (size_t)(T + 1) * N + 4 * (size_t)T * M + 4 * N * N + 8 * N + 4 * M + 64;
     }
+    // records in HBM: stride padded to 16 B; on chip only the 3-slot staging ring stays in place of the records
+    static constexpr int SP = (S + 1) / 2 * 2, RING = 3;
+    static __host__ __device__ size_t hbm_doubles(int T) { return doubles(T) - (size_t)T * S + (size_t)RING * SP; }
+    static size_t record_bytes(int T) { return ((size_t)T * SP * sizeof(double) + 255) / 256 * 256; }
 };
 
-template <class Model, bool DU>
-__global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a) {
+typedef double v2d __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(1))) v2d gv2d;    // global: a generic pointer would make these flat accesses,
+                                                        // which also count in lgkmcnt and would stall at every wave_sync
+
+template <class Model, bool DU, bool HBM>
+__global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs) {
     if (a.run_flag != nullptr && *a.run_flag == 0) return;          // uniform
     constexpr int NR = Model::NX, M = Model::NU;      // real state / control sizes
     constexpr int N = NR + (DU ? M : 0);              // size of the QP's state (z = [x; u_prev] if DU)
@@ -87,8 +101,8 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a) {
     };
     extern __shared__ double lds[];
     const int T = a.T, lane = threadIdx.x;
-    double* F = lds;                                   // T records of L::S doubles
-    double* qxT = F + (size_t)T * L::S;                // Qd xd_T
+    double* F = lds;                                   // T records of L::S doubles, or (HBM) the ring: 3 x L::SP
+    double* qxT = F + (HBM ? (size_t)L::RING * L::SP : (size_t)T * L::S);   // Qd xd_T
     double* wx = qxT + N;                              // (T+1, N)
     double* yx = wx + (size_t)(T + 1) * N;
     double* zx = yx + (size_t)(T + 1) * N;
@@ -140,7 +154,8 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a) {
     // ---- factorisation: backward Riccati with Q^ = Q + rho/2 Mx, R^ = alpha R + rho/2 Mu --
     int bad = 0;
     for (int t = T - 1; t >= 0; --t) {
-        double* rec = F + (size_t)t * L::S;
+        // HBM: records T-1 and T-2 are built in the ring slots the first sweep reads them from, the rest in the third
+        double* rec = HBM ? F + (size_t)((t >= T - 2 ? t : T - 3) % L::RING) * L::SP : F + (size_t)t * L::S;
         for (int q = lane; q < N * N; q += 64) Am[q] = A_(t, q / N, q % N);
         for (int q = lane; q < N * M; q += 64) rec[L::oB + q] = B_(t, q / M, q % M);
         if (lane < N) {
@@ -265,8 +280,36 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a) {
             int q = lane + 64 * r;
             if (q < N * N) P[q] = pn[r];
         }
+        if constexpr (HBM) {                             // the finished record, once, to the workspace
+            const v2d* src = reinterpret_cast<const v2d*>(rec);
+            gv2d* dst = (gv2d*)(recs + (size_t)t * L::SP);
+            for (int c = lane; c < L::SP / 2; c += 64) dst[c] = src[c];
+        }
         wave_sync();
     }
+    if constexpr (HBM) {                                 // the sweeps read them back: the stores are done first
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+    }
+
+    // ---- HBM records: staging through the LDS ring -------------------------------------------
+    // record t = L::SP / 2 16-byte chunks; lane l moves chunks l, l + 64, ..  (global_load_dwordx4 into registers;
+    // the compiler's vmcnt wait lands at the ds_write_b128 that puts them in the ring, one step after the load)
+    constexpr int NC = L::SP / 2, RC = (NC + 63) / 64;
+    struct Stage { v2d v[RC]; };
+    auto fetch = [&](int t, Stage& st) {
+        const gv2d* src = (const gv2d*)(recs + (size_t)t * L::SP);
+#pragma unroll
+        for (int r = 0; r < RC; ++r)
+            if (r * 64 + lane < NC) st.v[r] = src[r * 64 + lane];
+    };
+    auto put = [&](int t, const Stage& st) {
+        v2d* dst = reinterpret_cast<v2d*>(F + (size_t)(t % L::RING) * L::SP);
+#pragma unroll
+        for (int r = 0; r < RC; ++r)
+            if (r * 64 + lane < NC) dst[r * 64 + lane] = st.v[r];
+    };
+    (void)fetch; (void)put;
 
     // ---- MPC loop: T tail re-solves, first control applied to the true dynamics ----------
     double xr[NR], ur[M], xn[NR], up[M];
@@ -318,8 +361,9 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a) {
             // backward affine sweep: p_T = -(Qd xd_T + rho/2 mx (w - y)_T)
             if (lane < N) pv[lane] = -(qxT[lane] + hr * mxv[lane] * (wx[(size_t)T * N + lane] - yx[(size_t)T * N + lane]));
             wave_sync();
-            for (int t = T - 1; t >= tau; --t) {
-                const double* rec = F + (size_t)t * L::S;
+            // (HBM: `hook` stages the record two steps ahead into the ring just before the step's last wave_sync)
+            auto bw_step = [&](int t, auto hook) {
+                const double* rec = HBM ? F + (size_t)(t % L::RING) * L::SP : F + (size_t)t * L::S;
                 if (lane < N) gv[lane] = rec[L::oD + lane] + pv[lane];
                 else if (lane < N + M) {
                     int j = lane - N;
@@ -338,11 +382,12 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a) {
                     for (int l = 0; l < M; ++l) s -= rec[L::oHinv + j * M + l] * sv[l];
                     kk[(size_t)t * M + j] = s;
                 }
+                hook();
                 wave_sync();
-            }
+            };
             // forward sweep on the linear model: u = K x + k, x+ = Acl x + B k + c
-            for (int t = tau; t < T; ++t) {
-                const double* rec = F + (size_t)t * L::S;
+            auto fw_step = [&](int t, auto hook) {
+                const double* rec = HBM ? F + (size_t)(t % L::RING) * L::SP : F + (size_t)t * L::S;
                 const double* xt = zx + (size_t)t * N;
                 if (lane < N) {
                     double s = rec[L::oC + lane];
@@ -355,7 +400,35 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a) {
                     for (int l = 0; l < N; ++l) s += rec[L::oK + j * N + l] * xt[l];
                     zu[(size_t)t * M + j] = s;
                 }
+                hook();
                 wave_sync();
+            };
+            if constexpr (!HBM) {
+                for (int t = T - 1; t >= tau; --t) bw_step(t, [] {});
+                for (int t = tau; t < T; ++t) fw_step(t, [] {});
+            } else {
+                // Ring invariant: a step t of either sweep starts with records t and t -+ 1 (the next one) in their
+                // slots t % 3 and (t -+ 1) % 3, and record t -+ 2 in flight into registers; it issues the loads of
+                // t -+ 3 and writes t -+ 2 into the slot of t +- 1, which nothing reads any more.  The factorisation
+                // leaves T-1 and T-2 in place; a backward sweep ends with tau and tau+1 in place, a forward sweep with
+                // T-1 and T-2 -- each what the next sweep starts from.  Two register sets, alternate steps.
+                Stage sa, sb;
+                if (T - 3 >= tau) fetch(T - 3, sa);
+                for (int t = T - 1; t >= tau; t -= 2) {
+                    if (t - 3 >= tau) fetch(t - 3, sb);
+                    bw_step(t, [&] { if (t - 2 >= tau) put(t - 2, sa); });
+                    if (t - 1 < tau) break;
+                    if (t - 4 >= tau) fetch(t - 4, sa);
+                    bw_step(t - 1, [&] { if (t - 3 >= tau) put(t - 3, sb); });
+                }
+                if (tau + 2 < T) fetch(tau + 2, sa);
+                for (int t = tau; t < T; t += 2) {
+                    if (t + 3 < T) fetch(t + 3, sb);
+                    fw_step(t, [&] { if (t + 2 < T) put(t + 2, sa); });
+                    if (t + 1 >= T) break;
+                    if (t + 4 < T) fetch(t + 4, sa);
+                    fw_step(t + 1, [&] { if (t + 3 < T) put(t + 3, sb); });
+                }
             }
             // projection + dual update (x_tau is fixed: only t > tau), residuals
             double rp = 0.0, rd = 0.0;
@@ -440,15 +513,15 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a) {
     }
 }
 
-template <class Model, bool DU>
-int launch_box(const BoxArgs& a, hipStream_t st) {
-    constexpr int N = Model::NX + (DU ? Model::NU : 0), M = Model::NU;
-    const size_t bytes = BoxLayout<N, M>::doubles(a.T) * sizeof(double);
-    if (bytes > 160 * 1024 - 512) {
-        irs_set_error("irs_tvlqr_box_descent: horizon T=%d needs %zu bytes of LDS (max ~160 KB)", a.T, bytes);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    auto kern = box_descent_kernel<Model, DU>;
+constexpr size_t kBoxLds = 160 * 1024 - 512;
+
+// sizes of the bounded TV-LQR kernel at one horizon: LDS with the records on chip, LDS with the records in HBM,
+// the HBM record bytes, and the longest horizon the HBM form runs
+struct BoxSizes { size_t lds, hbm_lds, records; int max_T; };
+
+template <class Model, bool DU, bool HBM>
+int launch_box_kernel(const BoxArgs& a, double* recs, size_t bytes, hipStream_t st) {
+    auto kern = box_descent_kernel<Model, DU, HBM>;
     static size_t granted = 0;           // per instantiation: the attribute call is a driver round trip (fused iterate)
     if (bytes > granted) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -459,11 +532,77 @@ int launch_box(const BoxArgs& a, hipStream_t st) {
         }
         granted = bytes;
     }
-    hipLaunchKernelGGL(kern, dim3(1), dim3(64), bytes, st, a);
+    hipLaunchKernelGGL(kern, dim3(1), dim3(64), bytes, st, a, recs);
     return IRS_OK;
 }
 
+// the longest horizon the kernel runs with its records in HBM (the ADMM vectors stay in LDS)
+template <int N, int M>
+int box_hbm_max_T() {
+    using L = BoxLayout<N, M>;
+    return (int)((kBoxLds / sizeof(double) - L::hbm_doubles(0)) / (3 * N + 4 * M));
+}
+
+// ws == nullptr: records in LDS (the horizon must fit).  ws given: records in ws when force_ws or when they do not
+// fit LDS; ws must then hold BoxLayout::record_bytes(T).
+template <class Model, bool DU>
+int launch_box(const BoxArgs& a, double* ws, size_t ws_bytes, bool force_ws, hipStream_t st) {
+    constexpr int N = Model::NX + (DU ? Model::NU : 0), M = Model::NU;
+    using L = BoxLayout<N, M>;
+    const size_t bytes = L::doubles(a.T) * sizeof(double);
+    if (ws == nullptr || (!force_ws && bytes <= kBoxLds)) {
+        if (bytes > kBoxLds) {
+            irs_set_error("irs_tvlqr_box_descent: horizon T=%d needs %zu bytes of LDS (max ~160 KB) with its records on "
+                          "chip; give a workspace of %zu bytes (T <= %d)", a.T, bytes, L::record_bytes(a.T),
+                          box_hbm_max_T<N, M>());
+            return IRS_ERR_UNSUPPORTED;
+        }
+        return launch_box_kernel<Model, DU, false>(a, nullptr, bytes, st);
+    }
+    const size_t hbytes = L::hbm_doubles(a.T) * sizeof(double);
+    if (hbytes > kBoxLds) {
+        irs_set_error("irs_tvlqr_box_descent: horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d with its "
+                      "records in HBM (its ADMM vectors need %zu bytes of LDS, max ~160 KB)", a.T, box_hbm_max_T<N, M>(),
+                      hbytes);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (ws_bytes < L::record_bytes(a.T)) {
+        irs_set_error("irs_tvlqr_box_descent: workspace %zu < %zu bytes", ws_bytes, L::record_bytes(a.T));
+        return IRS_ERR_WORKSPACE;
+    }
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) {
+        irs_set_error("irs_tvlqr_box_descent: the workspace must be 256-byte aligned");
+        return IRS_ERR_INVALID_ARG;
+    }
+    return launch_box_kernel<Model, DU, true>(a, ws, hbytes, st);
+}
+
+template <int N, int M>
+void fill_box_sizes(int T, BoxSizes* z) {
+    using L = BoxLayout<N, M>;
+    z->lds = L::doubles(T) * sizeof(double);
+    z->hbm_lds = L::hbm_doubles(T) * sizeof(double);
+    z->records = L::record_bytes(T);
+    z->max_T = box_hbm_max_T<N, M>();
+}
+
 }  // namespace
+
+// the plain (du = 0) or position-controlled (du = 1) form of `model`: IRS_OK, or IRS_ERR_UNSUPPORTED when the model
+// has no such form
+static int box_sizes(int model, int T, int du, BoxSizes* z) {
+    int rc = IRS_ERR_UNSUPPORTED;
+    IRS_DISPATCH_MODEL(model, {
+        if (du == 0) {
+            fill_box_sizes<Model::NX, Model::NU>(T, z);
+            rc = IRS_OK;
+        } else if constexpr (has_u_into_x<Model>::value) {
+            fill_box_sizes<Model::NX + Model::NU, Model::NU>(T, z);
+            rc = IRS_OK;
+        }
+    });
+    return rc;
+}
 
 extern "C" {
 
@@ -486,6 +625,38 @@ size_t irs_quasistatic_box_lds_bytes(int model, int T, int solver) {
     return r;
 }
 
+size_t irs_tvlqr_box_workspace_bytes(int model, int T, int du) {
+    BoxSizes z;
+    if (T <= 0 || box_sizes(model, T, du != 0, &z) != IRS_OK) return 0;
+    return z.lds <= kBoxLds ? 0 : z.records;
+}
+
+size_t irs_tvlqr_box_hbm_lds_bytes(int model, int T, int du) {
+    BoxSizes z;
+    if (T <= 0 || box_sizes(model, T, du != 0, &z) != IRS_OK) return 0;
+    return z.hbm_lds;
+}
+
+// a workspace the records must go to: 256-byte aligned, large enough
+static int check_box_workspace(const char* fn, int model, int T, int du, const void* ws, size_t ws_bytes) {
+    if (ws == nullptr) return IRS_OK;
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) {
+        irs_set_error("%s: the workspace must be 256-byte aligned", fn);
+        return IRS_ERR_INVALID_ARG;
+    }
+    BoxSizes z;
+    const int rc = box_sizes(model, T, du, &z);
+    if (rc != IRS_OK) {
+        irs_set_error("%s: model %d has no %s form", fn, model, du ? "position-controlled" : "plain");
+        return rc;
+    }
+    if (ws_bytes < z.records) {
+        irs_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, z.records);
+        return IRS_ERR_WORKSPACE;
+    }
+    return IRS_OK;
+}
+
 int irs_tvlqr_box_descent(int model, const double* params, int n_params, int T, const double* At,
                           const double* Bt, const double* ct, const double* Q, const double* Qd,
                           const double* R, double alpha_R, const double* xd_trj, const double* x0,
@@ -499,19 +670,16 @@ int irs_tvlqr_box_descent(int model, const double* params, int n_params, int T, 
                                     uhi, rho, relax, max_iter, eps, x_new, u_new, nullptr, info, nullptr, stream);
 }
 
-int irs_tvlqr_box_descent_if(int model, const double* params, int n_params, int T, const double* At,
-                             const double* Bt, const double* ct, const double* Q, const double* Qd,
-                             const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                             const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                             double rho, double relax, int max_iter, double eps, double* x_new,
-                             double* u_new, double* cost, int* info, const int* run_flag, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
-                  x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+static int box_descent_impl(int model, const double* params, int n_params, int T, const double* At,
+                            const double* Bt, const double* ct, const double* Q, const double* Qd,
+                            const double* R, double alpha_R, const double* xd_trj, const double* x0,
+                            const double* xlo, const double* xhi, const double* ulo, const double* uhi,
+                            double rho, double relax, int max_iter, double eps, double* x_new,
+                            double* u_new, double* cost, int* info, const int* run_flag, void* workspace,
+                            size_t workspace_bytes, bool force_ws, void* stream) {
     BoxArgs a;
     a.act_io = nullptr;
     a.single_tail = 0;
-    a.run_flag = nullptr;
     a.run_flag = run_flag;
     int rc = irs_load_params(model, params, n_params, &a.p);
     if (rc != IRS_OK) return rc;
@@ -521,10 +689,55 @@ int irs_tvlqr_box_descent_if(int model, const double* params, int n_params, int 
     a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info;
     a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.eps = eps; a.T = T; a.max_iter = max_iter;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, st); });
+    double* ws = static_cast<double*>(workspace);
+    IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, ws, workspace_bytes, force_ws, st); });
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
+}
+
+int irs_tvlqr_box_descent_if(int model, const double* params, int n_params, int T, const double* At,
+                             const double* Bt, const double* ct, const double* Q, const double* Qd,
+                             const double* R, double alpha_R, const double* xd_trj, const double* x0,
+                             const double* xlo, const double* xhi, const double* ulo, const double* uhi,
+                             double rho, double relax, int max_iter, double eps, double* x_new,
+                             double* u_new, double* cost, int* info, const int* run_flag, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
+                  x_new && u_new && info, "bad argument");
+    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+    return box_descent_impl(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi,
+                            rho, relax, max_iter, eps, x_new, u_new, cost, info, run_flag, nullptr, 0, false, stream);
+}
+
+int irs_tvlqr_box_descent_ifw(int model, const double* params, int n_params, int T, const double* At,
+                              const double* Bt, const double* ct, const double* Q, const double* Qd,
+                              const double* R, double alpha_R, const double* xd_trj, const double* x0,
+                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
+                              double rho, double relax, int max_iter, double eps, double* x_new,
+                              double* u_new, double* cost, int* info, const int* run_flag, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
+                  x_new && u_new && info, "bad argument");
+    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+    return box_descent_impl(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi,
+                            rho, relax, max_iter, eps, x_new, u_new, cost, info, run_flag, workspace, workspace_bytes,
+                            false, stream);
+}
+
+int irs_tvlqr_box_descent_wsx(int model, const double* params, int n_params, int T, const double* At,
+                              const double* Bt, const double* ct, const double* Q, const double* Qd,
+                              const double* R, double alpha_R, const double* xd_trj, const double* x0,
+                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
+                              double rho, double relax, int max_iter, double eps, double* x_new,
+                              double* u_new, int* info, void* workspace, size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
+                  x_new && u_new && info, "bad argument");
+    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+    int rc = check_box_workspace(__func__, model, T, 0, workspace, workspace_bytes);
+    if (rc != IRS_OK) return rc;
+    return box_descent_impl(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi,
+                            rho, relax, max_iter, eps, x_new, u_new, nullptr, info, nullptr, workspace, workspace_bytes,
+                            true, stream);
 }
 
 int irs_quasistatic_box_descent(int model, const double* params, int n_params, int T, const double* At,
@@ -553,9 +766,17 @@ int irs_quasistatic_box_descent_ws(int model, const double* params, int n_params
 }
 
 size_t irs_quasistatic_descent_workspace_bytes(int model, int T, int solver) {
-    if (T <= 0 || (solver != 0 && solver != 3)) return 0;
-    const size_t lds = irs_ctrlbox_mfma_lds_bytes(model, T);
-    return (lds == 0 || lds <= (size_t)(160 * 1024 - 512)) ? 0 : irs_ctrlbox_mfma_record_bytes(model, T);
+    if (T <= 0 || solver < 0 || solver > 3 || solver == 2) return 0;
+    size_t need = 0;
+    if (solver != 1) {            // matrix-core active set
+        const size_t lds = irs_ctrlbox_mfma_lds_bytes(model, T);
+        need = (lds == 0 || lds <= kBoxLds) ? 0 : irs_ctrlbox_mfma_record_bytes(model, T);
+    }
+    if (solver != 3) {            // ADMM: its factor records, when they do not fit LDS
+        const size_t rec = irs_tvlqr_box_workspace_bytes(model, T, 1);
+        need = rec > need ? rec : need;
+    }
+    return need;
 }
 
 int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_params, int T, const double* At,
@@ -615,7 +836,8 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
     }
     rc = IRS_ERR_UNSUPPORTED;
     IRS_DISPATCH_MODEL(model, {
-        if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, st);
+        if constexpr (has_u_into_x<Model>::value)      // records in the workspace only when they do not fit LDS
+            rc = launch_box<Model, true>(a, static_cast<double*>(workspace), workspace_bytes, false, st);
         else irs_set_error("irs_quasistatic_box_descent: model %d is not position controlled", model);
     });
     if (rc != IRS_OK) return rc;
@@ -624,17 +846,13 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
 }
 
 // solve_tvlqr (irs_lqr/tv_lqr.py:30-145) stand-alone: ONE bounded QP, its plan returned.
-int irs_tvlqr_box_solve(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                        const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                        const double* xd_trj, const double* x0, int position_controlled,
-                        const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
-                        const double* du_lo, const double* du_hi, double rho, double relax, int max_iter,
-                        double eps, double* x_star, double* u_star, int* info, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_star && u_star && info, "bad argument");
-    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
-                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
-    IRS_CHECK_ARG(position_controlled || du_lo == nullptr, "du bounds need the position-controlled form");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+static int box_solve_impl(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
+                          const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
+                          const double* xd_trj, const double* x0, int position_controlled,
+                          const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
+                          const double* du_lo, const double* du_hi, double rho, double relax, int max_iter,
+                          double eps, double* x_star, double* u_star, int* info, void* workspace,
+                          size_t workspace_bytes, void* stream) {
     BoxArgs a;
     a.act_io = nullptr;
     a.single_tail = 1;
@@ -649,18 +867,49 @@ int irs_tvlqr_box_solve(int model, const double* params, int n_params, int T, co
     a.x_new = x_star; a.u_new = u_star; a.cost = nullptr; a.info = info;
     a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.eps = eps; a.T = T; a.max_iter = max_iter;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    double* ws = static_cast<double*>(workspace);
     rc = IRS_ERR_UNSUPPORTED;
     if (position_controlled) {
         IRS_DISPATCH_MODEL(model, {
-            if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, st);
+            if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, ws, workspace_bytes, true, st);
             else irs_set_error("irs_tvlqr_box_solve: model %d is not position controlled", model);
         });
     } else {
-        IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, st); });
+        IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, ws, workspace_bytes, true, st); });
     }
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
+}
+
+int irs_tvlqr_box_solve(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
+                        const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
+                        const double* xd_trj, const double* x0, int position_controlled,
+                        const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
+                        const double* du_lo, const double* du_hi, double rho, double relax, int max_iter,
+                        double eps, double* x_star, double* u_star, int* info, void* stream) {
+    return irs_tvlqr_box_solve_wsx(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0,
+                                   position_controlled, x_lo, x_hi, u_lo, u_hi, du_lo, du_hi, rho, relax, max_iter, eps,
+                                   x_star, u_star, info, nullptr, 0, stream);
+}
+
+int irs_tvlqr_box_solve_wsx(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
+                            const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
+                            const double* xd_trj, const double* x0, int position_controlled,
+                            const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
+                            const double* du_lo, const double* du_hi, double rho, double relax, int max_iter,
+                            double eps, double* x_star, double* u_star, int* info, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_star && u_star && info, "bad argument");
+    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
+                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
+    IRS_CHECK_ARG(position_controlled || du_lo == nullptr, "du bounds need the position-controlled form");
+    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+    int rc = check_box_workspace(__func__, model, T, position_controlled ? 1 : 0, workspace, workspace_bytes);
+    if (rc != IRS_OK) return rc;
+    return box_solve_impl(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, position_controlled,
+                          x_lo, x_hi, u_lo, u_hi, du_lo, du_hi, rho, relax, max_iter, eps, x_star, u_star, info,
+                          workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -278,6 +278,13 @@ struct PhaseTimer {
     }
 };
 
+// the bounded descent's factor records where they do not fit LDS but its HBM form runs (0 otherwise): the tail of
+// the scratch, 256-byte aligned (every part before it is a multiple of 256 bytes)
+size_t box_record_bytes(int model, int T) {
+    const size_t rec = irs_tvlqr_box_workspace_bytes(model, T, 0);
+    return (rec > 0 && irs_tvlqr_box_hbm_lds_bytes(model, T, 0) <= (size_t)(160 * 1024 - 512)) ? rec : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -294,16 +301,23 @@ int irs_tvlqr_plan_within_bounds(int n, int m, int T, const double* At, const do
     return IRS_OK;
 }
 
-size_t irs_iterate_scratch_bytes(int model, int mode, int T, int N) {
+// the scratch before the smoothing workspace: TV matrices, gains, sums, info words; a multiple of 256 bytes
+static size_t scratch_front_bytes(int model, int mode, int T) {
     int n, m, np;
     if (irs_model_info(model, &n, &m, &np) != IRS_OK || T <= 0) return 0;
     const int P = mode == IRS_ITERATE_EXACT ? 0 : irs_sums_len(model, mode);
     if (P < 0) return 0;
     size_t doubles = (size_t)T * (n * n + n * m + n + m * n + m + (size_t)P) + 8;
     size_t bytes = doubles * sizeof(double) + ((size_t)T + 16) * sizeof(int);
-    bytes = (bytes + 255) / 256 * 256;
+    return (bytes + 255) / 256 * 256;
+}
+
+size_t irs_iterate_scratch_bytes(int model, int mode, int T, int N) {
+    size_t bytes = scratch_front_bytes(model, mode, T);
+    if (bytes == 0) return 0;
     if (mode != IRS_ITERATE_EXACT) bytes += irs_smooth_workspace_bytes(model, mode, T, N);
-    return bytes;
+    const size_t rec = box_record_bytes(model, T);
+    return rec > 0 ? (bytes + 255) / 256 * 256 + rec : bytes;
 }
 
 int irs_iterate(const irs_iterate_call* c, irs_timing* timing, void* stream) {
@@ -339,15 +353,18 @@ int irs_iterate(const irs_iterate_call* c, irs_timing* timing, void* stream) {
     int* smooth_info = ip; ip += T;
     int* descent_info = ip; ip += 4;
     int* box_flag = ip; ip += 4;
-    char* ws = static_cast<char*>(c->scratch) + (need - (exact ? 0 : irs_smooth_workspace_bytes(c->model, c->mode, T, c->N)));
+    const size_t rec_bytes = box_record_bytes(c->model, T);
     const size_t ws_bytes = exact ? 0 : irs_smooth_workspace_bytes(c->model, c->mode, T, c->N);
+    char* ws = static_cast<char*>(c->scratch) + scratch_front_bytes(c->model, c->mode, T);
+    void* recs = rec_bytes > 0 ? static_cast<char*>(c->scratch) + (need - rec_bytes) : nullptr;   // 256-aligned offset
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!exact) {
         rc = irs_workspace_init(ws, ws_bytes, stream);
         if (rc != IRS_OK) return rc;
     }
+    // the bounded descent runs on chip, or with its records in the tail of the scratch
     const bool box_fits = bounded && irs_tvlqr_box_lds_bytes(c->model, T) > 0 &&
-                          irs_tvlqr_box_lds_bytes(c->model, T) <= (size_t)(160 * 1024 - 512);
+                          (irs_tvlqr_box_lds_bytes(c->model, T) <= (size_t)(160 * 1024 - 512) || rec_bytes > 0);
     PhaseTimer tm(timing != nullptr, st);
     const size_t xs = (size_t)(T + 1) * n, us = (size_t)T * m;
     for (int it = 0; it < c->n_descents; ++it) {
@@ -376,12 +393,12 @@ int irs_iterate(const irs_iterate_call* c, irs_timing* timing, void* stream) {
                                    exact ? nullptr : smooth_info, box_fits ? 0 : 1, c->info_hist + (size_t)it * 8, st);
             if (rc != IRS_OK) return rc;
             if (box_fits) {
-                rc = irs_tvlqr_box_descent_if(c->model, c->params, c->n_params, T, At, Bt, ct, c->Q, c->Qd, c->R,
+                rc = irs_tvlqr_box_descent_ifw(c->model, c->params, c->n_params, T, At, Bt, ct, c->Q, c->Qd, c->R,
                                               c->alpha_R, c->xd_trj, x_nom, c->xlo, c->xhi, c->ulo, c->uhi,
                                               c->qp_rho > 0 ? c->qp_rho : 10.0, c->qp_relax > 0 ? c->qp_relax : 1.6,
                                               c->qp_max_iter > 0 ? c->qp_max_iter : 5000, c->qp_eps > 0 ? c->qp_eps : 1e-8,
-                                              x_new, u_new, c->cost_hist + it, c->info_hist + (size_t)it * 8 + 3, box_flag,
-                                              stream);       // its info lands in the row (zeroed above) if it runs
+                                               x_new, u_new, c->cost_hist + it, c->info_hist + (size_t)it * 8 + 3, box_flag,
+                                               recs, rec_bytes, stream);   // its info lands in the row (zeroed above) if it runs
                 if (rc != IRS_OK) return rc;
             }
         }

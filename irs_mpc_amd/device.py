@@ -167,35 +167,74 @@ class DeviceModel:
     # ---- box-constrained descent ----------------------------------------------
     BOX_LDS_LIMIT = 160 * 1024 - 512
 
-    def box_descent_supported(self, T):
-        return 0 < self.lib.irs_tvlqr_box_lds_bytes(self.model_id, int(T)) <= self.BOX_LDS_LIMIT
+    def box_descent_supported(self, T, du=False):
+        """Whether the bounded TV-LQR kernel runs horizon T: with its factor records on chip, or in a workspace in
+        HBM.  du: the position-controlled form (quasistatic solver 1)."""
+        T = int(T)
+        if not du and 0 < self.lib.irs_tvlqr_box_lds_bytes(self.model_id, T) <= self.BOX_LDS_LIMIT:
+            return True
+        return 0 < self.lib.irs_tvlqr_box_hbm_lds_bytes(self.model_id, T, 1 if du else 0) <= self.BOX_LDS_LIMIT
+
+    def box_horizon_limit(self, du=False):
+        """The longest horizon the bounded TV-LQR kernel runs (records in HBM; 0: the model has no such form)."""
+        q = lambda T: self.lib.irs_tvlqr_box_hbm_lds_bytes(self.model_id, T, 1 if du else 0)
+        if not 0 < q(1) <= self.BOX_LDS_LIMIT:
+            return 0
+        lo, hi = 1, 1 << 20                     # q grows linearly in T
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if q(mid) <= self.BOX_LDS_LIMIT else (lo, mid)
+        return lo
+
+    def _box_workspace(self, T, du, device, force=False):
+        """Cached per device: the bounded TV-LQR kernel's factor records, when they do not fit LDS (or `force`)."""
+        need = self.lib.irs_tvlqr_box_workspace_bytes(self.model_id, int(T), 1 if du else 0)
+        if force and need == 0:
+            # records that would fit on chip: T x the record stride (the query at 2^14 steps is exactly 2^14 strides)
+            stride = self.lib.irs_tvlqr_box_workspace_bytes(self.model_id, 1 << 14, 1 if du else 0) >> 14
+            need = (int(T) * stride + 255) // 256 * 256
+        if need == 0:
+            return None
+        ws = self._ws.get(("box", device))
+        if ws is None or ws.numel() < need:
+            ws = torch.empty((need,), dtype=torch.uint8, device=device)
+            self._ws[("box", device)] = ws
+        return ws
 
     def tvlqr_box_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, xlo, xhi, ulo, uhi, alpha_R=0.5,
-                          rho=10.0, relax=1.6, max_iter=5000, eps=1e-8):
+                          rho=10.0, relax=1.6, max_iter=5000, eps=1e-8, records_in_hbm=False):
         """local_descent with active abs bounds (T warm-started tail QPs by ADMM around one
-        Riccati factorisation).  Returns dict(x_new, u_new, info[3])."""
+        Riccati factorisation).  Beyond the LDS horizon the factor records go to a cached workspace in HBM;
+        records_in_hbm=True puts them there at any horizon (same result, bit for bit).  Returns
+        dict(x_new, u_new, info[3])."""
         T = At.shape[0]
         dev = At.device
         o = dict(x_new=torch.empty((T + 1, self.n), dtype=F64, device=dev),
                  u_new=torch.empty((T, self.m), dtype=F64, device=dev),
                  info=torch.empty((3,), dtype=torch.int32, device=dev))
-        check(self.lib.irs_tvlqr_box_descent(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
-                                             _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
-                                             float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(xlo, F64),
-                                             _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64), float(rho),
-                                             float(relax), int(max_iter), float(eps), _ptr(o["x_new"], F64),
-                                             _ptr(o["u_new"], F64), o["info"].data_ptr(), _stream()),
-              "irs_tvlqr_box_descent")
+        ws = self._box_workspace(T, False, dev, force=records_in_hbm)
+        check(self.lib.irs_tvlqr_box_descent_wsx(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
+                                                 _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
+                                                 float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(xlo, F64),
+                                                 _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64), float(rho),
+                                                 float(relax), int(max_iter), float(eps), _ptr(o["x_new"], F64),
+                                                 _ptr(o["u_new"], F64), o["info"].data_ptr(),
+                                                 ws.data_ptr() if ws is not None else None,
+                                                 ws.numel() if ws is not None else 0, _stream()),
+              "irs_tvlqr_box_descent_wsx")
         return o
 
     SOLVER_AUTO, SOLVER_ADMM, SOLVER_ACTIVE_SET, SOLVER_ACTIVE_SET_MFMA = 0, 1, 2, 3
 
     def quasistatic_descent_supported(self, T, solver=1):
         """Whether `solver` can run horizon T (3: always, for models that fit the matrix-core tile -- beyond
-        the LDS-resident size its records go to a workspace in HBM; 1, 2: while their data fit LDS)."""
+        the LDS-resident size its records go to a workspace in HBM; 1: likewise, up to box_horizon_limit(du=True);
+        2: while its data fit LDS)."""
         lds = self.lib.irs_quasistatic_box_lds_bytes(self.model_id, int(T), int(solver))
         if int(solver) == 3:
             return lds > 0
+        if int(solver) == 1 and lds > self.BOX_LDS_LIMIT:   # ADMM: its records in a workspace in HBM
+            return self.box_descent_supported(T, du=True)
         return 0 < lds <= self.BOX_LDS_LIMIT
 
     def _descent_workspace(self, T, solver, device):
@@ -213,8 +252,8 @@ class DeviceModel:
                                 max_iter=5000, eps=1e-8, out=None, act=None):
         """IrsLqrQuasistatic.local_descent after get_TV_matrices (irs_lqr_quasistatic.py:286-345) +
         eval_cost.  Bounds are absolute per-time rows ((T+1,n) / (T,m)) or None.  solver: 0 auto,
-        1 ADMM, 2 active set (one control box, no x bounds; lanes, LDS-resident), 3 the same on matrix-core
-        tiles (any horizon).  `act` (T,m) f64 in {-1,0,+1}, in/out: the active set the first tail starts
+        1 ADMM (beyond the LDS horizon with its records in HBM), 2 active set (one control box, no x bounds; lanes,
+        LDS-resident), 3 the same on matrix-core tiles (any horizon).  `act` (T,m) f64 in {-1,0,+1}, in/out: the active set the first tail starts
         from / converged to (hand it from one iteration's descent to the next; zeros = cold start).
         Returns dict(x_new, u_new, cost, info[3])."""
         T = At.shape[0]
@@ -229,7 +268,7 @@ class DeviceModel:
                          (u_hi, (T, self.m)), (du_lo, (T, self.m)), (du_hi, (T, self.m))):
             assert b is None or tuple(b.shape) == shape, (tuple(b.shape), shape)
         assert act is None or tuple(act.shape) == (T, self.m)
-        ws = self._descent_workspace(T, solver, dev) if int(solver) in (0, 3) else None
+        ws = self._descent_workspace(T, solver, dev) if int(solver) in (0, 1, 3) else None
         check(self.lib.irs_quasistatic_box_descent_wsx(
             self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64), _ptr(ct, F64), _ptr(Q, F64),
             _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(x_lo, F64), _ptr(x_hi, F64),

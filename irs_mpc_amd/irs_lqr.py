@@ -147,8 +147,8 @@ class IrsLqr:
             return o["x_new"], o["u_new"], o["cost"]
         if not self._dm.box_descent_supported(self.T):
             raise NotImplementedError(
-                "a box bound is active and horizon T=%d does not fit the LDS-resident factorisation of the "
-                "bounded TV-LQR kernel (tv_lqr.py:112-123)" % self.T)
+                "a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
+                "(factor records in HBM, ADMM vectors in LDS; tv_lqr.py:112-123)" % (self.T, self._dm.box_horizon_limit()))
         # genuine bounds (tv_lqr.py:112-123): T warm-started tail QPs, one launch
         ob = self._dm.tvlqr_box_descent(At, Bt, ct, self._Q, self._Qd, self._R, self._xd,
                                         x_trj[0].contiguous(), *box, alpha_R=0.5,
@@ -283,8 +283,8 @@ class IrsLqr:
                                  "definite; need more samples or a non-zero std)")
             if row[6] != 0:
                 raise NotImplementedError(
-                    "a box bound is active and horizon T=%d does not fit the LDS-resident factorisation of the "
-                    "bounded TV-LQR kernel (tv_lqr.py:112-123)" % self.T)
+                    "a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
+                    "(factor records in HBM, ADMM vectors in LDS; tv_lqr.py:112-123)" % (self.T, self._dm.box_horizon_limit()))
             if row[2] != 0 and row[5] != 0:
                 raise ValueError("TV_LQR failed. Optimization problem is not solved.")
             self.x_trj_lst.append(xs[i])

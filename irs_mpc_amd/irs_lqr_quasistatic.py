@@ -100,6 +100,9 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
                 self._solver = 3 if dm.quasistatic_descent_supported(params.T, 3) else (
                     2 if dm.quasistatic_descent_supported(params.T, 2) else 1)
         if not dm.quasistatic_descent_supported(params.T, self._solver):
+            if self._solver == 1:
+                raise NotImplementedError("horizon T=%d is beyond the limit T <= %d of solver 1 (ADMM: factor records "
+                                          "in HBM, its vectors in LDS)" % (params.T, dm.box_horizon_limit(du=True)))
             raise NotImplementedError("horizon T=%d does not fit the LDS-resident QP factorisation of solver %d"
                                       % (params.T, self._solver))
         self._setup(q_dynamics, params, params.x_trj_d)

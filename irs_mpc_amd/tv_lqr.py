@@ -7,8 +7,11 @@ GPU, whatever its options:
     of the resulting affine policy (irs_tvlqr_linear_rollout) -- exact;
   * an active `x_bound_abs` / `u_bound_abs` / `u_bound_rel`, and / or `indices_u_into_x` (the
     position-controlled form: cost on du_t = u_t - u_{t-1}, du_0 = u_0 - x0[idx], tv_lqr.py:96-108):
-    irs_tvlqr_box_solve -- ADMM around one Riccati factorisation (csrc/boxqp.hip), converged to `eps`
-    (OSQP's default is 1e-3; this runs to 1e-8).
+    irs_tvlqr_box_solve_wsx -- ADMM around one Riccati factorisation (csrc/boxqp.hip), converged to `eps`
+    (OSQP's default is 1e-3; this runs to 1e-8).  Its factor records stay in LDS while they fit and go to a
+    cached workspace in HBM beyond that, so the horizon is limited only by the ADMM vectors, which stay in LDS:
+    T <= 357 for the quadrotor (12, 4), 867 for (5, 2), 763 for (6, 2), 528 for (7, 4); position-controlled
+    (7, 4) T <= 383, (5, 2) T <= 679.  Longer horizons raise NotImplementedError.
 
 The reference's callers are the MPC loops of `local_descent`; those run as whole-descent kernels
 (irs_tvlqr_descent / irs_tvlqr_box_descent / irs_quasistatic_box_descent_wsx) and do not go through here.
@@ -108,19 +111,25 @@ def solve_tvlqr(At, Bt, ct, Q, Qd, R, x0, x_trj_d, solver=None, indices_u_into_x
     x_lo, x_hi = _rows(x_bound_abs, T + 1, n, dev)
     u_lo, u_hi = _rows(u_bound_abs, T, m, dev)
     du_lo, du_hi = _rows(u_bound_rel, T, m, dev) if position else (None, None)
+    if not dm.box_descent_supported(T, du=position):
+        raise NotImplementedError("solve_tvlqr with bounds: horizon T=%d is beyond the kernel's limit T <= %d"
+                                  % (T, dm.box_horizon_limit(du=position)))
     x_star = dev.to_dev(np.zeros((T + 1, n)))
     u_star = dev.to_dev(np.zeros((T, m)))
     import torch
     info = torch.full((3,), -1, dtype=torch.int32, device=x_star.device)
     lib = load()
     ptr = dev._ptr
-    check(lib.irs_tvlqr_box_solve(dm.model_id, dm._p, dm._np, T, ptr(At_d, dev.F64), ptr(Bt_d, dev.F64), ptr(ct_d, dev.F64),
+    ws = dm._box_workspace(T, position, x_star.device)        # None while the records fit on chip
+    check(lib.irs_tvlqr_box_solve_wsx(dm.model_id, dm._p, dm._np, T, ptr(At_d, dev.F64), ptr(Bt_d, dev.F64), ptr(ct_d, dev.F64),
                                   ptr(Q_d, dev.F64), ptr(Qd_d, dev.F64), ptr(R_d, dev.F64), 1.0 if position else 0.5,
                                   ptr(xd_d, dev.F64), ptr(x0_d, dev.F64), 1 if position else 0,
                                   ptr(x_lo, dev.F64), ptr(x_hi, dev.F64), ptr(u_lo, dev.F64), ptr(u_hi, dev.F64),
                                   ptr(du_lo, dev.F64), ptr(du_hi, dev.F64), float(rho), 1.6, int(max_iter), float(eps),
-                                  ptr(x_star, dev.F64), ptr(u_star, dev.F64), info.data_ptr(), dev._stream()),
-          "irs_tvlqr_box_solve")
+                                  ptr(x_star, dev.F64), ptr(u_star, dev.F64), info.data_ptr(),
+                                  ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                                  dev._stream()),
+          "irs_tvlqr_box_solve_wsx")
     i = info.cpu().numpy()
     if i[0] != 0 or i[2] != 0:
         raise ValueError("TV_LQR failed. Optimization problem is not solved.")
