@@ -287,8 +287,8 @@ size_t irs_tvlqr_box_lds_bytes(int model, int T);
 /* The bounded TV-LQR beyond the LDS horizon.  The kernel keeps one factor record per time step (the Riccati
  * factorisation every ADMM iteration sweeps) and the ADMM vectors.  With the records in a caller workspace in HBM
  * only the vectors stay in LDS: the horizon is limited by irs_tvlqr_box_hbm_lds_bytes(model, T, du) <= ~160 KB
- * instead (quadrotor T <= 357, bicycle T <= 867; position-controlled form, du = 1: planar hand T <= 383, box
- * pivoting T <= 679).  The sweeps stage the records back through LDS two steps ahead of use; the results are
+ * instead (irs_box_horizon_limit: quadrotor T <= 357, bicycle T <= 867; position-controlled form, du = 1: planar
+ * hand T <= 383, box pivoting T <= 679).  The sweeps stage the records back through LDS two steps ahead of use; the results are
  * bit-identical to the on-chip path.
  * irs_tvlqr_box_workspace_bytes: the record bytes when the records do not fit LDS, 0 when they do (or when the
  * model has no such form).  du = 0: the plain form of irs_tvlqr_box_descent; du = 1: the position-controlled
@@ -296,6 +296,20 @@ size_t irs_tvlqr_box_lds_bytes(int model, int T);
  * touches the GPU.                                                                                             */
 size_t irs_tvlqr_box_workspace_bytes(int model, int T, int du);
 size_t irs_tvlqr_box_hbm_lds_bytes(int model, int T, int du);
+/* The longest horizon a bounded-descent kind runs on `model`, with a workspace where the kind takes one; 0 when the
+ * model has no such form, INT_MAX for the matrix-core tiles (no cap).  One planner in csrc/boxqp.hip decides every
+ * placement, LDS size and cap of the bounded descents; this and the size queries above read it.  No GPU.
+ *   IRS_BOX_ADMM             irs_tvlqr_box_descent / _solve, plain form (records in HBM)
+ *   IRS_BOX_ADMM_DU          the position-controlled form: irs_quasistatic_box_descent solver 1 (records in HBM)
+ *   IRS_BOX_ACTIVE_SET       irs_quasistatic_box_descent solver 2 (on chip only)
+ *   IRS_BOX_ACTIVE_SET_MFMA  irs_quasistatic_box_descent solver 3                                               */
+typedef enum irs_box_kind {
+    IRS_BOX_ADMM = 0,
+    IRS_BOX_ADMM_DU = 1,
+    IRS_BOX_ACTIVE_SET = 2,
+    IRS_BOX_ACTIVE_SET_MFMA = 3
+} irs_box_kind;
+int irs_box_horizon_limit(int model, int kind);
 /* irs_tvlqr_box_descent / irs_tvlqr_box_solve with a workspace: DEV, 256-byte aligned, >= the record bytes of
  * this horizon (BoxLayout stride x T, rounded up to 256; irs_tvlqr_box_workspace_bytes where the records do not
  * fit LDS).  A workspace that is given is used, even where the records would fit on chip; NULL = the entry

@@ -27,6 +27,7 @@ MODEL_BOX_PUSH_EXACT = 10
 SMOOTH_ZERO_ORDER_AB = 0
 SMOOTH_FIRST_ORDER = 1
 SMOOTH_ZERO_ORDER_B = 2
+BOX_ADMM, BOX_ADMM_DU, BOX_ACTIVE_SET, BOX_ACTIVE_SET_MFMA = 0, 1, 2, 3     # irs_box_horizon_limit kinds
 
 _dp = c_void_p   # device pointers travel as plain addresses
 
@@ -130,6 +131,7 @@ SIGNATURES["irs_tvlqr_box_descent"] = (c_int, [c_int, POINTER(c_double), c_int, 
 SIGNATURES["irs_tvlqr_box_lds_bytes"] = (c_size_t, [c_int, c_int])
 SIGNATURES["irs_tvlqr_box_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int])
 SIGNATURES["irs_tvlqr_box_hbm_lds_bytes"] = (c_size_t, [c_int, c_int, c_int])
+SIGNATURES["irs_box_horizon_limit"] = (c_int, [c_int, c_int])
 SIGNATURES["irs_tvlqr_box_descent_wsx"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
                                                    c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_double, c_double, c_int,
                                                    c_double, _dp, _dp, _dp, _dp, c_size_t, c_void_p])

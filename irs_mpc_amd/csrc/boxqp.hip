@@ -30,6 +30,8 @@
 // advance, stage them back through a 3-slot LDS ring two steps ahead of use (global_load_dwordx4 into
 // registers, ds_write_b128 one step before the record is needed).  The arithmetic and its order are the same
 // on both paths: they give bit-identical results.
+#include <climits>
+
 #include "boxqp.hpp"
 
 namespace {
@@ -513,128 +515,125 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
     }
 }
 
-constexpr size_t kBoxLds = 160 * 1024 - 512;
-
-// sizes of the bounded TV-LQR kernel at one horizon: LDS with the records on chip, LDS with the records in HBM,
-// the HBM record bytes, and the longest horizon the HBM form runs
-struct BoxSizes { size_t lds, hbm_lds, records; int max_T; };
-
 template <class Model, bool DU, bool HBM>
 int launch_box_kernel(const BoxArgs& a, double* recs, size_t bytes, hipStream_t st) {
-    auto kern = box_descent_kernel<Model, DU, HBM>;
-    static size_t granted = 0;           // per instantiation: the attribute call is a driver round trip (fused iterate)
-    if (bytes > granted) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) {
-            irs_set_error("irs_tvlqr_box_descent: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return IRS_ERR_HIP;
-        }
-        granted = bytes;
-    }
+    constexpr auto kern = box_descent_kernel<Model, DU, HBM>;
+    const int rc = irs_raise_lds_limit<kern>(bytes, "irs_tvlqr_box_descent");
+    if (rc != IRS_OK) return rc;
     hipLaunchKernelGGL(kern, dim3(1), dim3(64), bytes, st, a, recs);
     return IRS_OK;
 }
 
-// the longest horizon the kernel runs with its records in HBM (the ADMM vectors stay in LDS)
-template <int N, int M>
-int box_hbm_max_T() {
-    using L = BoxLayout<N, M>;
-    return (int)((kBoxLds / sizeof(double) - L::hbm_doubles(0)) / (3 * N + 4 * M));
-}
-
-// ws == nullptr: records in LDS (the horizon must fit).  ws given: records in ws when force_ws or when they do not
-// fit LDS; ws must then hold BoxLayout::record_bytes(T).
 template <class Model, bool DU>
-int launch_box(const BoxArgs& a, double* ws, size_t ws_bytes, bool force_ws, hipStream_t st) {
-    constexpr int N = Model::NX + (DU ? Model::NU : 0), M = Model::NU;
-    using L = BoxLayout<N, M>;
-    const size_t bytes = L::doubles(a.T) * sizeof(double);
-    if (ws == nullptr || (!force_ws && bytes <= kBoxLds)) {
-        if (bytes > kBoxLds) {
-            irs_set_error("irs_tvlqr_box_descent: horizon T=%d needs %zu bytes of LDS (max ~160 KB) with its records on "
-                          "chip; give a workspace of %zu bytes (T <= %d)", a.T, bytes, L::record_bytes(a.T),
-                          box_hbm_max_T<N, M>());
-            return IRS_ERR_UNSUPPORTED;
-        }
-        return launch_box_kernel<Model, DU, false>(a, nullptr, bytes, st);
-    }
-    const size_t hbytes = L::hbm_doubles(a.T) * sizeof(double);
-    if (hbytes > kBoxLds) {
-        irs_set_error("irs_tvlqr_box_descent: horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d with its "
-                      "records in HBM (its ADMM vectors need %zu bytes of LDS, max ~160 KB)", a.T, box_hbm_max_T<N, M>(),
-                      hbytes);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    if (ws_bytes < L::record_bytes(a.T)) {
-        irs_set_error("irs_tvlqr_box_descent: workspace %zu < %zu bytes", ws_bytes, L::record_bytes(a.T));
-        return IRS_ERR_WORKSPACE;
-    }
-    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) {
-        irs_set_error("irs_tvlqr_box_descent: the workspace must be 256-byte aligned");
-        return IRS_ERR_INVALID_ARG;
-    }
-    return launch_box_kernel<Model, DU, true>(a, ws, hbytes, st);
+int launch_box(const BoxArgs& a, const BoxPlan& p, double* ws, hipStream_t st) {
+    if (p.place != BoxPlace::AdmmHbm) return launch_box_kernel<Model, DU, false>(a, nullptr, p.lds, st);
+    return launch_box_kernel<Model, DU, true>(a, ws, p.lds, st);
 }
 
+// The ADMM kernel: its records on chip when they fit LDS and no workspace is forced on them; otherwise in HBM,
+// where only the ADMM vectors stay in LDS (hbm_doubles grows by 3 N + 4 M per step: that caps the horizon).
 template <int N, int M>
-void fill_box_sizes(int T, BoxSizes* z) {
+BoxPlan admm_plan(int T, BoxWs ws) {
     using L = BoxLayout<N, M>;
-    z->lds = L::doubles(T) * sizeof(double);
-    z->hbm_lds = L::hbm_doubles(T) * sizeof(double);
-    z->records = L::record_bytes(T);
-    z->max_T = box_hbm_max_T<N, M>();
+    const size_t lds = L::doubles(T) * sizeof(double), hbm = L::hbm_doubles(T) * sizeof(double);
+    const int max_T = (int)((IRS_LDS_BUDGET / sizeof(double) - L::hbm_doubles(0)) / (3 * N + 4 * M));
+    if (ws == BoxWs::Always || (ws == BoxWs::IfNeeded && lds > IRS_LDS_BUDGET))
+        return {hbm <= IRS_LDS_BUDGET ? BoxPlace::AdmmHbm : BoxPlace::None, hbm, L::record_bytes(T), max_T};
+    if (lds <= IRS_LDS_BUDGET) return {BoxPlace::AdmmLds, lds, 0, max_T};
+    return {BoxPlace::None, lds, L::record_bytes(T), max_T};
 }
 
 }  // namespace
 
-// the plain (du = 0) or position-controlled (du = 1) form of `model`: IRS_OK, or IRS_ERR_UNSUPPORTED when the model
-// has no such form
-static int box_sizes(int model, int T, int du, BoxSizes* z) {
+// the plain (du = false) or position-controlled ADMM form of `model`; *p is left alone when it has no such form
+static int admm_plan_of(int model, int T, bool du, BoxWs ws, BoxPlan* p) {
+    IRS_DISPATCH_MODEL(model, {
+        if (!du) *p = admm_plan<Model::NX, Model::NU>(T, ws);
+        else if constexpr (has_u_into_x<Model>::value) *p = admm_plan<Model::NX + Model::NU, Model::NU>(T, ws);
+    });
+    return IRS_OK;
+}
+
+BoxPlan irs_box_plan(int model, int T, int kind, BoxWs ws) {
+    BoxPlan p{BoxPlace::None, 0, 0, 0};
+    if (irs_model_info(model, nullptr, nullptr, nullptr) != IRS_OK) return p;
+    if (kind == IRS_BOX_ADMM || kind == IRS_BOX_ADMM_DU) {
+        admm_plan_of(model, T, kind == IRS_BOX_ADMM_DU, ws, &p);
+    } else if (kind == IRS_BOX_ACTIVE_SET) {
+        // everything in LDS; the layout grows by the same record every step
+        const size_t lds = irs_ctrlbox_lds_bytes(model, T), base = irs_ctrlbox_lds_bytes(model, 0);
+        if (lds > 0)
+            p = {lds <= IRS_LDS_BUDGET ? BoxPlace::Lanes : BoxPlace::None, lds, 0,
+                 (int)((IRS_LDS_BUDGET - base) / (irs_ctrlbox_lds_bytes(model, 1) - base))};
+    } else if (kind == IRS_BOX_ACTIVE_SET_MFMA) {
+        // the records on chip while they fit, else in the workspace: no horizon cap
+        const size_t lds = irs_ctrlbox_mfma_lds_bytes(model, T), rec = irs_ctrlbox_mfma_record_bytes(model, T);
+        if (lds > 0 && lds <= IRS_LDS_BUDGET) p = {BoxPlace::TilesLds, lds, 0, INT_MAX};
+        else if (lds > 0 && ws != BoxWs::None) p = {BoxPlace::TilesHbm, lds - rec, rec, INT_MAX};
+        else if (lds > 0) p = {BoxPlace::None, lds, rec, INT_MAX};
+    }
+    return p;
+}
+
+// the ADMM kernel where the plan puts it: records on chip, or in `ws` -- whenever one is given (force_ws), or only
+// where they do not fit LDS
+static int run_admm(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, bool force_ws,
+                    hipStream_t st) {
+    const BoxPlan p = irs_box_plan(model, a.T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM,
+                                   ws == nullptr ? BoxWs::None : force_ws ? BoxWs::Always : BoxWs::IfNeeded);
+    if (p.max_T == 0) {
+        irs_set_error("%s: model %d is not position controlled", fn, model);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (p.place == BoxPlace::None) {
+        if (ws == nullptr)
+            irs_set_error("irs_tvlqr_box_descent: horizon T=%d needs %zu bytes of LDS (max ~160 KB) with its records on "
+                          "chip; give a workspace of %zu bytes (T <= %d)", a.T, p.lds, p.records, p.max_T);
+        else
+            irs_set_error("irs_tvlqr_box_descent: horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d with "
+                          "its records in HBM (its ADMM vectors need %zu bytes of LDS, max ~160 KB)", a.T, p.max_T, p.lds);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (p.place == BoxPlace::AdmmHbm && ws_bytes < p.records) {
+        irs_set_error("irs_tvlqr_box_descent: workspace %zu < %zu bytes", ws_bytes, p.records);
+        return IRS_ERR_WORKSPACE;
+    }
+    if (p.place == BoxPlace::AdmmHbm && (reinterpret_cast<uintptr_t>(ws) & 255) != 0) {
+        irs_set_error("irs_tvlqr_box_descent: the workspace must be 256-byte aligned");
+        return IRS_ERR_INVALID_ARG;
+    }
+    double* recs = static_cast<double*>(ws);
     int rc = IRS_ERR_UNSUPPORTED;
-    IRS_DISPATCH_MODEL(model, {
-        if (du == 0) {
-            fill_box_sizes<Model::NX, Model::NU>(T, z);
-            rc = IRS_OK;
-        } else if constexpr (has_u_into_x<Model>::value) {
-            fill_box_sizes<Model::NX + Model::NU, Model::NU>(T, z);
-            rc = IRS_OK;
-        }
-    });
-    return rc;
+    if (!du) {
+        IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, p, recs, st); });
+    } else {
+        IRS_DISPATCH_MODEL(model, {
+            if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, p, recs, st);
+        });
+    }
+    if (rc != IRS_OK) return rc;
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
 }
 
-extern "C" {
-
-size_t irs_tvlqr_box_lds_bytes(int model, int T) {
-    if (T <= 0) return 0;
-    size_t r = 0;
-    IRS_DISPATCH_MODEL(model, { r = BoxLayout<Model::NX, Model::NU>::doubles(T) * sizeof(double); });
-    return r;
-}
-
-size_t irs_quasistatic_box_lds_bytes(int model, int T, int solver) {
-    if (T <= 0) return 0;
-    if (solver == 2) return irs_ctrlbox_lds_bytes(model, T);
-    if (solver == 3) return irs_ctrlbox_mfma_lds_bytes(model, T);
-    size_t r = 0;
-    IRS_DISPATCH_MODEL(model, {
-        if constexpr (has_u_into_x<Model>::value)
-            r = BoxLayout<Model::NX + Model::NU, Model::NU>::doubles(T) * sizeof(double);
-    });
-    return r;
-}
-
-size_t irs_tvlqr_box_workspace_bytes(int model, int T, int du) {
-    BoxSizes z;
-    if (T <= 0 || box_sizes(model, T, du != 0, &z) != IRS_OK) return 0;
-    return z.lds <= kBoxLds ? 0 : z.records;
-}
-
-size_t irs_tvlqr_box_hbm_lds_bytes(int model, int T, int du) {
-    BoxSizes z;
-    if (T <= 0 || box_sizes(model, T, du != 0, &z) != IRS_OK) return 0;
-    return z.hbm_lds;
+// The BoxArgs every entry fills alike.  rows: bounds are per-time rows (strides n / m), else one constant row.  The
+// callers set what is theirs alone: single_tail, act_io, run_flag.
+static int box_args(BoxArgs* a, int model, const double* params, int n_params, int T, const double* At,
+                    const double* Bt, const double* ct, const double* Q, const double* Qd, const double* R, double alpha,
+                    const double* xd, const double* x0, const double* xlo, const double* xhi, const double* ulo,
+                    const double* uhi, const double* dlo, const double* dhi, bool rows, double rho, double relax,
+                    int max_iter, double eps, double* x_new, double* u_new, double* cost, int* info) {
+    *a = BoxArgs{};
+    const int rc = irs_load_params(model, params, n_params, &a->p);
+    if (rc != IRS_OK) return rc;
+    int n = 0, m = 0, np;
+    if (rows) irs_model_info(model, &n, &m, &np);
+    a->At = At; a->Bt = Bt; a->ct = ct; a->Q = Q; a->Qd = Qd; a->R = R; a->xd = xd; a->x0 = x0;
+    a->xlo = xlo; a->xhi = xhi; a->ulo = ulo; a->uhi = uhi; a->dlo = dlo; a->dhi = dhi;
+    a->sx = n; a->su = m; a->sd = m;
+    a->x_new = x_new; a->u_new = u_new; a->cost = cost; a->info = info;
+    a->alpha = alpha; a->rho = rho; a->relax = relax; a->eps = eps; a->T = T; a->max_iter = max_iter;
+    return IRS_OK;
 }
 
 // a workspace the records must go to: 256-byte aligned, large enough
@@ -644,17 +643,85 @@ static int check_box_workspace(const char* fn, int model, int T, int du, const v
         irs_set_error("%s: the workspace must be 256-byte aligned", fn);
         return IRS_ERR_INVALID_ARG;
     }
-    BoxSizes z;
-    const int rc = box_sizes(model, T, du, &z);
-    if (rc != IRS_OK) {
+    const BoxPlan p = irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::Always);
+    if (p.max_T == 0) {
         irs_set_error("%s: model %d has no %s form", fn, model, du ? "position-controlled" : "plain");
-        return rc;
+        return IRS_ERR_UNSUPPORTED;
     }
-    if (ws_bytes < z.records) {
-        irs_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, z.records);
+    if (ws_bytes < p.records) {
+        irs_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, p.records);
         return IRS_ERR_WORKSPACE;
     }
     return IRS_OK;
+}
+
+// solver 0 of the quasistatic descent: the tiles where the model fits them and their records have a place, else the
+// lanes where they fit LDS, else ADMM
+static int auto_solver(int model, int T, bool one_box, const void* ws, size_t ws_bytes) {
+    if (!one_box) return 1;
+    const BoxPlan tiles = irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, ws ? BoxWs::IfNeeded : BoxWs::None);
+    if (tiles.place != BoxPlace::None && ws_bytes >= tiles.records) return 3;
+    return irs_box_plan(model, T, IRS_BOX_ACTIVE_SET, BoxWs::None).place == BoxPlace::Lanes ? 2 : 1;
+}
+
+static int box_descent(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
+                       const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
+                       const double* xd_trj, const double* x0, const double* xlo, const double* xhi, const double* ulo,
+                       const double* uhi, double rho, double relax, int max_iter, double eps, double* x_new,
+                       double* u_new, double* cost, int* info, const int* run_flag, void* workspace,
+                       size_t workspace_bytes, bool force_ws, void* stream) {
+    BoxArgs a;
+    const int rc = box_args(&a, model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo,
+                            uhi, nullptr, nullptr, false, rho, relax, max_iter, eps, x_new, u_new, cost, info);
+    if (rc != IRS_OK) return rc;
+    a.run_flag = run_flag;
+    return run_admm("irs_tvlqr_box_descent", model, false, a, workspace, workspace_bytes, force_ws,
+                    static_cast<hipStream_t>(stream));
+}
+
+int irs_tvlqr_box_descent_ifw(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
+                              const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
+                              const double* xd_trj, const double* x0, const double* xlo, const double* xhi,
+                              const double* ulo, const double* uhi, double rho, double relax, int max_iter, double eps,
+                              double* x_new, double* u_new, double* cost, int* info, const int* run_flag,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
+                  x_new && u_new && info, "bad argument");
+    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+    return box_descent(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi, rho,
+                       relax, max_iter, eps, x_new, u_new, cost, info, run_flag, workspace, workspace_bytes, false,
+                       stream);
+}
+
+extern "C" {
+
+size_t irs_tvlqr_box_lds_bytes(int model, int T) {
+    return T > 0 ? irs_box_plan(model, T, IRS_BOX_ADMM, BoxWs::None).lds : 0;
+}
+
+size_t irs_quasistatic_box_lds_bytes(int model, int T, int solver) {
+    const int kind = solver == 2 ? IRS_BOX_ACTIVE_SET : solver == 3 ? IRS_BOX_ACTIVE_SET_MFMA : IRS_BOX_ADMM_DU;
+    return T > 0 ? irs_box_plan(model, T, kind, BoxWs::None).lds : 0;
+}
+
+size_t irs_tvlqr_box_workspace_bytes(int model, int T, int du) {
+    return T > 0 ? irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::IfNeeded).records : 0;
+}
+
+size_t irs_tvlqr_box_hbm_lds_bytes(int model, int T, int du) {
+    return T > 0 ? irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::Always).lds : 0;
+}
+
+size_t irs_quasistatic_descent_workspace_bytes(int model, int T, int solver) {
+    if (T <= 0 || solver < 0 || solver > 3 || solver == 2) return 0;
+    const size_t tiles = solver != 1 ? irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, BoxWs::IfNeeded).records : 0;
+    const size_t admm = solver != 3 ? irs_box_plan(model, T, IRS_BOX_ADMM_DU, BoxWs::IfNeeded).records : 0;
+    return tiles > admm ? tiles : admm;
+}
+
+int irs_box_horizon_limit(int model, int kind) {
+    return kind >= IRS_BOX_ADMM && kind <= IRS_BOX_ACTIVE_SET_MFMA ? irs_box_plan(model, 1, kind, BoxWs::IfNeeded).max_T
+                                                                   : 0;
 }
 
 int irs_tvlqr_box_descent(int model, const double* params, int n_params, int T, const double* At,
@@ -663,37 +730,8 @@ int irs_tvlqr_box_descent(int model, const double* params, int n_params, int T, 
                           const double* xlo, const double* xhi, const double* ulo, const double* uhi,
                           double rho, double relax, int max_iter, double eps, double* x_new,
                           double* u_new, int* info, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
-                  x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
     return irs_tvlqr_box_descent_if(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo,
                                     uhi, rho, relax, max_iter, eps, x_new, u_new, nullptr, info, nullptr, stream);
-}
-
-static int box_descent_impl(int model, const double* params, int n_params, int T, const double* At,
-                            const double* Bt, const double* ct, const double* Q, const double* Qd,
-                            const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                            const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                            double rho, double relax, int max_iter, double eps, double* x_new,
-                            double* u_new, double* cost, int* info, const int* run_flag, void* workspace,
-                            size_t workspace_bytes, bool force_ws, void* stream) {
-    BoxArgs a;
-    a.act_io = nullptr;
-    a.single_tail = 0;
-    a.run_flag = run_flag;
-    int rc = irs_load_params(model, params, n_params, &a.p);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi; a.dlo = nullptr; a.dhi = nullptr;
-    a.sx = 0; a.su = 0; a.sd = 0;
-    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info;
-    a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.eps = eps; a.T = T; a.max_iter = max_iter;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, ws, workspace_bytes, force_ws, st); });
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
 }
 
 int irs_tvlqr_box_descent_if(int model, const double* params, int n_params, int T, const double* At,
@@ -702,26 +740,9 @@ int irs_tvlqr_box_descent_if(int model, const double* params, int n_params, int 
                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
                              double rho, double relax, int max_iter, double eps, double* x_new,
                              double* u_new, double* cost, int* info, const int* run_flag, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
-                  x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
-    return box_descent_impl(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi,
-                            rho, relax, max_iter, eps, x_new, u_new, cost, info, run_flag, nullptr, 0, false, stream);
-}
-
-int irs_tvlqr_box_descent_ifw(int model, const double* params, int n_params, int T, const double* At,
-                              const double* Bt, const double* ct, const double* Q, const double* Qd,
-                              const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                              double rho, double relax, int max_iter, double eps, double* x_new,
-                              double* u_new, double* cost, int* info, const int* run_flag, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
-                  x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
-    return box_descent_impl(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi,
-                            rho, relax, max_iter, eps, x_new, u_new, cost, info, run_flag, workspace, workspace_bytes,
-                            false, stream);
+    return irs_tvlqr_box_descent_ifw(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi,
+                                     ulo, uhi, rho, relax, max_iter, eps, x_new, u_new, cost, info, run_flag, nullptr, 0,
+                                     stream);
 }
 
 int irs_tvlqr_box_descent_wsx(int model, const double* params, int n_params, int T, const double* At,
@@ -735,9 +756,9 @@ int irs_tvlqr_box_descent_wsx(int model, const double* params, int n_params, int
     IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
     int rc = check_box_workspace(__func__, model, T, 0, workspace, workspace_bytes);
     if (rc != IRS_OK) return rc;
-    return box_descent_impl(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi,
-                            rho, relax, max_iter, eps, x_new, u_new, nullptr, info, nullptr, workspace, workspace_bytes,
-                            true, stream);
+    return box_descent(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi, rho,
+                       relax, max_iter, eps, x_new, u_new, nullptr, info, nullptr, workspace, workspace_bytes, true,
+                       stream);
 }
 
 int irs_quasistatic_box_descent(int model, const double* params, int n_params, int T, const double* At,
@@ -765,20 +786,6 @@ int irs_quasistatic_box_descent_ws(int model, const double* params, int n_params
                                            u_new, cost, info, act_io, nullptr, 0, stream);
 }
 
-size_t irs_quasistatic_descent_workspace_bytes(int model, int T, int solver) {
-    if (T <= 0 || solver < 0 || solver > 3 || solver == 2) return 0;
-    size_t need = 0;
-    if (solver != 1) {            // matrix-core active set
-        const size_t lds = irs_ctrlbox_mfma_lds_bytes(model, T);
-        need = (lds == 0 || lds <= kBoxLds) ? 0 : irs_ctrlbox_mfma_record_bytes(model, T);
-    }
-    if (solver != 3) {            // ADMM: its factor records, when they do not fit LDS
-        const size_t rec = irs_tvlqr_box_workspace_bytes(model, T, 1);
-        need = rec > need ? rec : need;
-    }
-    return need;
-}
-
 int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_params, int T, const double* At,
                                     const double* Bt, const double* ct, const double* Q, const double* Qd,
                                     const double* R, const double* xd_trj, const double* x0,
@@ -794,19 +801,12 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
                   (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
     IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
     BoxArgs a;
-    a.act_io = act_io;
-    a.single_tail = 0;
-    a.run_flag = nullptr;
-    int rc = irs_load_params(model, params, n_params, &a.p);
+    int rc = box_args(&a, model, params, n_params, T, At, Bt, ct, Q, Qd, R,
+                      1.0,      // tv_lqr.py:107 adds du'R du as an expression: the full quadratic
+                      xd_trj, x0, x_lo, x_hi, u_lo, u_hi, du_lo, du_hi, true, rho, relax, max_iter, eps, x_new, u_new,
+                      cost, info);
     if (rc != IRS_OK) return rc;
-    int n, m, np;
-    irs_model_info(model, &n, &m, &np);
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.sx = n; a.su = m; a.sd = m;
-    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info;
-    a.alpha = 1.0;      // tv_lqr.py:107 adds du'R du as an expression: the full quadratic
-    a.rho = rho; a.relax = relax; a.eps = eps; a.T = T; a.max_iter = max_iter;
+    a.act_io = act_io;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // one control box (or none) and no state bounds: the exact active-set solvers apply
     const bool one_box = x_lo == nullptr && !(u_lo != nullptr && du_lo != nullptr);
@@ -814,69 +814,28 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
         irs_set_error("irs_quasistatic_box_descent: the active-set solvers handle ONE of u / du bounds and no x bounds");
         return IRS_ERR_UNSUPPORTED;
     }
-    const size_t kLds = (size_t)(160 * 1024 - 512);
+    if (solver == 0) solver = auto_solver(model, T, one_box, workspace, workspace_bytes);
+    if (solver == 1)    // records in the workspace only when they do not fit LDS
+        return run_admm("irs_quasistatic_box_descent", model, true, a, workspace, workspace_bytes, false, st);
+    const BoxPlan p = irs_box_plan(model, T, solver == 3 ? IRS_BOX_ACTIVE_SET_MFMA : IRS_BOX_ACTIVE_SET,
+                                   workspace != nullptr ? BoxWs::IfNeeded : BoxWs::None);
+    if (p.max_T == 0) {
+        irs_set_error(irs_box_plan(model, T, IRS_BOX_ADMM_DU, BoxWs::None).max_T > 0
+                          ? "irs_quasistatic_box_descent: model %d does not fit the 16 x 16 tile"
+                          : "irs_quasistatic_box_descent: model %d is not position controlled", model);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (p.place == BoxPlace::None || workspace_bytes < p.records) {
+        if (solver == 3)
+            irs_set_error("irs_quasistatic_box_descent: horizon T=%d needs a %zu-byte workspace for the matrix-core "
+                          "active-set solver (records do not fit LDS)", T, p.records);
+        else
+            irs_set_error("irs_quasistatic_box_descent: horizon T=%d needs %zu bytes of LDS (max ~160 KB)", T, p.lds);
+        return IRS_ERR_UNSUPPORTED;
+    }
     const int kind = du_lo != nullptr ? 1 : 0;
-    if (one_box && (solver == 3 || solver == 0)) {
-        // matrix-core tiles: records on chip when they fit, in the caller's workspace otherwise
-        const size_t lds = irs_ctrlbox_mfma_lds_bytes(model, T);
-        const bool fits = lds != 0 && (lds <= kLds ||
-                                       (workspace != nullptr && workspace_bytes >= irs_ctrlbox_mfma_record_bytes(model, T)));
-        if (solver == 3 || fits) {
-            rc = irs_ctrlbox_mfma_launch(model, a, kind, static_cast<double*>(workspace), workspace_bytes, st);
-            if (rc != IRS_OK) return rc;
-            IRS_CHECK_LAUNCH();
-            return IRS_OK;
-        }
-    }
-    if (solver == 2 || (solver == 0 && one_box && irs_ctrlbox_lds_bytes(model, T) <= kLds)) {
-        rc = irs_ctrlbox_launch(model, a, kind, st);
-        if (rc != IRS_OK) return rc;
-        IRS_CHECK_LAUNCH();
-        return IRS_OK;
-    }
-    rc = IRS_ERR_UNSUPPORTED;
-    IRS_DISPATCH_MODEL(model, {
-        if constexpr (has_u_into_x<Model>::value)      // records in the workspace only when they do not fit LDS
-            rc = launch_box<Model, true>(a, static_cast<double*>(workspace), workspace_bytes, false, st);
-        else irs_set_error("irs_quasistatic_box_descent: model %d is not position controlled", model);
-    });
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-// solve_tvlqr (irs_lqr/tv_lqr.py:30-145) stand-alone: ONE bounded QP, its plan returned.
-static int box_solve_impl(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                          const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                          const double* xd_trj, const double* x0, int position_controlled,
-                          const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
-                          const double* du_lo, const double* du_hi, double rho, double relax, int max_iter,
-                          double eps, double* x_star, double* u_star, int* info, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    BoxArgs a;
-    a.act_io = nullptr;
-    a.single_tail = 1;
-    a.run_flag = nullptr;
-    int rc = irs_load_params(model, params, n_params, &a.p);
-    if (rc != IRS_OK) return rc;
-    int n, m, np;
-    irs_model_info(model, &n, &m, &np);
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.sx = n; a.su = m; a.sd = m;
-    a.x_new = x_star; a.u_new = u_star; a.cost = nullptr; a.info = info;
-    a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.eps = eps; a.T = T; a.max_iter = max_iter;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* ws = static_cast<double*>(workspace);
-    rc = IRS_ERR_UNSUPPORTED;
-    if (position_controlled) {
-        IRS_DISPATCH_MODEL(model, {
-            if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, ws, workspace_bytes, true, st);
-            else irs_set_error("irs_tvlqr_box_solve: model %d is not position controlled", model);
-        });
-    } else {
-        IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, ws, workspace_bytes, true, st); });
-    }
+    rc = solver == 3 ? irs_ctrlbox_mfma_launch(model, a, kind, p, static_cast<double*>(workspace), st)
+                     : irs_ctrlbox_launch(model, a, kind, p, st);
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
@@ -893,6 +852,7 @@ int irs_tvlqr_box_solve(int model, const double* params, int n_params, int T, co
                                    x_star, u_star, info, nullptr, 0, stream);
 }
 
+// solve_tvlqr (irs_lqr/tv_lqr.py:30-145) stand-alone: ONE bounded QP, its plan returned.
 int irs_tvlqr_box_solve_wsx(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
                             const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
                             const double* xd_trj, const double* x0, int position_controlled,
@@ -907,9 +867,13 @@ int irs_tvlqr_box_solve_wsx(int model, const double* params, int n_params, int T
     IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
     int rc = check_box_workspace(__func__, model, T, position_controlled ? 1 : 0, workspace, workspace_bytes);
     if (rc != IRS_OK) return rc;
-    return box_solve_impl(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, position_controlled,
-                          x_lo, x_hi, u_lo, u_hi, du_lo, du_hi, rho, relax, max_iter, eps, x_star, u_star, info,
-                          workspace, workspace_bytes, stream);
+    BoxArgs a;
+    rc = box_args(&a, model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, x_lo, x_hi, u_lo, u_hi,
+                  du_lo, du_hi, true, rho, relax, max_iter, eps, x_star, u_star, nullptr, info);
+    if (rc != IRS_OK) return rc;
+    a.single_tail = 1;
+    return run_admm("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes, true,
+                    static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

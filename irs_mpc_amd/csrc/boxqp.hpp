@@ -37,16 +37,29 @@ template <class M>
 struct has_u_into_x<M, std::void_t<decltype(M::u_into_x(0))>> : std::true_type {};
 
 
+// Where a bounded descent runs: the ADMM kernel with its factor records on chip or in a workspace in HBM, the
+// active-set solver on lanes (always on chip), or on matrix-core tiles with its records on chip or in HBM.
+enum class BoxPlace { None, AdmmLds, AdmmHbm, Lanes, TilesLds, TilesHbm };
+// how the caller offers a workspace: none, for records that do not fit LDS, or for the records at any horizon
+enum class BoxWs { None, IfNeeded, Always };
+struct BoxPlan {
+    BoxPlace place;     // None: the horizon does not run this way (max_T == 0: the model has no such form)
+    size_t lds;         // dynamic LDS bytes of the launch (None: what the placement tried last would need)
+    size_t records;     // bytes the workspace must hold: the records when they do not stay on chip, else 0
+    int max_T;          // the longest horizon of the form, with a workspace where it takes one (INT_MAX: no cap)
+};
+// boxqp.hip: the one placement decision of every bounded descent and size query.  kind: IRS_BOX_*.  No HIP calls.
+BoxPlan irs_box_plan(int model, int T, int kind, BoxWs ws);
+
 // ctrlbox.hip: active-set solver for the quasistatic descent with ONE control box.
 // kind 0: bounds on u_t (a.ulo/a.uhi), kind 1: bounds on u_t - u_{t-1} (a.dlo/a.dhi); a bound pair
-// may be null (unbounded).  Returns IRS_ERR_UNSUPPORTED (message set) if the model is not position
-// controlled or the horizon does not fit LDS.
-int irs_ctrlbox_launch(int model, const BoxArgs& a, int kind, hipStream_t st);
+// may be null (unbounded).  Launches with the plan's LDS bytes (place Lanes).
+int irs_ctrlbox_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, hipStream_t st);
 size_t irs_ctrlbox_lds_bytes(int model, int T);
 
 // ctrlbox_mfma.hip: the same active-set method with every step riding in one 16 x 16 matrix-core tile.
 // record_bytes: size of the per-step records (0 = the model does not fit the tile); lds_bytes: LDS needed
-// to keep them on chip (beyond the CU's 160 KB the caller supplies `ws`, >= record_bytes, in HBM).
+// to keep them on chip.  Launches as planned: TilesLds, or TilesHbm with the records in `ws`.
 size_t irs_ctrlbox_mfma_record_bytes(int model, int T);
 size_t irs_ctrlbox_mfma_lds_bytes(int model, int T);
-int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, double* ws, size_t ws_bytes, hipStream_t st);
+int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, hipStream_t st);

@@ -659,33 +659,22 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
 }
 
 template <class Model, int KIND>
-int launch_ctrlbox(const BoxArgs& a, hipStream_t st) {
-    const size_t bytes = CbLayout<Model::NX, Model::NU>::doubles(a.T) * sizeof(double);
-    if (bytes > 160 * 1024 - 512) {
-        irs_set_error("irs_quasistatic_box_descent: horizon T=%d needs %zu bytes of LDS (max ~160 KB)", a.T, bytes);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    auto kern = ctrlbox_descent_kernel<Model, KIND>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-        irs_set_error("irs_quasistatic_box_descent: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        return IRS_ERR_HIP;
-    }
+int launch_ctrlbox(const BoxArgs& a, size_t bytes, hipStream_t st) {
+    constexpr auto kern = ctrlbox_descent_kernel<Model, KIND>;
+    const int rc = irs_raise_lds_limit<kern>(bytes, "irs_quasistatic_box_descent");
+    if (rc != IRS_OK) return rc;
     hipLaunchKernelGGL(kern, dim3(1), dim3(128), bytes, st, a);
     return IRS_OK;
 }
 
 }  // namespace
 
-int irs_ctrlbox_launch(int model, const BoxArgs& a, int kind, hipStream_t st) {
+int irs_ctrlbox_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, hipStream_t st) {
     int rc = IRS_ERR_UNSUPPORTED;
     IRS_DISPATCH_MODEL(model, {
-        if constexpr (has_u_into_x<Model>::value) {
-            rc = kind == KIND_ABS ? launch_ctrlbox<Model, KIND_ABS>(a, st) : launch_ctrlbox<Model, KIND_REL>(a, st);
-        } else {
-            irs_set_error("irs_quasistatic_box_descent: model %d is not position controlled", model);
-        }
+        if constexpr (has_u_into_x<Model>::value)
+            rc = kind == KIND_ABS ? launch_ctrlbox<Model, KIND_ABS>(a, p.lds, st)
+                                  : launch_ctrlbox<Model, KIND_REL>(a, p.lds, st);
     });
     return rc;
 }

@@ -1241,8 +1241,6 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
 #endif
 }
 
-constexpr size_t kLdsMax = 160 * 1024 - 512;
-
 // diagnostic build: a device buffer for the stamps, printed (and reset) by irs_cbm_print_stamps()
 #ifdef IRS_CBM_STAMPS
 static long long* g_stamps = nullptr;
@@ -1258,28 +1256,15 @@ static long long* cbm_stamps() { return nullptr; }
 #endif
 
 template <class Model, int KIND>
-int launch_ctrlbox_mfma(const BoxArgs& a, double* ws, size_t ws_bytes, hipStream_t st) {
-    using L = MfLayout<Model::NX, Model::NU>;
-    const size_t rec = L::rec_doubles(a.T) * sizeof(double), small = L::small * sizeof(double);
-    const bool in_lds = rec + small <= kLdsMax;
-    if (!in_lds && (ws == nullptr || ws_bytes < rec)) {
-        irs_set_error("irs_quasistatic_box_descent: horizon T=%d needs a %zu-byte workspace for the matrix-core "
-                      "active-set solver (records do not fit LDS)", a.T, rec);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    const size_t bytes = in_lds ? rec + small : small;
-    if (in_lds) {
-        auto kern = ctrlbox_mfma_kernel<Model, KIND, true>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        if (e != hipSuccess) {
-            irs_set_error("irs_quasistatic_box_descent: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return IRS_ERR_HIP;
-        }
-        hipLaunchKernelGGL(kern, dim3(1), dim3(128), bytes, st, a, (double*)nullptr, cbm_stamps());
+int launch_ctrlbox_mfma(const BoxArgs& a, const BoxPlan& p, double* ws, hipStream_t st) {
+    if (p.place == BoxPlace::TilesLds) {
+        constexpr auto kern = ctrlbox_mfma_kernel<Model, KIND, true>;
+        const int rc = irs_raise_lds_limit<kern>(p.lds, "irs_quasistatic_box_descent");
+        if (rc != IRS_OK) return rc;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(128), p.lds, st, a, (double*)nullptr, cbm_stamps());
     } else {
         auto kern = ctrlbox_mfma_kernel<Model, KIND, false>;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(128), bytes, st, a, ws, cbm_stamps());
+        hipLaunchKernelGGL(kern, dim3(1), dim3(128), p.lds, st, a, ws, cbm_stamps());
     }
     return IRS_OK;
 }
@@ -1298,7 +1283,7 @@ size_t irs_ctrlbox_mfma_record_bytes(int model, int T) {
     return r;
 }
 
-// bytes of LDS the records need to stay on chip (0 = model unsupported); > kLdsMax: a workspace is needed
+// bytes of LDS the records need to stay on chip (0 = model unsupported); beyond the budget: a workspace is needed
 size_t irs_ctrlbox_mfma_lds_bytes(int model, int T) {
     size_t r = 0;
     IRS_DISPATCH_MODEL(model, {
@@ -1310,18 +1295,13 @@ size_t irs_ctrlbox_mfma_lds_bytes(int model, int T) {
     return r;
 }
 
-int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, double* ws, size_t ws_bytes, hipStream_t st) {
+int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, hipStream_t st) {
     int rc = IRS_ERR_UNSUPPORTED;
     IRS_DISPATCH_MODEL(model, {
         if constexpr (has_u_into_x<Model>::value) {
-            if constexpr (MfLayout<Model::NX, Model::NU>::FITS) {
-                rc = kind == KIND_ABS_M ? launch_ctrlbox_mfma<Model, KIND_ABS_M>(a, ws, ws_bytes, st)
-                                        : launch_ctrlbox_mfma<Model, KIND_REL_M>(a, ws, ws_bytes, st);
-            } else {
-                irs_set_error("irs_quasistatic_box_descent: model %d does not fit the 16 x 16 tile", model);
-            }
-        } else {
-            irs_set_error("irs_quasistatic_box_descent: model %d is not position controlled", model);
+            if constexpr (MfLayout<Model::NX, Model::NU>::FITS)
+                rc = kind == KIND_ABS_M ? launch_ctrlbox_mfma<Model, KIND_ABS_M>(a, p, ws, st)
+                                        : launch_ctrlbox_mfma<Model, KIND_REL_M>(a, p, ws, st);
         }
     });
     return rc;

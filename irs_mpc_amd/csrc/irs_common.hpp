@@ -1,6 +1,7 @@
 // Shared host-side helpers for the C ABI implementation files.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include "../../include/irs_hip.h"
@@ -16,13 +17,37 @@ int irs_tvlqr_descent_row(int model, const double* params, int n_params, int T, 
 
 // boxqp.hip, for iterate.hip: irs_tvlqr_box_descent_if whose records go to `workspace` (may be null) when they do
 // not fit LDS
-extern "C" int irs_tvlqr_box_descent_ifw(int model, const double* params, int n_params, int T, const double* At,
-                              const double* Bt, const double* ct, const double* Q, const double* Qd,
-                              const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                              double rho, double relax, int max_iter, double eps, double* x_new,
-                              double* u_new, double* cost, int* info, const int* run_flag, void* workspace,
-                              size_t workspace_bytes, void* stream);
+int irs_tvlqr_box_descent_ifw(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
+                              const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
+                              const double* xd_trj, const double* x0, const double* xlo, const double* xhi,
+                              const double* ulo, const double* uhi, double rho, double relax, int max_iter, double eps,
+                              double* x_new, double* u_new, double* cost, int* info, const int* run_flag,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+// The dynamic LDS one workgroup of the bounded-descent kernels may take (160 KB per CU, less a margin).
+constexpr size_t IRS_LDS_BUDGET = 160 * 1024 - 512;
+
+// Raises KERN's dynamic-LDS limit to `bytes` before a launch.  The attribute call is a driver round trip, so the
+// granted size is cached per kernel and per device; devices beyond the table call the driver every time.
+template <auto KERN>
+int irs_raise_lds_limit(size_t bytes, const char* fn) {
+    constexpr int kDevices = 16;
+    static std::atomic<size_t> granted[kDevices];
+    int dev = -1;
+    const bool cached = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kDevices;
+    if (cached && bytes <= granted[dev].load(std::memory_order_relaxed)) return IRS_OK;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERN),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) {
+        irs_set_error("%s: hipFuncSetAttribute: %s", fn, hipGetErrorString(e));
+        return IRS_ERR_HIP;
+    }
+    if (cached) {
+        size_t g = granted[dev].load(std::memory_order_relaxed);
+        while (g < bytes && !granted[dev].compare_exchange_weak(g, bytes, std::memory_order_relaxed)) {}
+    }
+    return IRS_OK;
+}
 
 #define IRS_CHECK_ARG(cond, msg)                               \
     do {                                                       \

@@ -8,7 +8,7 @@
 // The reference's loop (Python, one QP per timestep per iteration) is what this replaces; the host twin
 // irs_mpc_amd/irs_lqr.py routes IrsLqr*.iterate here whenever the sampling object can be drawn on the device
 // (GaussianSmoothing) or the linearisation is exact.
-#include "irs_common.hpp"
+#include "boxqp.hpp"
 
 namespace {
 
@@ -205,17 +205,9 @@ static int plan_check16_launch(int m, int T, size_t bytes, const double* At, con
                                const double* xhi, const double* ulo, const double* uhi, int* flag,
                                const int* descent_info, const int* smooth_info, int box_unsupported, int* row,
                                hipStream_t st) {
-    static bool attr = false;
-    auto kern = plan_check16_kernel<NN>;
-    if (!attr) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        if (e != hipSuccess) {
-            irs_set_error("plan check: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            return IRS_ERR_HIP;
-        }
-        attr = true;
-    }
+    constexpr auto kern = plan_check16_kernel<NN>;
+    const int rc = irs_raise_lds_limit<kern>(150 * 1024, "plan check");
+    if (rc != IRS_OK) return rc;
     // as many 64-lane waves as there are groups of four tails, at most 16
     const int waves = (T + 3) / 4 < 16 ? (T + 3) / 4 : 16;
     hipLaunchKernelGGL(kern, dim3(1), dim3(64 * waves), bytes, st, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag,
@@ -280,10 +272,7 @@ struct PhaseTimer {
 
 // the bounded descent's factor records where they do not fit LDS but its HBM form runs (0 otherwise): the tail of
 // the scratch, 256-byte aligned (every part before it is a multiple of 256 bytes)
-size_t box_record_bytes(int model, int T) {
-    const size_t rec = irs_tvlqr_box_workspace_bytes(model, T, 0);
-    return (rec > 0 && irs_tvlqr_box_hbm_lds_bytes(model, T, 0) <= (size_t)(160 * 1024 - 512)) ? rec : 0;
-}
+size_t box_record_bytes(const BoxPlan& p) { return p.place == BoxPlace::AdmmHbm ? p.records : 0; }
 
 }  // namespace
 
@@ -316,7 +305,7 @@ size_t irs_iterate_scratch_bytes(int model, int mode, int T, int N) {
     size_t bytes = scratch_front_bytes(model, mode, T);
     if (bytes == 0) return 0;
     if (mode != IRS_ITERATE_EXACT) bytes += irs_smooth_workspace_bytes(model, mode, T, N);
-    const size_t rec = box_record_bytes(model, T);
+    const size_t rec = box_record_bytes(irs_box_plan(model, T, IRS_BOX_ADMM, BoxWs::IfNeeded));
     return rec > 0 ? (bytes + 255) / 256 * 256 + rec : bytes;
 }
 
@@ -353,7 +342,8 @@ int irs_iterate(const irs_iterate_call* c, irs_timing* timing, void* stream) {
     int* smooth_info = ip; ip += T;
     int* descent_info = ip; ip += 4;
     int* box_flag = ip; ip += 4;
-    const size_t rec_bytes = box_record_bytes(c->model, T);
+    const BoxPlan box = irs_box_plan(c->model, T, IRS_BOX_ADMM, BoxWs::IfNeeded);
+    const size_t rec_bytes = box_record_bytes(box);
     const size_t ws_bytes = exact ? 0 : irs_smooth_workspace_bytes(c->model, c->mode, T, c->N);
     char* ws = static_cast<char*>(c->scratch) + scratch_front_bytes(c->model, c->mode, T);
     void* recs = rec_bytes > 0 ? static_cast<char*>(c->scratch) + (need - rec_bytes) : nullptr;   // 256-aligned offset
@@ -363,8 +353,7 @@ int irs_iterate(const irs_iterate_call* c, irs_timing* timing, void* stream) {
         if (rc != IRS_OK) return rc;
     }
     // the bounded descent runs on chip, or with its records in the tail of the scratch
-    const bool box_fits = bounded && irs_tvlqr_box_lds_bytes(c->model, T) > 0 &&
-                          (irs_tvlqr_box_lds_bytes(c->model, T) <= (size_t)(160 * 1024 - 512) || rec_bytes > 0);
+    const bool box_fits = bounded && box.place != BoxPlace::None;
     PhaseTimer tm(timing != nullptr, st);
     const size_t xs = (size_t)(T + 1) * n, us = (size_t)T * m;
     for (int it = 0; it < c->n_descents; ++it) {

@@ -165,26 +165,18 @@ class DeviceModel:
         return o
 
     # ---- box-constrained descent ----------------------------------------------
+    # the dynamic-LDS budget of the bounded-descent kernels (IRS_LDS_BUDGET in csrc/irs_common.hpp), for callers that
+    # compare the size queries with it; every placement decision reads irs_box_horizon_limit instead
     BOX_LDS_LIMIT = 160 * 1024 - 512
 
     def box_descent_supported(self, T, du=False):
         """Whether the bounded TV-LQR kernel runs horizon T: with its factor records on chip, or in a workspace in
         HBM.  du: the position-controlled form (quasistatic solver 1)."""
-        T = int(T)
-        if not du and 0 < self.lib.irs_tvlqr_box_lds_bytes(self.model_id, T) <= self.BOX_LDS_LIMIT:
-            return True
-        return 0 < self.lib.irs_tvlqr_box_hbm_lds_bytes(self.model_id, T, 1 if du else 0) <= self.BOX_LDS_LIMIT
+        return 0 < int(T) <= self.box_horizon_limit(du)
 
     def box_horizon_limit(self, du=False):
         """The longest horizon the bounded TV-LQR kernel runs (records in HBM; 0: the model has no such form)."""
-        q = lambda T: self.lib.irs_tvlqr_box_hbm_lds_bytes(self.model_id, T, 1 if du else 0)
-        if not 0 < q(1) <= self.BOX_LDS_LIMIT:
-            return 0
-        lo, hi = 1, 1 << 20                     # q grows linearly in T
-        while hi - lo > 1:
-            mid = (lo + hi) // 2
-            lo, hi = (mid, hi) if q(mid) <= self.BOX_LDS_LIMIT else (lo, mid)
-        return lo
+        return self.lib.irs_box_horizon_limit(self.model_id, _lib.BOX_ADMM_DU if du else _lib.BOX_ADMM)
 
     def _box_workspace(self, T, du, device, force=False):
         """Cached per device: the bounded TV-LQR kernel's factor records, when they do not fit LDS (or `force`)."""
@@ -224,18 +216,38 @@ class DeviceModel:
               "irs_tvlqr_box_descent_wsx")
         return o
 
+    def tvlqr_box_solve(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo=None, x_hi=None, u_lo=None, u_hi=None,
+                        du_lo=None, du_hi=None, position_controlled=False, alpha_R=0.5, rho=10.0, relax=1.6,
+                        max_iter=5000, eps=1e-8):
+        """solve_tvlqr stand-alone: ONE bounded QP by ADMM, its plan returned.  Bounds are per-time rows or None;
+        du bounds need the position-controlled form.  Beyond the LDS horizon the factor records go to a cached
+        workspace in HBM.  Returns dict(x_star, u_star, info[3])."""
+        T = At.shape[0]
+        dev = At.device
+        o = dict(x_star=torch.zeros((T + 1, At.shape[1]), dtype=F64, device=dev),
+                 u_star=torch.zeros((T, Bt.shape[2]), dtype=F64, device=dev),
+                 info=torch.full((3,), -1, dtype=torch.int32, device=dev))
+        ws = self._box_workspace(T, position_controlled, dev)        # None while the records fit on chip
+        check(self.lib.irs_tvlqr_box_solve_wsx(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
+                                               _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
+                                               float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64),
+                                               1 if position_controlled else 0, _ptr(x_lo, F64), _ptr(x_hi, F64),
+                                               _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64),
+                                               float(rho), float(relax), int(max_iter), float(eps),
+                                               _ptr(o["x_star"], F64), _ptr(o["u_star"], F64), o["info"].data_ptr(),
+                                               ws.data_ptr() if ws is not None else None,
+                                               ws.numel() if ws is not None else 0, _stream()),
+              "irs_tvlqr_box_solve_wsx")
+        return o
+
     SOLVER_AUTO, SOLVER_ADMM, SOLVER_ACTIVE_SET, SOLVER_ACTIVE_SET_MFMA = 0, 1, 2, 3
 
     def quasistatic_descent_supported(self, T, solver=1):
         """Whether `solver` can run horizon T (3: always, for models that fit the matrix-core tile -- beyond
         the LDS-resident size its records go to a workspace in HBM; 1: likewise, up to box_horizon_limit(du=True);
         2: while its data fit LDS)."""
-        lds = self.lib.irs_quasistatic_box_lds_bytes(self.model_id, int(T), int(solver))
-        if int(solver) == 3:
-            return lds > 0
-        if int(solver) == 1 and lds > self.BOX_LDS_LIMIT:   # ADMM: its records in a workspace in HBM
-            return self.box_descent_supported(T, du=True)
-        return 0 < lds <= self.BOX_LDS_LIMIT
+        kind = {2: _lib.BOX_ACTIVE_SET, 3: _lib.BOX_ACTIVE_SET_MFMA}.get(int(solver), _lib.BOX_ADMM_DU)
+        return 0 < int(T) <= self.lib.irs_box_horizon_limit(self.model_id, kind)
 
     def _descent_workspace(self, T, solver, device):
         need = self.lib.irs_quasistatic_descent_workspace_bytes(self.model_id, int(T), int(solver))

@@ -23,7 +23,6 @@ tied to x, u inside the `indices_u_into_x` branch, tv_lqr.py:93-104), i.e. it ha
 import numpy as np
 
 from . import device as dev
-from ._lib import check, dbl_array, load
 
 _SOLVERS = ("osqp", "snopt", "clp", "gurobi")
 
@@ -114,23 +113,10 @@ def solve_tvlqr(At, Bt, ct, Q, Qd, R, x0, x_trj_d, solver=None, indices_u_into_x
     if not dm.box_descent_supported(T, du=position):
         raise NotImplementedError("solve_tvlqr with bounds: horizon T=%d is beyond the kernel's limit T <= %d"
                                   % (T, dm.box_horizon_limit(du=position)))
-    x_star = dev.to_dev(np.zeros((T + 1, n)))
-    u_star = dev.to_dev(np.zeros((T, m)))
-    import torch
-    info = torch.full((3,), -1, dtype=torch.int32, device=x_star.device)
-    lib = load()
-    ptr = dev._ptr
-    ws = dm._box_workspace(T, position, x_star.device)        # None while the records fit on chip
-    check(lib.irs_tvlqr_box_solve_wsx(dm.model_id, dm._p, dm._np, T, ptr(At_d, dev.F64), ptr(Bt_d, dev.F64), ptr(ct_d, dev.F64),
-                                  ptr(Q_d, dev.F64), ptr(Qd_d, dev.F64), ptr(R_d, dev.F64), 1.0 if position else 0.5,
-                                  ptr(xd_d, dev.F64), ptr(x0_d, dev.F64), 1 if position else 0,
-                                  ptr(x_lo, dev.F64), ptr(x_hi, dev.F64), ptr(u_lo, dev.F64), ptr(u_hi, dev.F64),
-                                  ptr(du_lo, dev.F64), ptr(du_hi, dev.F64), float(rho), 1.6, int(max_iter), float(eps),
-                                  ptr(x_star, dev.F64), ptr(u_star, dev.F64), info.data_ptr(),
-                                  ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
-                                  dev._stream()),
-          "irs_tvlqr_box_solve_wsx")
-    i = info.cpu().numpy()
+    o = dm.tvlqr_box_solve(At_d, Bt_d, ct_d, Q_d, Qd_d, R_d, xd_d, x0_d, x_lo, x_hi, u_lo, u_hi, du_lo, du_hi,
+                           position_controlled=position, alpha_R=1.0 if position else 0.5, rho=rho,
+                           max_iter=max_iter, eps=eps)
+    i = o["info"].cpu().numpy()
     if i[0] != 0 or i[2] != 0:
         raise ValueError("TV_LQR failed. Optimization problem is not solved.")
-    return x_star.cpu().numpy(), u_star.cpu().numpy()
+    return o["x_star"].cpu().numpy(), o["u_star"].cpu().numpy()

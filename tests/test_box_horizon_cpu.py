@@ -1,12 +1,19 @@
 """CPU-side checks of the bounded TV-LQR beyond the LDS horizon (csrc/boxqp.hip with its factor records in a
-workspace in HBM): the size queries and the argument checks of the workspace entries.  No GPU is touched."""
+workspace in HBM): the size queries, the placement table of the bounded descents and the argument checks of the
+workspace entries.  No GPU is touched: every call is a size query or is rejected before any HIP call."""
+import ctypes
+import json
 import os
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LDS_LIMIT = 160 * 1024 - 512
 QUAD, BICYCLE, HAND, BOX_PIVOT = 1, 2, 4, 5
+N_MODELS = 11
+INT_MAX = 2 ** 31 - 1
+GOLDEN = os.path.join(ROOT, "tests", "golden", "box_plan_table.json")
 
 
 @pytest.fixture(scope="module")
@@ -100,3 +107,142 @@ def test_wsx_argument_checks_without_gpu(lib):
     # the bicycle has no position-controlled form
     assert lib.irs_tvlqr_box_solve_wsx(BICYCLE, bike, 1, 10, *a, 1.0, one, one, 1, None, None, one, one,
                                        None, None, 100.0, 1.6, 100, 1e-8, one, one, one, ws, 1 << 20, None) == -3
+    # the legacy entries: the same checks before anything runs
+    assert lib.irs_tvlqr_box_descent(BICYCLE, bike, 1, 30, None, *a[:5], 0.5, one, one, one, one, one, one,
+                                     10.0, 1.6, 100, 1e-8, one, one, one, None) == -1
+    assert lib.irs_tvlqr_box_descent(BICYCLE, bike, 1, 30, *a, 0.5, one, one, one, one, one, one,
+                                     10.0, 2.0, 100, 1e-8, one, one, one, None) == -1        # relax < 2
+    assert lib.irs_tvlqr_box_descent_if(BICYCLE, bike, 1, 30, *a, 0.5, one, one, one, one, one, one,
+                                        10.0, 1.6, 100, 1e-8, one, one, None, None, None, None) == -1
+    assert lib.irs_tvlqr_box_descent_if(11, bike, 1, 30, *a, 0.5, one, one, one, one, one, one,
+                                        10.0, 1.6, 100, 1e-8, one, one, None, one, None, None) == -3
+    assert b"unknown model" in lib.irs_last_error()
+    assert lib.irs_tvlqr_box_solve(HAND, ph, 12, 10, None, *a[:5], 1.0, one, one, 1, None, None, one, one,
+                                   None, None, 100.0, 1.6, 100, 1e-8, one, one, one, None) == -1
+    assert lib.irs_tvlqr_box_solve(BICYCLE, bike, 1, 10, *a, 1.0, one, one, 1, None, None, one, one,
+                                   None, None, 100.0, 1.6, 100, 1e-8, one, one, one, None) == -3
+    # past the caps: the plain form at T = 358 on the quadrotor, with or without a workspace
+    nq = lib_nparams(lib, QUAD)
+    quad = dbl_array([0.1] * nq)
+    assert lib.irs_tvlqr_box_descent_wsx(QUAD, quad, nq, 358, *a, 0.5, one, one, one, one, one, one,
+                                         10.0, 1.6, 100, 1e-8, one, one, one, ws, 1 << 30, None) == -3
+    assert lib.irs_tvlqr_box_descent(QUAD, quad, nq, 51, *a, 0.5, one, one, one, one, one, one,
+                                     10.0, 1.6, 100, 1e-8, one, one, one, None) == -3
+    assert b"workspace" in lib.irs_last_error()
+    # irs_quasistatic_box_descent_ws / _wsx: null pointers, an unknown solver, two boxes for the active set, a
+    # model that is not position controlled, horizons the chosen solver cannot take
+    q = [one] * 8
+    assert lib.irs_quasistatic_box_descent_ws(HAND, ph, 12, 10, None, *q[:7], None, None, None, None, None, None,
+                                              0, 10.0, 1.6, 100, 1e-8, one, one, None, one, None, None) == -1
+    assert lib.irs_quasistatic_box_descent_ws(HAND, ph, 12, 10, *q, None, None, None, None, None, None,
+                                              4, 10.0, 1.6, 100, 1e-8, one, one, None, one, None, None) == -1
+    assert lib.irs_quasistatic_box_descent_ws(HAND, ph, 12, 10, *q, None, None, one, one, one, one,
+                                              3, 10.0, 1.6, 100, 1e-8, one, one, None, one, None, None) == -3
+    for solver in (1, 2, 3):
+        assert lib.irs_quasistatic_box_descent_wsx(BICYCLE, bike, 1, 10, *q, None, None, one, one, None, None, solver,
+                                                   10.0, 1.6, 100, 1e-8, one, one, None, one, None, None, 0,
+                                                   None) == -3
+        assert b"position controlled" in lib.irs_last_error()
+    assert lib.irs_quasistatic_box_descent_ws(HAND, ph, 12, 80, *q, None, None, one, one, None, None,
+                                              2, 10.0, 1.6, 100, 1e-8, one, one, None, one, None, None) == -3
+    assert lib.irs_quasistatic_box_descent_wsx(HAND, ph, 12, 120, *q, None, None, one, one, None, None, 3,
+                                               10.0, 1.6, 100, 1e-8, one, one, None, one, None, ws, 256, None) == -3
+    assert b"workspace" in lib.irs_last_error()
+    assert lib.irs_quasistatic_box_descent_ws(HAND, ph, 12, 384, *q, None, None, one, one, one, one,
+                                              1, 10.0, 1.6, 100, 1e-8, one, one, None, one, None, None) == -3
+
+
+def lib_nparams(lib, model):
+    n = ctypes.c_int()
+    assert lib.irs_model_info(model, None, None, ctypes.byref(n)) == 0
+    return n.value
+
+
+def walk_horizon_limit(lib, model, kind):
+    """The longest horizon the size queries let `kind` run, by walking T upwards (0: the model has no such form)."""
+    if kind == 3:
+        return INT_MAX if lib.irs_quasistatic_box_lds_bytes(model, 1, 3) > 0 else 0
+    if kind == 2:
+        def fits(T):
+            return 0 < lib.irs_quasistatic_box_lds_bytes(model, T, 2) <= LDS_LIMIT
+    else:
+        def fits(T):
+            return 0 < lib.irs_tvlqr_box_hbm_lds_bytes(model, T, kind) <= LDS_LIMIT
+    T = 0
+    while fits(T + 1):
+        T += 1
+    return T
+
+
+def plan_horizons(lib, model):
+    """T = 0..64, a stride to ~1100 and each cap +-1: the caps with records in HBM, and where the records leave LDS."""
+    caps = [walk_horizon_limit(lib, model, k) for k in range(3)]
+    for fits in (lambda T: lib.irs_tvlqr_box_lds_bytes(model, T) <= LDS_LIMIT,
+                 lambda T: 0 < lib.irs_quasistatic_box_lds_bytes(model, T, 1) <= LDS_LIMIT,
+                 lambda T: 0 < lib.irs_quasistatic_box_lds_bytes(model, T, 3) <= LDS_LIMIT):
+        T = 0
+        while T < 2000 and fits(T + 1):
+            T += 1
+        caps.append(T)
+    Ts = set(range(65)) | set(range(80, 1101, 40)) | {c + d for c in caps if c > 0 for d in (-1, 0, 1)}
+    return sorted(Ts)
+
+
+def box_plan_table(lib, horizons=None):
+    """Every placement answer of the bounded descents for the 11 models: the size queries of csrc/boxqp.hip, the fused
+    iterate's scratch (modes 0-3, N = 1000) and DeviceModel's support answers.  horizons: {model: [T, ...]}."""
+    from irs_mpc_amd.device import DeviceModel
+    table = {}
+    for model in range(N_MODELS):
+        Ts = horizons[str(model)] if horizons else plan_horizons(lib, model)
+        dm = DeviceModel(model, [0.1] * lib_nparams(lib, model))
+        row = {"T": Ts,
+               "tvlqr_box_lds_bytes": [lib.irs_tvlqr_box_lds_bytes(model, T) for T in Ts],
+               "box_horizon_limit": [dm.box_horizon_limit(du=False), dm.box_horizon_limit(du=True)]}
+        for du in (0, 1):
+            row["tvlqr_box_workspace_bytes/%d" % du] = [lib.irs_tvlqr_box_workspace_bytes(model, T, du) for T in Ts]
+            row["tvlqr_box_hbm_lds_bytes/%d" % du] = [lib.irs_tvlqr_box_hbm_lds_bytes(model, T, du) for T in Ts]
+            row["box_descent_supported/%d" % du] = [int(dm.box_descent_supported(T, du=bool(du))) for T in Ts]
+        for solver in range(4):
+            row["quasistatic_box_lds_bytes/%d" % solver] = [lib.irs_quasistatic_box_lds_bytes(model, T, solver)
+                                                            for T in Ts]
+            row["quasistatic_descent_workspace_bytes/%d" % solver] = [
+                lib.irs_quasistatic_descent_workspace_bytes(model, T, solver) for T in Ts]
+            row["iterate_scratch_bytes/%d" % solver] = [lib.irs_iterate_scratch_bytes(model, solver, T, 1000)
+                                                        for T in Ts]
+        for solver in (1, 2, 3):
+            row["quasistatic_descent_supported/%d" % solver] = [int(dm.quasistatic_descent_supported(T, solver))
+                                                                for T in Ts]
+        table[str(model)] = row
+    return table
+
+
+def test_box_plan_table_matches_the_golden(lib):
+    """The planner answers every size and support question as the code before it did (tests/golden/
+    box_plan_table.json was written by this module's __main__ against a library built before the planner)."""
+    with open(GOLDEN) as f:
+        golden = json.load(f)
+    got = box_plan_table(lib, {m: golden[m]["T"] for m in golden})
+    assert sorted(got) == sorted(golden)
+    for m in golden:
+        for key in golden[m]:
+            assert got[m][key] == golden[m][key], (m, key)
+
+
+def test_box_horizon_limit_equals_the_walk(lib):
+    from irs_mpc_amd.device import DeviceModel
+    assert DeviceModel.BOX_LDS_LIMIT == LDS_LIMIT
+    for model in range(N_MODELS):
+        for kind in range(4):
+            assert lib.irs_box_horizon_limit(model, kind) == walk_horizon_limit(lib, model, kind), (model, kind)
+    assert lib.irs_box_horizon_limit(QUAD, 0) == 357 and lib.irs_box_horizon_limit(HAND, 1) == 383
+    assert lib.irs_box_horizon_limit(HAND, 4) == 0 and lib.irs_box_horizon_limit(N_MODELS, 0) == 0
+
+
+if __name__ == "__main__":
+    # writes the golden table: run from a tree whose package and library predate the planner
+    sys.path.insert(0, os.getcwd())
+    from irs_mpc_amd import _lib
+    with open(sys.argv[1] if len(sys.argv) > 1 else GOLDEN, "w") as f:
+        json.dump(box_plan_table(_lib.load()), f, separators=(",", ":"))
+        f.write("\n")
