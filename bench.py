@@ -18,12 +18,16 @@ torch.distributed.run.  Prints ONE JSON line of headline figures on rank 0 (stdo
 result_line); --full-report FILE writes the full report as well.  --dump-outputs DIR writes what the last timed
 step computed (A_t, B_t, c_t) as .npy files.
 
+A plain run does only what the headline needs: set-up, the warm-up, the timed steps, the dump, the line.
+Everything else below -- iLQR iterations / s, the roofline, the public-API rate, the CPU baseline and the
+sub-reports -- runs with --full (--no-cpu-baseline / --no-secondary then leave parts of it out).
+
 iLQR iterations / s of the contact workloads are measured on the optimisation the reference's script
 performs ("ilqr_loop": 20 iterations per episode, every one re-linearised around the previous result with
 fresh device-drawn samples, bounds re-centred, first tail warm-started from the previous descent);
 "ilqr_first_iter_per_s" is the first iteration alone, repeated from a cold start.
 
-Sub-reports of the default single-GPU run (in the full report; the line carries their rates):
+Sub-reports of a --full single-GPU run (in the full report; the line carries their rates):
   "sweep_N"             the metric's workload at N = 1e3 and 1e5 (north_star's N points)
   "first_order"         the reference's planar-hand gradient mode (planar_hand_setup.py:28)
   "pgs_contact_solver"  the opt-in approximate step-QP solver (50 projected sweeps + polish)
@@ -410,10 +414,11 @@ SUB_REPORTS = ("first_order", "pgs_contact_solver", "general_kernel", "pendulum"
 
 
 def result_line(out):
-    """The JSON line bench.py prints, from the full report `out`: its headline keys, the roofline's bound and
-    share, the iLQR loop's outcome, and every sub-report by its headline rate alone."""
+    """The JSON line bench.py prints, from the full report `out`: its headline keys and, from a --full run, the
+    roofline's bound and share, the iLQR loop's outcome, and every sub-report by its headline rate alone."""
     line = {k: out[k] for k in LINE_KEYS if k in out}
-    line["roofline"] = {k: out["roofline"][k] for k in ("bound", "achieved", "peak", "unit", "frac")}
+    if "roofline" in out:
+        line["roofline"] = {k: out["roofline"][k] for k in ("bound", "achieved", "peak", "unit", "frac")}
     if out.get("ilqr_loop"):
         line["ilqr_loop"] = {k: out["ilqr_loop"][k] for k in ("descends", "qp_converged_last_iteration",
                                                               "cost_first_iteration", "cost_last")}
@@ -436,12 +441,16 @@ def main():
     ap.add_argument("--workload", default="planar_hand", choices=["planar_hand", "pendulum", "quadrotor", "box_pivoting"])
     ap.add_argument("--T", type=int, default=None)
     ap.add_argument("--N", type=int, default=10000, help="samples per timestep per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip every sub-report (timed workload only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure iLQR iterations / s, the roofline, the public-API rate, the CPU baseline and "
+                         "the sub-reports (a plain run times the smoothing step alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full: skip every sub-report (the timed workload's extra figures only)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL)")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="run all ranks on GPU 0 with gloo (exercises the N>1 code path on a 1-GPU box)")
-    ap.add_argument("--sweep", action="store_true", help="also time N=1e6 for the pendulum (extra key)")
+    ap.add_argument("--sweep", action="store_true", help="--full: also time N=1e6 for the pendulum (extra key)")
     ap.add_argument("--mode", default=None, choices=["first_order"],
                     help="planar_hand: gradient_mode first_order instead of zero_order_B as the timed workload")
     ap.add_argument("--contact-solver", default="exact", choices=["pgs", "exact"],
@@ -483,7 +492,7 @@ def main():
     # the CPU baseline runs FIRST, before this process initialises the GPU: its pooled leg starts worker
     # processes (fresh interpreters), which a process that already holds the GPU must not do on this pool
     cpu_base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.force_unfused \
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.force_unfused \
             and args.workload in ("planar_hand", "pendulum"):
         cpu_base = cpu_baseline(Workload(args.workload, args.T, args.mode, host_only=True,
                                          contact_solver=args.contact_solver), args.N)
@@ -606,9 +615,9 @@ def main():
         return dict(du_lo=torch.full((w.T, m), -wd, dtype=dev.F64, device=x_trj.device),
                     du_hi=torch.full((w.T, m), wd, dtype=dev.F64, device=x_trj.device))
 
-    def run(w, N, steps, warmup, loop_iters=20, dump=None):
-        """Times the smoothing step and the full iLQR iteration of workload `w`.  `dump` (a dict): receives the
-        host copies of what the last timed smoothing step returned."""
+    def run(w, N, steps, warmup, loop_iters=20, dump=None, full=True):
+        """Times the smoothing step of workload `w` and, with `full`, its iLQR iteration.  `dump` (a dict):
+        receives the host copies of what the last timed smoothing step returned."""
         dm = w.system.dm()
         n, m, T, MODE = dm.n, dm.m, w.T, w.mode
         Q, Qd, R = dev.to_dev(w.Q), dev.to_dev(w.Qd), dev.to_dev(w.R)
@@ -702,6 +711,13 @@ def main():
                     step_info["graph_error"] = "capture failed on another rank; eager step timed"
 
         smooth_step()
+        el, ev_ms = timed(smooth_step, steps, warmup)
+        if dump is not None:        # before the iLQR timing below launches the step again
+            dump.update({k: tv[k].cpu().numpy() for k in ("At", "Bt", "ct")})
+        info = int(tv["info"].abs().sum().item())
+        assert info == 0, "smoothing solve reported a non-SPD Gram matrix or a non-finite statistic"
+        if not full:
+            return el, None, None, (n, m), None
         if contact:
             # IrsLqrQuasistatic.local_descent (irs_lqr_quasistatic.py:286-345) as the reference's script sets
             # it up: du cost, ONE control box (trust region / rate limit), T re-solved tail QPs, contact
@@ -724,9 +740,6 @@ def main():
             smooth_step()
             descent_run()
 
-        el, ev_ms = timed(smooth_step, steps, warmup)
-        if dump is not None:        # before the iLQR timing below launches the step again
-            dump.update({k: tv[k].cpu().numpy() for k in ("At", "Bt", "ct")})
         it_steps = max(1, steps // (20 if contact else 4))
         el_it, _ = timed(ilqr_step, it_steps, max(1, it_steps // 10))
         el_it *= steps / it_steps
@@ -811,8 +824,6 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             k_ms = e0.elapsed_time(e1) / steps
-        info = int(tv["info"].abs().sum().item())
-        assert info == 0, "smoothing solve reported a non-SPD Gram matrix or a non-finite statistic"
         return el, el_it, k_ms, (n, m), loop
 
     def public_api(w_, N_, k_iters, episodes=3):
@@ -959,7 +970,7 @@ def main():
     N, T = args.N, w.T
     contact = w.bounds is not None
     dumped = {} if args.dump_outputs else None
-    el, el_it, k_mean, nm, loop = run(w, N, args.steps, args.warmup, dump=dumped)
+    el, el_it, k_mean, nm, loop = run(w, N, args.steps, args.warmup, dump=dumped, full=args.full)
     if dumped is not None and sum(a.nbytes for a in dumped.values()) > 64 << 20:
         raise SystemExit("--dump-outputs: the outputs exceed 64 MB at T=%d" % T)      # (the same on every rank)
     if dumped is not None and rank == 0:
@@ -990,19 +1001,22 @@ def main():
                    "contact_solver": w.contact_solver if contact else None,
                    "samples": "supplied, resident in HBM (f32)",
                    "parallelism": "samples sharded over %d GPU(s), 1 all-reduce of (T,P) f64 per step" % world},
-        "ilqr_iters_per_s": loop["iters_per_s"] if loop else args.steps / el_it,
-        "ms_per_ilqr_iter": loop["ms_per_iter"] if loop else 1e3 * el_it / args.steps,
-        "ilqr_loop": loop,
-        "ilqr_first_iter_per_s": args.steps / el_it,
-        "ilqr_iters_note": ("ilqr_iters_per_s = the real 20-iteration loop (ilqr_loop); ilqr_first_iter_per_s = the "
-                            "first iteration alone, repeated from a cold start (no warm start, supplied samples)"
-                            if loop else "one iteration repeated: its cost does not depend on the trajectory"),
-        "ilqr_iter": ("smoothing launch + IrsLqrQuasistatic.local_descent (du cost, one control box, T re-solved tail "
-                      "QPs by the active-set solver, contact dynamics in the loop)"
-                      if contact else "smoothing launch + Riccati + closed-loop rollout + cost (bounds inactive)"),
-        "roofline": roofline(w, N, k_mean, nm),
     }
-    if world == 1 and not unfused:
+    if args.full:
+        out.update({
+            "ilqr_iters_per_s": loop["iters_per_s"] if loop else args.steps / el_it,
+            "ms_per_ilqr_iter": loop["ms_per_iter"] if loop else 1e3 * el_it / args.steps,
+            "ilqr_loop": loop,
+            "ilqr_first_iter_per_s": args.steps / el_it,
+            "ilqr_iters_note": ("ilqr_iters_per_s = the real 20-iteration loop (ilqr_loop); ilqr_first_iter_per_s = "
+                                "the first iteration alone, repeated from a cold start (no warm start, supplied samples)"
+                                if loop else "one iteration repeated: its cost does not depend on the trajectory"),
+            "ilqr_iter": ("smoothing launch + IrsLqrQuasistatic.local_descent (du cost, one control box, T re-solved "
+                          "tail QPs by the active-set solver, contact dynamics in the loop)"
+                          if contact else "smoothing launch + Riccati + closed-loop rollout + cost (bounds inactive)"),
+            "roofline": roofline(w, N, k_mean, nm),
+        })
+    if args.full and world == 1 and not unfused:
         try:
             api = public_api(w, N, 19 if contact else (3 if w.name == "quadrotor" else 99))
             out["ilqr_iters_per_s_public_api"], out["public_api"] = api["iters_per_s"], api
@@ -1017,7 +1031,7 @@ def main():
         out["config"]["collective"] = step_info.get("collective", "torch.distributed all_reduce (%s)" % args.backend)
         if "collective_fallback" in step_info:
             out["config"]["collective_fallback"] = step_info["collective_fallback"]
-    secondary = world == 1 and not unfused and not args.no_secondary
+    secondary = args.full and world == 1 and not unfused and not args.no_secondary
     if secondary:
         # north_star's N points for the timed workload
         sweep = {}

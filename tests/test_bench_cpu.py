@@ -91,3 +91,17 @@ def test_result_line_is_compact_and_keeps_the_headline():
     assert line["sweep_N"] == {n: r["value"] for n, r in full["sweep_N"].items()}
     assert all(line[k] == full[k]["value"] for k in bench.SUB_REPORTS)
     assert line["cpu_baseline"]["value"] == full["cpu_baseline"]["value"]
+
+
+def test_result_line_of_a_plain_run():
+    """A plain run (no --full) reports the headline keys and the config alone: no roofline, iLQR figures,
+    sub-reports or CPU baseline; result_line carries what it has."""
+    import json
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r03i_bench.json")))
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+                                  "timed_region_s", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+                                  "parity", "config")}
+    line = bench.result_line(plain)
+    assert line == {k: plain[k] for k in bench.LINE_KEYS if k in plain}
+    assert line["value"] == full["value"] and line["ms_per_step"] == full["ms_per_step"]

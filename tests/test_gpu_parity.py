@@ -1197,7 +1197,7 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29611", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "20", "--warmup", "3", "--rehearse-one-gpu", "--T", "12", "--N", "1500"]
+           "--gpus", "2", "--steps", "20", "--warmup", "3", "--rehearse-one-gpu", "--T", "12", "--N", "1500", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=560, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1261,7 +1261,7 @@ def test_bench_two_ranks_peer_exchange_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29619", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "20", "--warmup", "3", "--rehearse-one-gpu", "--collective", "peer",
-           "--T", "12", "--N", "1500"]
+           "--T", "12", "--N", "1500", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=560, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
