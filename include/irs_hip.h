@@ -18,6 +18,8 @@
  *    costs are float64 (the reference computes in float64); the sample tensors
  *    dx/du, which carry all the bytes, are float32 and the per-sample dynamics
  *    evaluation runs in float32 (`dtype` of the path: f32).
+ *  - The cost weights Q, Qd (n x n) and R (m x m) are dense and need not be symmetric:
+ *    every entry point uses the symmetric part (W + W')/2, as Drake's quadratic costs do.
  *  - Return value: IRS_OK (0) or a negative irs_status; irs_last_error() returns
  *    a thread-local message.  Numerical failures inside kernels (non-SPD Gram or
  *    Hessian) are reported through the DEV `info` arrays, LAPACK style.

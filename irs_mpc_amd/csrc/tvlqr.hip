@@ -269,14 +269,19 @@ template <int N, int M>
 __device__ __forceinline__ void riccati_backward_reg(const RiccatiArgs& a, int lane) {
     const int T = a.T;
     double P[N][N], p[N], Q[N][N], R[M][M];
+    // only the symmetric parts of Q, Qd, R enter a quadratic form (the recursion itself is not invariant:
+    // an unsymmetric P would reach the gains through (PB)'A)
 #pragma unroll
     for (int i = 0; i < N; ++i)
 #pragma unroll
-        for (int j = 0; j < N; ++j) { P[i][j] = a.Qd[i * N + j]; Q[i][j] = a.Q[i * N + j]; }
+        for (int j = 0; j < N; ++j) {
+            P[i][j] = 0.5 * (a.Qd[i * N + j] + a.Qd[j * N + i]);
+            Q[i][j] = 0.5 * (a.Q[i * N + j] + a.Q[j * N + i]);
+        }
 #pragma unroll
     for (int i = 0; i < M; ++i)
 #pragma unroll
-        for (int j = 0; j < M; ++j) R[i][j] = a.alpha * a.R[i * M + j];
+        for (int j = 0; j < M; ++j) R[i][j] = 0.5 * a.alpha * (a.R[i * M + j] + a.R[j * M + i]);
 #pragma unroll
     for (int i = 0; i < N; ++i) {
         double s = 0.0;
@@ -715,8 +720,16 @@ __global__ __launch_bounds__(64) void riccati_kernel(RiccatiArgs a) {
     __shared__ int bad;
     const int ldh = m + 1;
 
-    for (int q = lane; q < n * n; q += 64) { P[q] = a.Qd[q]; Qs[q] = a.Q[q]; }
-    for (int q = lane; q < m * m; q += 64) Rs[q] = a.R[q];
+    // the symmetric parts, as in the compile-time paths
+    for (int q = lane; q < n * n; q += 64) {
+        const int i = q / n, j = q % n;
+        P[q] = 0.5 * (a.Qd[q] + a.Qd[j * n + i]);
+        Qs[q] = 0.5 * (a.Q[q] + a.Q[j * n + i]);
+    }
+    for (int q = lane; q < m * m; q += 64) {
+        const int i = q / m, j = q % m;
+        Rs[q] = 0.5 * (a.R[q] + a.R[j * m + i]);
+    }
     if (lane == 0) bad = 0;
     wave_sync();
     if (lane < n) {
