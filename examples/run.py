@@ -5,6 +5,7 @@
     python examples/run.py quadrotor first_order --device-rng
     python examples/run.py bicycle exact --csv bicycle_easy_exact.csv
     python examples/run.py pendulum cem
+    python examples/run.py pendulum cem --device-rng
 
 method = zero_order | first_order | exact | cem.  The sampling closure is the scripts'
 (host NumPy RNG, `--seed`) unless --device-rng draws on the GPU.  Prints the cost history
@@ -44,6 +45,8 @@ def main():
         for k in ("Q", "Qd", "R", "x0", "xd_trj", "u_trj_initial"):
             setattr(cp, k, getattr(params, k))
         cp.initial_std, cp.batch_size, cp.n_elite = cem["initial_std"], cem["batch_size"], cem["n_elite"]
+        if a.device_rng:        # candidates drawn inside the rollout kernel, iterate in one library call
+            cp.device_seed = a.seed
         solver = amd.CrossEntropyMethod(sysd, cp)
     elif a.method == "exact":
         solver = amd.IrsLqrExact(sysd, params)

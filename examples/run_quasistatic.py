@@ -6,6 +6,7 @@
     python examples/run_quasistatic.py planar_hand cem           # .../run_planar_hand_cem.py
     python examples/run_quasistatic.py box_pivoting irs_lqr      # examples/box_pivoting/run_box_pivoting.py
     python examples/run_quasistatic.py box_pivoting cem          # .../run_box_pivoting_cem.py
+    python examples/run_quasistatic.py box_pivoting cem --device-rng
     python examples/run_quasistatic.py box_pushing irs_lqr       # examples/box_pushing/run_box_pushing.py
     python examples/run_quasistatic.py planar_hand_spin irs_lqr  # examples/planar_hand/run_planar_hand_spin.py
 
@@ -152,6 +153,8 @@ def main():
         params.n_elite, params.batch_size = max(2, a.N // 10), a.N
         params.initial_std = 0.1 * np.ones(q_dynamics.dim_u)
         params.publish_every_iteration = False
+        if a.device_rng:        # candidates drawn inside the rollout kernel, iterate in one library call
+            params.device_seed = a.seed
         solver = amd.CrossEntropyMethodQuasistatic(q_dynamics, params)
     solver.verbose = not a.quiet
     t0 = time.time()

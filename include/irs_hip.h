@@ -455,6 +455,70 @@ int irs_cem_rollout_costs_quasistatic(int model, const double *params, int n_par
 int irs_cem_refit(int T, int m, int B, int n_elite, const double *u_cand, const double *costs,
                   int *elite_idx, double *u_new, double *std_new, void *stream);
 
+/* ---- Device-resident CEM: the candidates are drawn inside the kernels ------------
+ * The draw of cem.py:159-161 / cem_quasistatic.py:170-173 (np.random.normal(u_trj, std_trj, (B,T,m)))
+ * replaced by a counter-based stream, so the (B,T,m) tensor is never stored:
+ *   u_cand[b,t,j] = fma(std[t,j], (double) z, u_mean[t,j]),
+ *   z = component j % 4 of the four normals of Philox counter (sample_offset + b, t, block j / 4, iter), key seed
+ * -- the `du` stream of the smoothing generator (irs_rng_samples) with n = 0 and unit std, axes (T,B,m) ->
+ * (B,T,m).  It shares that generator's counters on purpose: no caller runs CEM and a smoothing pass with
+ * the same (seed, iter).  One refinement: where a Box-Muller pair has u1 within 2^-6 of 1 its radius is
+ * formed from 1 - u1, which f32 holds exactly there, so that every candidate agrees with the f64
+ * statement of the stream to std (2e-5 |z| + 2e-6); such draws differ from irs_rng_samples' by up to
+ * 1e-5, all others are bit-equal.  u_mean, std (T,m) DEV f64.                                          */
+
+/* Debug/verification: writes the candidates u_cand (B,T,m) DEV f64 the calls below draw.               */
+int irs_cem_candidates(int T, int m, int B, const double *u_mean, const double *std, uint64_t seed,
+                       uint32_t iter, uint64_t sample_offset, double *u_cand, void *stream);
+
+/* irs_cem_rollout_costs (cem.py:163-168) on drawn candidates: ceil(m/4) generator calls per (b,t) in
+ * the lane, no per-candidate memory read.                                                              */
+int irs_cem_rollout_costs_drawn(int model, const double *params, int n_params, int T, int B,
+                                const double *u_mean, const double *std, uint64_t seed, uint32_t iter,
+                                uint64_t sample_offset, const double *x0, const double *Q,
+                                const double *R, const double *xd_trj, double *costs, void *stream);
+
+/* irs_cem_rollout_costs_quasistatic (cem_quasistatic.py:175-186) on drawn candidates.                  */
+int irs_cem_rollout_costs_quasistatic_drawn(int model, const double *params, int n_params, int T, int B,
+                                            const double *u_mean, const double *std, uint64_t seed,
+                                            uint32_t iter, uint64_t sample_offset, const double *x0,
+                                            const double *Q, const double *Qd, const double *R,
+                                            const double *xd_trj, double *costs, void *stream);
+
+/* irs_cem_refit (cem.py:173-180, cem_quasistatic.py:188-197) with every elite regenerated from its index
+ * instead of loaded: same selection, same summation order.  Reads the OLD u_mean / std while it writes
+ * u_new / std_new: IRS_ERR_INVALID_ARG if they alias.                                                  */
+int irs_cem_refit_drawn(int T, int m, int B, int n_elite, const double *u_mean, const double *std,
+                        uint64_t seed, uint32_t iter, uint64_t sample_offset, const double *costs,
+                        int *elite_idx, double *u_new, double *std_new, void *stream);
+
+/* CrossEntropyMethod.iterate (cem.py:186-216) / CrossEntropyMethodQuasistatic.iterate
+ * (cem_quasistatic.py:200-258) as ONE call: n_descents x (price B drawn candidates, select, refit, roll
+ * out the new mean (cem.py:182) and price it with the cost the candidates got), enqueued back to back on
+ * `stream`; the caller reads the histories back once.  Descent i draws around u_hist[i-1] / std_hist[i-1]
+ * (descent 0: u_trj0 / std0) with generator iteration iter0 + i and sample_offset 0 -- the chain of the
+ * reference's loop, where every descent but the last is adopted and std_trj is always carried.
+ * quasistatic 0: the cost of cem.py:124-140 (terminal Q; Qd unused, may be NULL); 1: eval_cost of
+ * cem_quasistatic.py:122-160 (terminal Qd, input cost on u_t - u_{t-1}), position-controlled models only
+ * (IRS_ERR_UNSUPPORTED otherwise).  scratch: DEV, >= irs_cem_iterate_scratch_bytes(T, m, B, n_elite);
+ * IRS_ERR_INVALID_ARG if it is smaller.                                                                 */
+typedef struct irs_cem_iterate_call {
+    int model, n_params;
+    double params[12];
+    int T, B, n_elite, n_descents, quasistatic;
+    uint64_t seed;
+    uint32_t iter0;
+    const double *Q, *Qd, *R, *xd_trj, *x0;   /* DEV (n,n), (n,n), (m,m), (T+1,n), (n) */
+    const double *u_trj0, *std0;               /* DEV (T,m): mean and std of descent 0 */
+    double *u_hist, *std_hist;                 /* DEV out (n_descents, T, m) */
+    double *x_hist, *cost_hist;                /* DEV out (n_descents, T+1, n), (n_descents) */
+    void *scratch;
+    size_t scratch_bytes;
+} irs_cem_iterate_call;
+
+size_t irs_cem_iterate_scratch_bytes(int T, int m, int B, int n_elite);
+int irs_cem_iterate(const irs_cem_iterate_call *call, void *stream);
+
 /* ---- Pre-marshalled calls ------------------------------------------------------
  * The same operations with their arguments packed in a caller-owned struct, so that a
  * host loop (IrsLqr.iterate, irs_lqr/irs_lqr.py:188-218) pays one pointer-sized FFI

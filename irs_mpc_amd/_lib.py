@@ -125,6 +125,29 @@ SIGNATURES["irs_cem_rollout_costs"] = (c_int, [c_int, POINTER(c_double), c_int, 
 SIGNATURES["irs_cem_rollout_costs_quasistatic"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, _dp, _dp, _dp,
                                                            _dp, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_cem_refit"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, c_void_p])
+
+
+class CemIterateCall(ctypes.Structure):
+    """irs_cem_iterate_call (include/irs_hip.h)."""
+    _fields_ = [("model", c_int), ("n_params", c_int), ("params", c_double * 12),
+                ("T", c_int), ("B", c_int), ("n_elite", c_int), ("n_descents", c_int), ("quasistatic", c_int),
+                ("seed", c_uint64), ("iter0", c_uint32),
+                ("Q", c_void_p), ("Qd", c_void_p), ("R", c_void_p), ("xd_trj", c_void_p), ("x0", c_void_p),
+                ("u_trj0", c_void_p), ("std0", c_void_p),
+                ("u_hist", c_void_p), ("std_hist", c_void_p), ("x_hist", c_void_p), ("cost_hist", c_void_p),
+                ("scratch", c_void_p), ("scratch_bytes", c_size_t)]
+
+
+SIGNATURES["irs_cem_candidates"] = (c_int, [c_int, c_int, c_int, _dp, _dp, c_uint64, c_uint32, c_uint64, _dp, c_void_p])
+SIGNATURES["irs_cem_rollout_costs_drawn"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, _dp, _dp, c_uint64,
+                                                     c_uint32, c_uint64, _dp, _dp, _dp, _dp, _dp, c_void_p])
+SIGNATURES["irs_cem_rollout_costs_quasistatic_drawn"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, _dp, _dp,
+                                                                 c_uint64, c_uint32, c_uint64, _dp, _dp, _dp, _dp, _dp,
+                                                                 _dp, c_void_p])
+SIGNATURES["irs_cem_refit_drawn"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, c_uint64, c_uint32, c_uint64, _dp, _dp,
+                                             _dp, _dp, c_void_p])
+SIGNATURES["irs_cem_iterate_scratch_bytes"] = (c_size_t, [c_int, c_int, c_int, c_int])
+SIGNATURES["irs_cem_iterate"] = (c_int, [POINTER(CemIterateCall), c_void_p])
 SIGNATURES["irs_tvlqr_box_descent"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
                                                c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_double, c_double, c_int,
                                                c_double, _dp, _dp, _dp, c_void_p])

@@ -7,6 +7,11 @@ iterate and the attributes x_trj, u_trj, cost, std_trj, iter, x_trj_lst, u_trj_l
 identical candidates); the B rollouts + costs, the elite selection and the refit run on the GPU
 (csrc/cem.hip).  Construction-time validation is IrsLqr's (same checks, same messages:
 cem.py:77-106 duplicates irs_lqr.py:73-103).
+
+`params.device_seed` (optional, not a reference field; None = the host draw above): an int makes the
+method device resident -- the candidates are a counter-based stream keyed by (device_seed, self.iter)
+and drawn inside the rollout kernel, the refit regenerates the elites from their indices, no (B,T,m)
+tensor exists on either side; `iterate` is then ONE library call (irs_cem_iterate) and one read-back.
 """
 import time
 
@@ -23,6 +28,7 @@ class CemParameters:
         for name in ("Q", "Qd", "R", "x0", "xd_trj", "u_trj_initial", "n_elite", "batch_size", "elite_frac",
                      "initial_std"):
             setattr(self, name, None)
+        self.device_seed = None     # int: draw the candidates on the device (not a reference field)
 
 
 class CrossEntropyMethod:
@@ -35,6 +41,7 @@ class CrossEntropyMethod:
         self.check_valid_params(params, system)
         for name in ("Q", "Qd", "R", "x0", "xd_trj", "n_elite", "batch_size", "elite_frac", "initial_std"):
             setattr(self, name, getattr(params, name))
+        self.device_seed = getattr(params, "device_seed", None)
         self.u_trj = params.u_trj_initial
         self.T, self.dim_x, self.dim_u = self.u_trj.shape[0], system.dim_x, system.dim_u
 
@@ -62,6 +69,8 @@ class CrossEntropyMethod:
 
     def local_descent(self, x_trj, u_trj):
         """cem.py:151-184: sample, price, keep the elites, refit mean and std."""
+        if self.device_seed is not None:
+            return self._local_descent_drawn(u_trj)
         candidates = dev.to_dev(np.random.normal(u_trj, self.std_trj, (self.batch_size, self.T, self.dim_u)))
         self.cost_array = self._dm.cem_rollout_costs(candidates, self._x0, self._Q, self._R, self._xd)
         self.elite_idx, u_mean, u_std = self._dm.cem_refit(candidates, self.cost_array, self.n_elite)
@@ -69,8 +78,42 @@ class CrossEntropyMethod:
         self.std_trj = u_std.cpu().numpy()
         return x_mean.cpu().numpy(), u_mean.cpu().numpy()
 
+    def _local_descent_drawn(self, u_trj):
+        """local_descent on the candidate stream of (device_seed, self.iter): no candidate tensor."""
+        mean, std = dev.to_dev(np.asarray(u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float))
+        self.cost_array = self._dm.cem_rollout_costs_drawn(mean, std, self.batch_size, self.device_seed, self.iter,
+                                                           self._x0, self._Q, self._R, self._xd)
+        self.elite_idx, u_mean, u_std = self._dm.cem_refit_drawn(mean, std, self.device_seed, self.iter,
+                                                                 self.cost_array, self.n_elite)
+        x_mean, _ = self._dm.rollout_cost(self._x0, u_mean, self._Q, self._R, self._xd)
+        self.std_trj = u_std.cpu().numpy()
+        return x_mean.cpu().numpy(), u_mean.cpu().numpy()
+
+    def _iterate_drawn(self, max_iterations):
+        """The loop below through ONE irs_cem_iterate call: every descent enqueued back to back, one read-back."""
+        k = max(1, max_iterations - self.iter + 2)          # descents the host loop would run from self.iter
+        o = self._dm.cem_iterate(dev.to_dev(np.asarray(self.u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float)),
+                                 self._x0, self._Q, None, self._R, self._xd, self.batch_size, self.n_elite, k,
+                                 self.device_seed, self.iter)
+        x_hist, u_hist, std_hist, cost_hist = (o[key].cpu().numpy() for key in ("x_hist", "u_hist", "std_hist",
+                                                                                "cost_hist"))
+        for i in range(k):
+            x_new, u_new, cost_new = x_hist[i], u_hist[i], float(cost_hist[i])
+            if self.verbose:
+                print("Iteration: {:02d}  ||  Current Cost: {:05f}  ||  Elapsed time: {:05f} ".format(
+                    self.iter, cost_new, time.time() - self.start_time))
+            for log, item in ((self.x_trj_lst, x_new), (self.u_trj_lst, u_new), (self.cost_lst, cost_new)):
+                log.append(item)
+            self.std_trj = std_hist[i]
+            if i == k - 1:
+                return self.x_trj, self.u_trj, self.cost
+            self.cost, self.x_trj, self.u_trj = cost_new, x_new, u_new
+            self.iter += 1
+
     def iterate(self, max_iterations):
         """cem.py:186-216: max_iterations + 1 descents, the last one logged but not adopted."""
+        if self.device_seed is not None:
+            return self._iterate_drawn(max_iterations)
         while True:
             x_new, u_new = self.local_descent(self.x_trj, self.u_trj)
             cost_new = self.evaluate_cost(x_new, u_new)

@@ -9,7 +9,14 @@ local_descent / iterate and the reference's attribute names (quasistatic_base.py
 candidates); the B contact rollouts, their quasistatic costs, the elite selection and the refit run
 on the GPU (csrc/cem.hip).  The reference's parameter class declares `xd_trj` but its solver reads
 `params.x_trj_d` (:62, a latent AttributeError there): either attribute is accepted here.
+
+`params.device_seed` (optional, not a reference field; None = the host draw above): an int makes the
+method device resident, as in cem.py of this package -- candidates drawn inside the rollout kernel from
+the stream keyed by (device_seed, self.current_iter), elites regenerated from their indices, and
+`iterate` ONE library call (irs_cem_iterate) with one read-back.
 """
+import time
+
 import numpy as np
 
 from . import device as dev
@@ -24,6 +31,7 @@ class CemQuasistaticParameters:
                      "initial_std", "T"):
             setattr(self, name, None)       # initial_std: (dim_u,) array of initial stds
         self.publish_every_iteration = True
+        self.device_seed = None     # int: draw the candidates on the device (not a reference field)
 
 
 class CrossEntropyMethodQuasistatic(QuasistaticOptimizerBase):
@@ -32,9 +40,12 @@ class CrossEntropyMethodQuasistatic(QuasistaticOptimizerBase):
         self._setup(q_dynamics, params, params.xd_trj if goal is None else goal)
         self.n_elite, self.batch_size, self.initial_std = params.n_elite, params.batch_size, params.initial_std
         self.std_trj = np.tile(self.initial_std, (self.T, 1))
+        self.device_seed = getattr(params, "device_seed", None)
 
     def local_descent(self, x_trj, u_trj):
         """cem_quasistatic.py:168-211: sample, price, keep the elites, refit mean and std."""
+        if self.device_seed is not None:
+            return self._local_descent_drawn(u_trj)
         candidates = dev.to_dev(np.random.normal(u_trj, self.std_trj, (self.batch_size, self.T, self.dim_u)))
         self.cost_array = self._dm.cem_rollout_costs_quasistatic(candidates, self._x0, self._Q, self._Qd, self._R,
                                                                  self._xd)
@@ -42,6 +53,43 @@ class CrossEntropyMethodQuasistatic(QuasistaticOptimizerBase):
         x_mean, _ = self._dm.rollout_cost(self._x0, u_mean, self._Q, self._R, self._xd)
         self.std_trj = u_std.cpu().numpy()
         return x_mean.cpu().numpy(), u_mean.cpu().numpy()
+
+    def _local_descent_drawn(self, u_trj):
+        """local_descent on the candidate stream of (device_seed, self.current_iter): no candidate tensor."""
+        mean, std = dev.to_dev(np.asarray(u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float))
+        it = self.current_iter
+        self.cost_array = self._dm.cem_rollout_costs_quasistatic_drawn(mean, std, self.batch_size, self.device_seed, it,
+                                                                       self._x0, self._Q, self._Qd, self._R, self._xd)
+        self.elite_idx, u_mean, u_std = self._dm.cem_refit_drawn(mean, std, self.device_seed, it, self.cost_array,
+                                                                 self.n_elite)
+        x_mean, _ = self._dm.rollout_cost(self._x0, u_mean, self._Q, self._R, self._xd)
+        self.std_trj = u_std.cpu().numpy()
+        return x_mean.cpu().numpy(), u_mean.cpu().numpy()
+
+    def iterate(self, max_iterations):
+        """QuasistaticOptimizerBase.iterate; with device_seed set, through ONE irs_cem_iterate call: every descent
+        enqueued back to back, one read-back, then the loop's bookkeeping (the five-term log, best-so-far, the last
+        descent logged but not adopted)."""
+        if self.device_seed is None:
+            return super().iterate(max_iterations)
+        k = max(1, max_iterations - self.current_iter + 2)  # descents the host loop would run from current_iter
+        o = self._dm.cem_iterate(dev.to_dev(np.asarray(self.u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float)),
+                                 self._x0, self._Q, self._Qd, self._R, self._xd, self.batch_size, self.n_elite, k,
+                                 self.device_seed, self.current_iter, quasistatic=True)
+        x_hist, u_hist, std_hist = (o[key].cpu().numpy() for key in ("x_hist", "u_hist", "std_hist"))
+        for i in range(k):
+            if self.verbose:
+                print("Iter {:02d}, cost: {:0.4f}. time: {:0.2f}.".format(self.current_iter, self.cost,
+                                                                        time.time() - self.start_time))
+            x_new, u_new = x_hist[i], u_hist[i]
+            cost_new = self._log(x_new, u_new)
+            self.std_trj = std_hist[i]
+            if self.publish_every_iteration:
+                self.q_dynamics.publish_trajectory(x_new)
+            if i == k - 1:
+                return self.x_trj, self.u_trj, self.cost
+            self.cost, self.x_trj, self.u_trj = cost_new, x_new, u_new
+            self.current_iter += 1
 
     # outer loop: QuasistaticOptimizerBase.iterate
     def _start(self):

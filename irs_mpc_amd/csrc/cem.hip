@@ -8,13 +8,72 @@
 //   4. roll out the mean (:182)                          -> rollout_kernel (tvlqr.hip)
 // All arithmetic in f64: rollout costs only rank the candidates, but ties broken by f32
 // noise would change the elite set and hence the refit.
+//
+// Device-resident form (irs_cem_*_drawn, irs_cem_iterate): the candidate tensor is never stored.  Candidate b,
+// step t, component j is a pure function of (seed, iter, sample_offset + b, t, j) -- cem_candidate below -- so the
+// rollout draws its candidate in the lane as it goes and the refit regenerates only the n_elite winners from their
+// indices.  The stream is the `du` stream of oracle.irs_oracle.device_gaussian_samples(T, B, 0, m, [], ones(m), seed,
+// iter, sample_offset) with axes (T, B, m) -> (B, T, m), scaled by std and shifted by mean in f64.  It deliberately
+// REUSES the counters of the smoothing generator (csrc/philox.hpp): no program here runs CEM and a smoothing pass
+// with the same (seed, iter), so there is no second keying.  It is that generator with the radius of the rare pairs
+// with u1 -> 1 formed from 1 - u1 (philox_normal4<true>): the candidates are held to the f64 restatement element by
+// element (std (2e-5 |z| + 2e-6)), which the f32 rounding of u1 next to 1 misses about once in 3e4 pairs.
 #include "boxqp.hpp"      // has_u_into_x
+#include "philox.hpp"
 
 namespace {
 
-template <class Model>
-__global__ __launch_bounds__(256) void cem_rollout_kernel(ModelParams p, int T, int B,
-                                                          const double* __restrict__ u_cand,
+// The one statement of the candidate stream.  An explicit fma: the rollout, the refit and the debug writer get the
+// same bits whatever the compiler contracts around it.
+__device__ __forceinline__ double cem_candidate(double mean, double std, float z) { return fma(std, (double)z, mean); }
+
+// Where a rollout lane gets its candidate from.  Supplied: the (B,T,m) tensor of the host-draw path.
+// lane(b, T, m): what the lane keeps across the time loop; row<m>(lane, t, u): its controls of step t.
+struct CemSupplied {
+    const double* __restrict__ u_cand;
+    using Lane = const double*;
+    __device__ __forceinline__ Lane lane(int b, int T, int m) const { return u_cand + (size_t)b * T * m; }
+    template <int m>
+    __device__ __forceinline__ void row(Lane ub, int t, double* u) const {
+#pragma unroll
+        for (int j = 0; j < m; ++j) u[j] = ub[(size_t)t * m + j];
+    }
+};
+
+// Drawn: ceil(m/4) Philox calls per (b, t); mean / std rows are uniform addresses (scalar loads), no per-candidate
+// memory is read.
+struct CemDrawn {
+    const double* __restrict__ mean;   // (T,m)
+    const double* __restrict__ std;    // (T,m)
+    uint64_t seed, sample_offset;
+    uint32_t iter;
+    using Lane = uint64_t;             // the candidate's global index
+    __device__ __forceinline__ Lane lane(int b, int, int) const { return sample_offset + (uint64_t)b; }
+    template <int m>
+    __device__ __forceinline__ void row(Lane gidx, int t, double* u) const {
+#pragma unroll
+        for (int blk = 0; blk < (m + 3) / 4; ++blk) {
+            float z[4];
+            philox_normal4<true>(gidx, (uint32_t)t, (uint32_t)blk, iter, seed, z);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int j = 4 * blk + c;
+                if (j < m) u[j] = cem_candidate(mean[(size_t)t * m + j], std[(size_t)t * m + j], z[c]);
+            }
+        }
+    }
+    // one component, m known at run time (refit, debug writer)
+    __device__ __forceinline__ double at(int m, int b, int t, int j) const {
+        float z[4];
+        philox_normal4<true>(sample_offset + (uint64_t)b, (uint32_t)t, (uint32_t)(j >> 2), iter, seed, z);
+        const int c = j & 3;
+        const float zc = c == 0 ? z[0] : c == 1 ? z[1] : c == 2 ? z[2] : z[3];
+        return cem_candidate(mean[(size_t)t * m + j], std[(size_t)t * m + j], zc);
+    }
+};
+
+template <class Model, class Src>
+__global__ __launch_bounds__(256) void cem_rollout_kernel(ModelParams p, int T, int B, Src src,
                                                           const double* __restrict__ x0,
                                                           const double* __restrict__ Q,
                                                           const double* __restrict__ R,
@@ -31,7 +90,7 @@ __global__ __launch_bounds__(256) void cem_rollout_kernel(ModelParams p, int T, 
     double x[n], u[m], xn[n];
 #pragma unroll
     for (int i = 0; i < n; ++i) x[i] = x0[i];
-    const double* ub = u_cand + (size_t)b * T * m;
+    const typename Src::Lane ub = src.lane(b, T, m);
     double cost = 0.0;
     unsigned warm_set = ~0u;          // active set of the previous contact step (exact step QPs only)
     for (int t = 0; t <= T; ++t) {
@@ -48,8 +107,7 @@ __global__ __launch_bounds__(256) void cem_rollout_kernel(ModelParams p, int T, 
             cost += e[i] * r;
         }
         if (t == T) break;
-#pragma unroll
-        for (int j = 0; j < m; ++j) u[j] = ub[(size_t)t * m + j];
+        src.template row<m>(ub, t, u);
 #pragma unroll
         for (int i = 0; i < m; ++i) {
             double r = 0.0;
@@ -67,9 +125,8 @@ __global__ __launch_bounds__(256) void cem_rollout_kernel(ModelParams p, int T, 
 // CrossEntropyMethodQuasistatic.local_descent steps 1-2 (irs_lqr/cem_quasistatic.py:186-200): the
 // candidate cost is IrsLqrQuasistatic's eval_cost (:124-165) -- state error with Q, TERMINAL Qd,
 // input cost on du_t = u_t - u_{t-1} with du_0 = u_0 - x_0[indices_u_into_x].
-template <class Model>
-__global__ __launch_bounds__(64) void cem_rollout_quasistatic_kernel(ModelParams p, int T, int B,
-                                                                     const double* __restrict__ u_cand,
+template <class Model, class Src>
+__global__ __launch_bounds__(64) void cem_rollout_quasistatic_kernel(ModelParams p, int T, int B, Src src,
                                                                      const double* __restrict__ x0,
                                                                      const double* __restrict__ Q,
                                                                      const double* __restrict__ Qd,
@@ -90,7 +147,7 @@ __global__ __launch_bounds__(64) void cem_rollout_quasistatic_kernel(ModelParams
     for (int i = 0; i < n; ++i) x[i] = x0[i];
 #pragma unroll
     for (int j = 0; j < m; ++j) up[j] = x0[Model::u_into_x(j)];
-    const double* ub = u_cand + (size_t)b * T * m;
+    const typename Src::Lane ub = src.lane(b, T, m);
     double cost = 0.0;
     unsigned warm_set = ~0u;          // active set of the previous contact step (exact step QPs only)
     for (int t = 0; t <= T; ++t) {
@@ -108,8 +165,9 @@ __global__ __launch_bounds__(64) void cem_rollout_quasistatic_kernel(ModelParams
         }
         if (t == T) break;
         double dv[m];
+        src.template row<m>(ub, t, u);
 #pragma unroll
-        for (int j = 0; j < m; ++j) { u[j] = ub[(size_t)t * m + j]; dv[j] = u[j] - up[j]; up[j] = u[j]; }
+        for (int j = 0; j < m; ++j) { dv[j] = u[j] - up[j]; up[j] = u[j]; }
 #pragma unroll
         for (int i = 0; i < m; ++i) {
             double r = 0.0;
@@ -242,11 +300,11 @@ __global__ __launch_bounds__(kSelBlock) void cem_select_kernel(const double* __r
 // One workgroup per 64 consecutive outputs q: lane = q (an elite's row is contiguous in q: coalesced), the 16 waves
 // split the elites and meet in LDS, partial sums added in wave order (deterministic).  (One lane per q looping over
 // all elites alone -- 2 x n_elite dependent loads -- took 118 us for 312 elites.)
+// term(b, q) = component q of candidate b; called for q < Tm only.
 constexpr int kRefitWaves = 16;
-__global__ __launch_bounds__(64 * kRefitWaves) void cem_refit_kernel(const double* __restrict__ u_cand,
-                                                                     const int* __restrict__ elite_idx, int n_elite,
-                                                                     int Tm, double* __restrict__ u_new,
-                                                                     double* __restrict__ std_new) {
+template <class Term>
+__device__ __forceinline__ void cem_refit_body(Term term, const int* __restrict__ elite_idx, int n_elite, int Tm,
+                                               double* __restrict__ u_new, double* __restrict__ std_new) {
     __shared__ double part[kRefitWaves][64];
     __shared__ double mean_s[64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -254,7 +312,7 @@ __global__ __launch_bounds__(64 * kRefitWaves) void cem_refit_kernel(const doubl
     const bool on = q < Tm;
     double s = 0.0;
     for (int e = wave; e < n_elite; e += kRefitWaves)
-        s += on ? u_cand[(size_t)elite_idx[e] * Tm + q] : 0.0;
+        s += on ? term(elite_idx[e], q) : 0.0;
     part[wave][lane] = s;
     __syncthreads();
     if (wave == 0) {
@@ -267,7 +325,7 @@ __global__ __launch_bounds__(64 * kRefitWaves) void cem_refit_kernel(const doubl
     const double mean = mean_s[lane];
     double v = 0.0;
     for (int e = wave; e < n_elite; e += kRefitWaves) {
-        const double d = on ? u_cand[(size_t)elite_idx[e] * Tm + q] - mean : 0.0;
+        const double d = on ? term(elite_idx[e], q) - mean : 0.0;
         v += d * d;
     }
     __syncthreads();
@@ -280,6 +338,88 @@ __global__ __launch_bounds__(64 * kRefitWaves) void cem_refit_kernel(const doubl
         u_new[q] = mean;
         std_new[q] = sqrt(t / n_elite);
     }
+}
+
+__global__ __launch_bounds__(64 * kRefitWaves) void cem_refit_kernel(const double* __restrict__ u_cand,
+                                                                     const int* __restrict__ elite_idx, int n_elite,
+                                                                     int Tm, double* __restrict__ u_new,
+                                                                     double* __restrict__ std_new) {
+    cem_refit_body([=](int b, int q) { return u_cand[(size_t)b * Tm + q]; }, elite_idx, n_elite, Tm, u_new, std_new);
+}
+
+// The same sums with every term regenerated from (elite_idx[e], t, j) instead of loaded: one Philox call per term
+// and pass.  Reads the OLD mean / std (src) and writes the new ones: u_new / std_new must not alias them.
+__global__ __launch_bounds__(64 * kRefitWaves) void cem_refit_drawn_kernel(CemDrawn src, int m,
+                                                                           const int* __restrict__ elite_idx,
+                                                                           int n_elite, int Tm,
+                                                                           double* __restrict__ u_new,
+                                                                           double* __restrict__ std_new) {
+    cem_refit_body([=](int b, int q) { return src.at(m, b, q / m, q % m); }, elite_idx, n_elite, Tm, u_new, std_new);
+}
+
+// Debug writer: the (B,T,m) tensor the drawn rollout and the drawn refit see (as irs_rng_samples for the smoothing
+// stream).  One thread per element.
+__global__ __launch_bounds__(256) void cem_candidates_kernel(CemDrawn src, int m, int Tm, size_t total,
+                                                             double* __restrict__ u_cand) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int b = (int)(i / Tm), q = (int)(i - (size_t)b * Tm);
+    u_cand[i] = src.at(m, b, q / m, q % m);
+}
+
+// [a, a + len) and [b, b + len) share an element
+bool overlap(const double* a, const double* b, size_t len) { return a < b + len && b < a + len; }
+
+constexpr size_t round256(size_t v) { return (v + 255) / 256 * 256; }
+
+int launch_rollout_drawn(int model, const ModelParams& p, int T, int B, const CemDrawn& src, const double* x0,
+                         const double* Q, const double* R, const double* xd_trj, double* costs, hipStream_t st) {
+    IRS_DISPATCH_MODEL(model, {
+        hipLaunchKernelGGL((cem_rollout_kernel<Model, CemDrawn>), dim3((B + 255) / 256), dim3(256), 0, st, p, T, B, src,
+                           x0, Q, R, xd_trj, costs);
+    });
+    return IRS_OK;
+}
+
+// Src = CemSupplied or CemDrawn.  IRS_ERR_UNSUPPORTED (nothing launched) unless the model is position controlled.
+template <class Src>
+int launch_rollout_quasistatic(int model, const ModelParams& p, int T, int B, const Src& src, const double* x0,
+                               const double* Q, const double* Qd, const double* R, const double* xd_trj,
+                               double* costs, hipStream_t st) {
+    int rc = IRS_ERR_UNSUPPORTED;
+    IRS_DISPATCH_MODEL(model, {
+        if constexpr (has_u_into_x<Model>::value) {
+            // one wave per workgroup: the contact step holds hundreds of f64 registers per lane
+            hipLaunchKernelGGL((cem_rollout_quasistatic_kernel<Model, Src>), dim3((B + 63) / 64), dim3(64), 0, st, p,
+                               T, B, src, x0, Q, Qd, R, xd_trj, costs);
+            rc = IRS_OK;
+        }
+    });
+    return rc;
+}
+
+bool position_controlled(int model) {
+    bool yes = false;
+    switch (model) {
+        default: break;
+#define CEM_PC(ID_, M_) case ID_: yes = has_u_into_x<M_>::value; break;
+        CEM_PC(IRS_MODEL_PENDULUM, PendulumModel) CEM_PC(IRS_MODEL_QUADROTOR, QuadrotorModel)
+        CEM_PC(IRS_MODEL_BICYCLE, BicycleModel) CEM_PC(IRS_MODEL_THREE_CART, ThreeCartModel)
+        CEM_PC(IRS_MODEL_PLANAR_HAND, PlanarHandModel) CEM_PC(IRS_MODEL_BOX_PIVOT, BoxPivotModel)
+        CEM_PC(IRS_MODEL_BOX_ON_BOX, BoxOnBoxModel) CEM_PC(IRS_MODEL_BOX_PUSH, BoxPushModel)
+        CEM_PC(IRS_MODEL_PLANAR_HAND_EXACT, PlanarHandExactModel) CEM_PC(IRS_MODEL_BOX_PIVOT_EXACT, BoxPivotExactModel)
+        CEM_PC(IRS_MODEL_BOX_PUSH_EXACT, BoxPushExactModel)
+#undef CEM_PC
+    }
+    return yes;
+}
+
+void launch_refit_drawn(int T, int m, int B, int n_elite, const CemDrawn& src, const double* costs, int* elite_idx,
+                        double* u_new, double* std_new, hipStream_t st) {
+    hipLaunchKernelGGL(cem_select_kernel, dim3(1), dim3(kSelBlock), 0, st, costs, B, n_elite, elite_idx);
+    const int Tm = T * m;
+    hipLaunchKernelGGL(cem_refit_drawn_kernel, dim3((Tm + 63) / 64), dim3(64 * kRefitWaves), 0, st, src, m, elite_idx,
+                       n_elite, Tm, u_new, std_new);
 }
 
 }  // namespace
@@ -295,8 +435,8 @@ int irs_cem_rollout_costs(int model, const double* params, int n_params, int T, 
     if (rc != IRS_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     IRS_DISPATCH_MODEL(model, {
-        hipLaunchKernelGGL((cem_rollout_kernel<Model>), dim3((B + 255) / 256), dim3(256), 0, st, p, T, B,
-                           u_cand, x0, Q, R, xd_trj, costs);
+        hipLaunchKernelGGL((cem_rollout_kernel<Model, CemSupplied>), dim3((B + 255) / 256), dim3(256), 0, st, p, T, B,
+                           CemSupplied{u_cand}, x0, Q, R, xd_trj, costs);
     });
     IRS_CHECK_LAUNCH();
     return IRS_OK;
@@ -310,19 +450,12 @@ int irs_cem_rollout_costs_quasistatic(int model, const double* params, int n_par
     ModelParams p;
     int rc = irs_load_params(model, params, n_params, &p);
     if (rc != IRS_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = IRS_ERR_UNSUPPORTED;
-    IRS_DISPATCH_MODEL(model, {
-        if constexpr (has_u_into_x<Model>::value) {
-            // one wave per workgroup: the contact step holds hundreds of f64 registers per lane
-            hipLaunchKernelGGL((cem_rollout_quasistatic_kernel<Model>), dim3((B + 63) / 64), dim3(64), 0, st, p,
-                               T, B, u_cand, x0, Q, Qd, R, xd_trj, costs);
-            rc = IRS_OK;
-        } else {
-            irs_set_error("irs_cem_rollout_costs_quasistatic: model %d is not position controlled", model);
-        }
-    });
-    if (rc != IRS_OK) return rc;
+    rc = launch_rollout_quasistatic(model, p, T, B, CemSupplied{u_cand}, x0, Q, Qd, R, xd_trj, costs,
+                                    static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) {
+        irs_set_error("irs_cem_rollout_costs_quasistatic: model %d is not position controlled", model);
+        return rc;
+    }
     IRS_CHECK_LAUNCH();
     return IRS_OK;
 }
@@ -337,6 +470,129 @@ int irs_cem_refit(int T, int m, int B, int n_elite, const double* u_cand, const 
     const int Tm = T * m;
     hipLaunchKernelGGL(cem_refit_kernel, dim3((Tm + 63) / 64), dim3(64 * kRefitWaves), 0, st, u_cand, elite_idx, n_elite,
                        Tm, u_new, std_new);
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+// ---- device-resident form: candidates drawn in the kernels ---------------------------------------------------
+
+int irs_cem_candidates(int T, int m, int B, const double* u_mean, const double* std, uint64_t seed, uint32_t iter,
+                       uint64_t sample_offset, double* u_cand, void* stream) {
+    IRS_CHECK_ARG(T > 0 && m > 0 && B > 0, "sizes must be positive");
+    IRS_CHECK_ARG(u_mean && std && u_cand, "null pointer");
+    const size_t total = (size_t)B * T * m;
+    IRS_CHECK_ARG((total + 255) / 256 <= 0x7fffffffull, "B T m too large for one launch");
+    const CemDrawn src{u_mean, std, seed, sample_offset, iter};
+    hipLaunchKernelGGL(cem_candidates_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), src, m, T * m, total, u_cand);
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+int irs_cem_rollout_costs_drawn(int model, const double* params, int n_params, int T, int B, const double* u_mean,
+                                const double* std, uint64_t seed, uint32_t iter, uint64_t sample_offset,
+                                const double* x0, const double* Q, const double* R, const double* xd_trj,
+                                double* costs, void* stream) {
+    IRS_CHECK_ARG(T > 0 && B > 0 && u_mean && std && x0 && Q && R && xd_trj && costs, "bad argument");
+    ModelParams p;
+    int rc = irs_load_params(model, params, n_params, &p);
+    if (rc != IRS_OK) return rc;
+    rc = launch_rollout_drawn(model, p, T, B, CemDrawn{u_mean, std, seed, sample_offset, iter}, x0, Q, R, xd_trj, costs,
+                              static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) return rc;
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+int irs_cem_rollout_costs_quasistatic_drawn(int model, const double* params, int n_params, int T, int B,
+                                            const double* u_mean, const double* std, uint64_t seed, uint32_t iter,
+                                            uint64_t sample_offset, const double* x0, const double* Q,
+                                            const double* Qd, const double* R, const double* xd_trj, double* costs,
+                                            void* stream) {
+    IRS_CHECK_ARG(T > 0 && B > 0 && u_mean && std && x0 && Q && Qd && R && xd_trj && costs, "bad argument");
+    ModelParams p;
+    int rc = irs_load_params(model, params, n_params, &p);
+    if (rc != IRS_OK) return rc;
+    rc = launch_rollout_quasistatic(model, p, T, B, CemDrawn{u_mean, std, seed, sample_offset, iter}, x0, Q, Qd, R,
+                                    xd_trj, costs, static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) {
+        irs_set_error("irs_cem_rollout_costs_quasistatic_drawn: model %d is not position controlled", model);
+        return rc;
+    }
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+int irs_cem_refit_drawn(int T, int m, int B, int n_elite, const double* u_mean, const double* std, uint64_t seed,
+                        uint32_t iter, uint64_t sample_offset, const double* costs, int* elite_idx, double* u_new,
+                        double* std_new, void* stream) {
+    IRS_CHECK_ARG(T > 0 && m > 0 && B > 0 && n_elite > 0 && n_elite <= B, "need 0 < n_elite <= B");
+    IRS_CHECK_ARG(u_mean && std && costs && elite_idx && u_new && std_new, "null pointer");
+    const size_t len = (size_t)T * m;
+    IRS_CHECK_ARG(!overlap(u_new, u_mean, len) && !overlap(u_new, std, len) && !overlap(std_new, u_mean, len) &&
+                      !overlap(std_new, std, len) && !overlap(u_new, std_new, len),
+                  "u_new / std_new must not alias u_mean / std (the refit reads the old ones while it writes)");
+    launch_refit_drawn(T, m, B, n_elite, CemDrawn{u_mean, std, seed, sample_offset, iter}, costs, elite_idx, u_new,
+                       std_new, static_cast<hipStream_t>(stream));
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+// costs (B) | elite_idx (n_elite) | the plain cost of the mean's rollout where the quasistatic one is reported
+size_t irs_cem_iterate_scratch_bytes(int T, int m, int B, int n_elite) {
+    if (T <= 0 || m <= 0 || B <= 0 || n_elite <= 0) return 0;
+    return round256((size_t)B * sizeof(double)) + round256((size_t)n_elite * sizeof(int)) + 256;
+}
+
+int irs_cem_iterate(const irs_cem_iterate_call* c, void* stream) {
+    IRS_CHECK_ARG(c != nullptr, "null call struct");
+    IRS_CHECK_ARG(c->T > 0 && c->B > 0 && c->n_descents > 0, "T, B and n_descents must be positive");
+    IRS_CHECK_ARG(c->n_elite > 0 && c->n_elite <= c->B, "need 0 < n_elite <= B");
+    IRS_CHECK_ARG(c->Q && c->R && c->xd_trj && c->x0 && c->u_trj0 && c->std0, "null problem pointer");
+    IRS_CHECK_ARG(!c->quasistatic || c->Qd, "the quasistatic cost needs Qd");
+    IRS_CHECK_ARG(c->u_hist && c->std_hist && c->x_hist && c->cost_hist && c->scratch, "null output / scratch pointer");
+    int n, m, np;
+    int rc = irs_model_info(c->model, &n, &m, &np);
+    if (rc != IRS_OK) return rc;
+    ModelParams p;
+    rc = irs_load_params(c->model, c->params, c->n_params, &p);
+    if (rc != IRS_OK) return rc;
+    if (c->quasistatic && !position_controlled(c->model)) {
+        irs_set_error("irs_cem_iterate: model %d is not position controlled", c->model);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    const int T = c->T, B = c->B;
+    const size_t need = irs_cem_iterate_scratch_bytes(T, m, B, c->n_elite);
+    if (c->scratch_bytes < need) {
+        irs_set_error("irs_cem_iterate: scratch %zu < %zu bytes", c->scratch_bytes, need);
+        return IRS_ERR_INVALID_ARG;
+    }
+    char* sp = static_cast<char*>(c->scratch);
+    double* costs = reinterpret_cast<double*>(sp);
+    int* elite_idx = reinterpret_cast<int*>(sp + round256((size_t)B * sizeof(double)));
+    double* plain_cost = reinterpret_cast<double*>(sp + need - 256);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t us = (size_t)T * m, xs = (size_t)(T + 1) * n;
+    for (int i = 0; i < c->n_descents; ++i) {
+        // draw around the previous descent's refit (std is always carried; the caller decides what "adopted" means)
+        const CemDrawn src{i == 0 ? c->u_trj0 : c->u_hist + (size_t)(i - 1) * us,
+                           i == 0 ? c->std0 : c->std_hist + (size_t)(i - 1) * us, c->seed, 0, c->iter0 + (uint32_t)i};
+        double* u_new = c->u_hist + (size_t)i * us;
+        rc = c->quasistatic ? launch_rollout_quasistatic(c->model, p, T, B, src, c->x0, c->Q, c->Qd, c->R, c->xd_trj,
+                                                         costs, st)
+                            : launch_rollout_drawn(c->model, p, T, B, src, c->x0, c->Q, c->R, c->xd_trj, costs, st);
+        if (rc != IRS_OK) return rc;
+        launch_refit_drawn(T, m, B, c->n_elite, src, costs, elite_idx, u_new, c->std_hist + (size_t)i * us, st);
+        // the mean's rollout (cem.py:182), priced like the candidates
+        rc = irs_rollout_cost(c->model, c->params, c->n_params, T, c->x0, u_new, c->Q, c->R, c->xd_trj,
+                              c->x_hist + (size_t)i * xs, c->quasistatic ? plain_cost : c->cost_hist + i, stream);
+        if (rc != IRS_OK) return rc;
+        if (c->quasistatic) {
+            rc = launch_rollout_quasistatic(c->model, p, T, 1, CemSupplied{u_new}, c->x0, c->Q, c->Qd, c->R, c->xd_trj,
+                                            c->cost_hist + i, st);
+            if (rc != IRS_OK) return rc;
+        }
+    }
     IRS_CHECK_LAUNCH();
     return IRS_OK;
 }

@@ -321,6 +321,74 @@ class DeviceModel:
                                      _ptr(u_new, F64), _ptr(std_new, F64), _stream()), "irs_cem_refit")
         return idx, u_new, std_new
 
+    # device-resident form: the candidates are drawn inside the kernels (include/irs_hip.h), never stored
+    def cem_candidates(self, u_mean, std, B, seed, it, sample_offset=0):
+        """The (B,T,m) candidates the drawn kernels see (verification only)."""
+        T, m = u_mean.shape
+        u_cand = torch.empty((B, T, m), dtype=F64, device=u_mean.device)
+        check(self.lib.irs_cem_candidates(T, m, int(B), _ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it),
+                                          int(sample_offset), _ptr(u_cand, F64), _stream()), "irs_cem_candidates")
+        return u_cand
+
+    def cem_rollout_costs_drawn(self, u_mean, std, B, seed, it, x0, Q, R, xd_trj, sample_offset=0):
+        """cem_rollout_costs of B candidates drawn around u_mean (T,m) with std (T,m)."""
+        costs = torch.empty((int(B),), dtype=F64, device=u_mean.device)
+        check(self.lib.irs_cem_rollout_costs_drawn(self.model_id, self._p, self._np, u_mean.shape[0], int(B),
+                                                   _ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it),
+                                                   int(sample_offset), _ptr(x0, F64), _ptr(Q, F64), _ptr(R, F64),
+                                                   _ptr(xd_trj, F64), _ptr(costs, F64), _stream()),
+              "irs_cem_rollout_costs_drawn")
+        return costs
+
+    def cem_rollout_costs_quasistatic_drawn(self, u_mean, std, B, seed, it, x0, Q, Qd, R, xd_trj, sample_offset=0):
+        """cem_rollout_costs_quasistatic of B drawn candidates."""
+        costs = torch.empty((int(B),), dtype=F64, device=u_mean.device)
+        check(self.lib.irs_cem_rollout_costs_quasistatic_drawn(self.model_id, self._p, self._np, u_mean.shape[0], int(B),
+                                                               _ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it),
+                                                               int(sample_offset), _ptr(x0, F64), _ptr(Q, F64),
+                                                               _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64),
+                                                               _ptr(costs, F64), _stream()),
+              "irs_cem_rollout_costs_quasistatic_drawn")
+        return costs
+
+    def cem_refit_drawn(self, u_mean, std, seed, it, costs, n_elite, sample_offset=0):
+        """cem_refit with the elites regenerated from their indices: elite_idx, u_new, std_new (fresh tensors)."""
+        T, m = u_mean.shape
+        dev = u_mean.device
+        idx = torch.empty((n_elite,), dtype=torch.int32, device=dev)
+        u_new = torch.empty((T, m), dtype=F64, device=dev)
+        std_new = torch.empty((T, m), dtype=F64, device=dev)
+        check(self.lib.irs_cem_refit_drawn(T, m, costs.shape[0], int(n_elite), _ptr(u_mean, F64), _ptr(std, F64),
+                                           int(seed), int(it), int(sample_offset), _ptr(costs, F64), idx.data_ptr(),
+                                           _ptr(u_new, F64), _ptr(std_new, F64), _stream()), "irs_cem_refit_drawn")
+        return idx, u_new, std_new
+
+    def cem_iterate(self, u_trj0, std0, x0, Q, Qd, R, xd_trj, B, n_elite, n_descents, seed, iter0=1,
+                    quasistatic=False):
+        """n_descents CEM descents in ONE library call (irs_cem_iterate), nothing read back: a dict of the device
+        histories u_hist, std_hist (n_descents,T,m), x_hist (n_descents,T+1,n), cost_hist (n_descents)."""
+        T, m = u_trj0.shape
+        dev, k = u_trj0.device, int(n_descents)
+        o = {"u_hist": torch.empty((k, T, m), dtype=F64, device=dev),
+             "std_hist": torch.empty((k, T, m), dtype=F64, device=dev),
+             "x_hist": torch.empty((k, T + 1, self.n), dtype=F64, device=dev),
+             "cost_hist": torch.empty((k,), dtype=F64, device=dev)}
+        need = self.lib.irs_cem_iterate_scratch_bytes(T, m, int(B), int(n_elite))
+        scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+        c = _lib.CemIterateCall()
+        c.model, c.n_params = self.model_id, self._np
+        for i, v in enumerate(self.params):
+            c.params[i] = v
+        c.T, c.B, c.n_elite, c.n_descents, c.quasistatic = T, int(B), int(n_elite), k, int(bool(quasistatic))
+        c.seed, c.iter0 = int(seed), int(iter0)
+        c.Q, c.Qd, c.R, c.xd_trj, c.x0 = (_ptr(a, F64) for a in (Q, Qd, R, xd_trj, x0))
+        c.u_trj0, c.std0 = _ptr(u_trj0, F64), _ptr(std0, F64)
+        c.u_hist, c.std_hist, c.x_hist, c.cost_hist = (_ptr(o[key], F64) for key in ("u_hist", "std_hist", "x_hist",
+                                                                                      "cost_hist"))
+        c.scratch, c.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        check(self.lib.irs_cem_iterate(ctypes.byref(c), _stream()), "irs_cem_iterate")
+        return o
+
     def smooth_accumulate(self, mode, x_trj, u_trj, dx, du, sums=None):
         """Sample pass on supplied samples: dx (T,N,n) f32 (None for ZERO_ORDER_B), du (T,N,m) f32."""
         T, N = du.shape[0], du.shape[1]
