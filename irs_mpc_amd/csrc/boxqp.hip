@@ -33,19 +33,9 @@
 #include <climits>
 
 #include "boxqp.hpp"
+#include "wave.hpp"
 
 namespace {
-
-__device__ __forceinline__ void wave_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fmax(v, __shfl_xor(v, s, 64));
-    return v;
-}
 
 template <int N, int M>
 struct BoxLayout {

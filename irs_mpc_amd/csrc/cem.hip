@@ -372,23 +372,22 @@ bool overlap(const double* a, const double* b, size_t len) { return a < b + len 
 
 constexpr size_t round256(size_t v) { return (v + 255) / 256 * 256; }
 
-int launch_rollout_drawn(int model, const ModelParams& p, int T, int B, const CemDrawn& src, const double* x0,
-                         const double* Q, const double* R, const double* xd_trj, double* costs, hipStream_t st) {
-    IRS_DISPATCH_MODEL(model, {
-        hipLaunchKernelGGL((cem_rollout_kernel<Model, CemDrawn>), dim3((B + 255) / 256), dim3(256), 0, st, p, T, B, src,
-                           x0, Q, R, xd_trj, costs);
-    });
-    return IRS_OK;
-}
+// Which cost a rollout prices its candidates with: CrossEntropyMethod's (cem_rollout_kernel) or IrsLqrQuasistatic's
+// (cem_rollout_quasistatic_kernel: needs Qd and a position-controlled model).
+enum class CemCost { Plain, Quasistatic };
 
-// Src = CemSupplied or CemDrawn.  IRS_ERR_UNSUPPORTED (nothing launched) unless the model is position controlled.
-template <class Src>
-int launch_rollout_quasistatic(int model, const ModelParams& p, int T, int B, const Src& src, const double* x0,
-                               const double* Q, const double* Qd, const double* R, const double* xd_trj,
-                               double* costs, hipStream_t st) {
+// Src = CemSupplied or CemDrawn.  Qd is read by the quasistatic cost only.  IRS_ERR_UNSUPPORTED (nothing launched) when
+// the quasistatic cost is asked of a model that is not position controlled.
+template <CemCost COST, class Src>
+int launch_rollout(int model, const ModelParams& p, int T, int B, const Src& src, const double* x0, const double* Q,
+                   const double* Qd, const double* R, const double* xd_trj, double* costs, hipStream_t st) {
     int rc = IRS_ERR_UNSUPPORTED;
     IRS_DISPATCH_MODEL(model, {
-        if constexpr (has_u_into_x<Model>::value) {
+        if constexpr (COST == CemCost::Plain) {
+            hipLaunchKernelGGL((cem_rollout_kernel<Model, Src>), dim3((B + 255) / 256), dim3(256), 0, st, p, T, B, src,
+                               x0, Q, R, xd_trj, costs);
+            rc = IRS_OK;
+        } else if constexpr (has_u_into_x<Model>::value) {
             // one wave per workgroup: the contact step holds hundreds of f64 registers per lane
             hipLaunchKernelGGL((cem_rollout_quasistatic_kernel<Model, Src>), dim3((B + 63) / 64), dim3(64), 0, st, p,
                                T, B, src, x0, Q, Qd, R, xd_trj, costs);
@@ -398,20 +397,13 @@ int launch_rollout_quasistatic(int model, const ModelParams& p, int T, int B, co
     return rc;
 }
 
-bool position_controlled(int model) {
-    bool yes = false;
-    switch (model) {
-        default: break;
-#define CEM_PC(ID_, M_) case ID_: yes = has_u_into_x<M_>::value; break;
-        CEM_PC(IRS_MODEL_PENDULUM, PendulumModel) CEM_PC(IRS_MODEL_QUADROTOR, QuadrotorModel)
-        CEM_PC(IRS_MODEL_BICYCLE, BicycleModel) CEM_PC(IRS_MODEL_THREE_CART, ThreeCartModel)
-        CEM_PC(IRS_MODEL_PLANAR_HAND, PlanarHandModel) CEM_PC(IRS_MODEL_BOX_PIVOT, BoxPivotModel)
-        CEM_PC(IRS_MODEL_BOX_ON_BOX, BoxOnBoxModel) CEM_PC(IRS_MODEL_BOX_PUSH, BoxPushModel)
-        CEM_PC(IRS_MODEL_PLANAR_HAND_EXACT, PlanarHandExactModel) CEM_PC(IRS_MODEL_BOX_PIVOT_EXACT, BoxPivotExactModel)
-        CEM_PC(IRS_MODEL_BOX_PUSH_EXACT, BoxPushExactModel)
-#undef CEM_PC
-    }
-    return yes;
+// IRS_OK for a position-controlled model, else IRS_ERR_UNSUPPORTED
+int position_controlled(int model) {
+    int rc = IRS_ERR_UNSUPPORTED;
+    IRS_DISPATCH_MODEL(model, {
+        if (has_u_into_x<Model>::value) rc = IRS_OK;
+    });
+    return rc;
 }
 
 void launch_refit_drawn(int T, int m, int B, int n_elite, const CemDrawn& src, const double* costs, int* elite_idx,
@@ -433,11 +425,9 @@ int irs_cem_rollout_costs(int model, const double* params, int n_params, int T, 
     ModelParams p;
     int rc = irs_load_params(model, params, n_params, &p);
     if (rc != IRS_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    IRS_DISPATCH_MODEL(model, {
-        hipLaunchKernelGGL((cem_rollout_kernel<Model, CemSupplied>), dim3((B + 255) / 256), dim3(256), 0, st, p, T, B,
-                           CemSupplied{u_cand}, x0, Q, R, xd_trj, costs);
-    });
+    rc = launch_rollout<CemCost::Plain>(model, p, T, B, CemSupplied{u_cand}, x0, Q, nullptr, R, xd_trj, costs,
+                                        static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
 }
@@ -450,8 +440,8 @@ int irs_cem_rollout_costs_quasistatic(int model, const double* params, int n_par
     ModelParams p;
     int rc = irs_load_params(model, params, n_params, &p);
     if (rc != IRS_OK) return rc;
-    rc = launch_rollout_quasistatic(model, p, T, B, CemSupplied{u_cand}, x0, Q, Qd, R, xd_trj, costs,
-                                    static_cast<hipStream_t>(stream));
+    rc = launch_rollout<CemCost::Quasistatic>(model, p, T, B, CemSupplied{u_cand}, x0, Q, Qd, R, xd_trj, costs,
+                                              static_cast<hipStream_t>(stream));
     if (rc != IRS_OK) {
         irs_set_error("irs_cem_rollout_costs_quasistatic: model %d is not position controlled", model);
         return rc;
@@ -497,8 +487,8 @@ int irs_cem_rollout_costs_drawn(int model, const double* params, int n_params, i
     ModelParams p;
     int rc = irs_load_params(model, params, n_params, &p);
     if (rc != IRS_OK) return rc;
-    rc = launch_rollout_drawn(model, p, T, B, CemDrawn{u_mean, std, seed, sample_offset, iter}, x0, Q, R, xd_trj, costs,
-                              static_cast<hipStream_t>(stream));
+    rc = launch_rollout<CemCost::Plain>(model, p, T, B, CemDrawn{u_mean, std, seed, sample_offset, iter}, x0, Q, nullptr, R,
+                                        xd_trj, costs, static_cast<hipStream_t>(stream));
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
@@ -513,8 +503,8 @@ int irs_cem_rollout_costs_quasistatic_drawn(int model, const double* params, int
     ModelParams p;
     int rc = irs_load_params(model, params, n_params, &p);
     if (rc != IRS_OK) return rc;
-    rc = launch_rollout_quasistatic(model, p, T, B, CemDrawn{u_mean, std, seed, sample_offset, iter}, x0, Q, Qd, R,
-                                    xd_trj, costs, static_cast<hipStream_t>(stream));
+    rc = launch_rollout<CemCost::Quasistatic>(model, p, T, B, CemDrawn{u_mean, std, seed, sample_offset, iter}, x0, Q, Qd,
+                                              R, xd_trj, costs, static_cast<hipStream_t>(stream));
     if (rc != IRS_OK) {
         irs_set_error("irs_cem_rollout_costs_quasistatic_drawn: model %d is not position controlled", model);
         return rc;
@@ -557,7 +547,7 @@ int irs_cem_iterate(const irs_cem_iterate_call* c, void* stream) {
     ModelParams p;
     rc = irs_load_params(c->model, c->params, c->n_params, &p);
     if (rc != IRS_OK) return rc;
-    if (c->quasistatic && !position_controlled(c->model)) {
+    if (c->quasistatic && position_controlled(c->model) != IRS_OK) {
         irs_set_error("irs_cem_iterate: model %d is not position controlled", c->model);
         return IRS_ERR_UNSUPPORTED;
     }
@@ -578,9 +568,10 @@ int irs_cem_iterate(const irs_cem_iterate_call* c, void* stream) {
         const CemDrawn src{i == 0 ? c->u_trj0 : c->u_hist + (size_t)(i - 1) * us,
                            i == 0 ? c->std0 : c->std_hist + (size_t)(i - 1) * us, c->seed, 0, c->iter0 + (uint32_t)i};
         double* u_new = c->u_hist + (size_t)i * us;
-        rc = c->quasistatic ? launch_rollout_quasistatic(c->model, p, T, B, src, c->x0, c->Q, c->Qd, c->R, c->xd_trj,
-                                                         costs, st)
-                            : launch_rollout_drawn(c->model, p, T, B, src, c->x0, c->Q, c->R, c->xd_trj, costs, st);
+        rc = c->quasistatic ? launch_rollout<CemCost::Quasistatic>(c->model, p, T, B, src, c->x0, c->Q, c->Qd, c->R,
+                                                                   c->xd_trj, costs, st)
+                            : launch_rollout<CemCost::Plain>(c->model, p, T, B, src, c->x0, c->Q, nullptr, c->R,
+                                                             c->xd_trj, costs, st);
         if (rc != IRS_OK) return rc;
         launch_refit_drawn(T, m, B, c->n_elite, src, costs, elite_idx, u_new, c->std_hist + (size_t)i * us, st);
         // the mean's rollout (cem.py:182), priced like the candidates
@@ -588,8 +579,8 @@ int irs_cem_iterate(const irs_cem_iterate_call* c, void* stream) {
                               c->x_hist + (size_t)i * xs, c->quasistatic ? plain_cost : c->cost_hist + i, stream);
         if (rc != IRS_OK) return rc;
         if (c->quasistatic) {
-            rc = launch_rollout_quasistatic(c->model, p, T, 1, CemSupplied{u_new}, c->x0, c->Q, c->Qd, c->R, c->xd_trj,
-                                            c->cost_hist + i, st);
+            rc = launch_rollout<CemCost::Quasistatic>(c->model, p, T, 1, CemSupplied{u_new}, c->x0, c->Q, c->Qd, c->R,
+                                                      c->xd_trj, c->cost_hist + i, st);
             if (rc != IRS_OK) return rc;
         }
     }

@@ -25,46 +25,12 @@
 //
 // One solver wave (+ one plant wave), f64, everything in (dynamic) LDS: a latency-bound chain like the Riccati pass.
 #include "boxqp.hpp"
+#include "wave.hpp"
 
 namespace {
 
 constexpr int kPdasIter = 10;
 constexpr int KIND_ABS = 0, KIND_REL = 1;
-
-__device__ __forceinline__ void wave_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// 1/d to ~1 ulp: hardware reciprocal + two Newton steps (a correctly rounded f64 divide is ~40
-// dependent instructions, four times on the critical path of every backward step)
-__device__ __forceinline__ double fast_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    return r;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fmax(v, __shfl_xor(v, s, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fmin(v, __shfl_xor(v, s, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = max(v, __shfl_xor(v, s, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = min(v, __shfl_xor(v, s, 64));
-    return v;
-}
 
 // LDS record of one time step (doubles).  Record T holds only P, p.
 template <int NR, int M>
@@ -210,15 +176,9 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
     if (lane == 0) {
         a.info[0] = -1; a.info[1] = -1; a.info[2] = -1;
     }
-    for (int q = lane; q < NR * NR; q += 64) {
-        int i = q / NR, j = q % NR;
-        Qsym[q] = 0.5 * (a.Q[i * NR + j] + a.Q[j * NR + i]);
-        Qdsym[q] = 0.5 * (a.Qd[i * NR + j] + a.Qd[j * NR + i]);
-    }
-    for (int q = lane; q < M * M; q += 64) {
-        int i = q / M, j = q % M;
-        Rsym[q] = 0.5 * (a.R[i * M + j] + a.R[j * M + i]);
-    }
+    sym_part(Qsym, a.Q, NR, 0.5, lane);
+    sym_part(Qdsym, a.Qd, NR, 0.5, lane);
+    sym_part(Rsym, a.R, M, 0.5, lane);
     for (int q = lane; q < L::NTRI; q += 64) {
         int i = 0, r = q;
         while (r >= NS - i) { r -= NS - i; ++i; }
@@ -467,11 +427,6 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
     // them.  The coefficient rows of step t+1 are fetched from LDS while step t computes, so the
     // dependent chain per step is two length-NS FMA chains and 2 (M + NR) readlanes -- no LDS round
     // trip.  Outputs (controls -> record offset `dst`, multipliers -> omu) are stored off the chain.
-    auto bcast = [&](double v, int src) -> double {
-        const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-        const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-        return __hiloint2double(hi, lo);
-    };
     struct Rows { double r1[NS], r2[NS], r3[M], c1, c2; };
     auto load_rows = [&](int t, Rows& R) {
         const double* rec = rec_(t);
@@ -501,7 +456,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
             for (int l = 0; l < NS; ++l) acc += cur.r1[l] * sr[l];      // control lane: K_j s + k_j; x lane: A_i x + c_i
             double v[M];
 #pragma unroll
-            for (int j = 0; j < M; ++j) v[j] = bcast(acc, j);
+            for (int j = 0; j < M; ++j) v[j] = readlane_f64(acc, j);
             double ua[M];                                                // absolute command
 #pragma unroll
             for (int j = 0; j < M; ++j) ua[j] = v[j] + (KIND == KIND_REL ? sr[NR + j] : 0.0);
@@ -519,7 +474,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
             }
             const double xrow = acc + tail;                              // meaningful on lanes M..M+NR-1
 #pragma unroll
-            for (int i = 0; i < NR; ++i) sr[i] = bcast(xrow, M + i);
+            for (int i = 0; i < NR; ++i) sr[i] = readlane_f64(xrow, M + i);
 #pragma unroll
             for (int j = 0; j < M; ++j) sr[NR + j] = ua[j];
             cur = nxt;
@@ -560,7 +515,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
                 }
                 if (nw != ac) { rec[L::oact + j] = nw; chg = max(chg, t); }
             }
-            chg = wave_max_i(chg);
+            chg = wave_max(chg);
             wave_sync();
             if (chg < 0) conv = true;
             else t_dirty = chg;
@@ -577,7 +532,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
                 const double nw = u <= lo ? -1.0 : (u >= hi ? 1.0 : 0.0);
                 if (nw != rec[L::oact + j]) { rec[L::oact + j] = nw; chg = max(chg, t); }
             }
-            chg = wave_max_i(chg);
+            chg = wave_max(chg);
             wave_sync();
             t_dirty = max(t_dirty, chg);
             for (int it2 = 0; it2 < a.max_iter && !conv; ++it2) {
@@ -601,7 +556,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
                 }
                 const double alpha = wave_min(best);
                 if (alpha < 1.0) {
-                    const int qb = wave_min_i(best == alpha ? bq : 0x7fffffff);
+                    const int qb = wave_min(best == alpha ? bq : 0x7fffffff);
                     for (int q = t0 * M + lane; q < T * M; q += 64) {
                         const int t = q / M, j = q % M;
                         double* rec = rec_(t);
@@ -633,7 +588,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
                     wave_sync();
                     conv = true;
                 } else {
-                    const int qw = wave_min_i(worst == wmax ? wq : 0x7fffffff);
+                    const int qw = wave_min(worst == wmax ? wq : 0x7fffffff);
                     if (lane == 0) rec_(qw / M)[L::oact + qw % M] = 0.0;
                     wave_sync();
                     t_dirty = qw / M;

@@ -33,10 +33,10 @@
 // backward step; here ~2300 measured with in-kernel cycle stamps: 9 MFMAs at 64-108 cycles each in a
 // dependent chain, ~700 cycles to gather H into every lane, ~200 for the masked inverse).
 #include "boxqp.hpp"
+#include "wave.hpp"
 
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 // the caller's (A, B, c) are read through GLOBAL-address-space pointers: a generic pointer makes them
 // flat loads, which count against lgkmcnt too -- every wait for an LDS read would then also wait for the
 // prefetch of the next step's data (measured: 1.8 us per backward step instead of ~0.5)
@@ -59,49 +59,8 @@ constexpr int kPdasSingleM = 50;
 constexpr int kLazyPrefixMin = IRS_LAZY_MIN;   // shortest fully pinned head that is left out of the inner sweeps
 constexpr int KIND_ABS_M = 0, KIND_REL_M = 1;
 
-// 1/d: hardware estimate + two Newton steps (~1 ulp).  (The policy-evaluation form would forgive a cruder
-// gain in the cost-to-go, but the gain IS the control that is applied.)
-__device__ __forceinline__ double fast_rcp_m(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    return r;
-}
-__device__ __forceinline__ double readlane_d(double v, int src) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), src);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
-    return __hiloint2double(hi, lo);
-}
-// lane N of every 16-lane row to all lanes of that row (DPP row_newbcast; checked on gfx950: tools/microbench)
-template <int N>
-__device__ __forceinline__ double row_newbcast_d(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    // (bound_ctrl set: every lane has a valid source, and with it the compiler need not initialise the destination --
-    // it emitted a v_mov of zero per word and broadcast otherwise, 22 per backward step)
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x150 + N, 0xf, 0xf, true);
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x150 + N, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double wmax_d(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fmax(v, __shfl_xor(v, s, 64));
-    return v;
-}
-__device__ __forceinline__ double wmin_d(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fmin(v, __shfl_xor(v, s, 64));
-    return v;
-}
-__device__ __forceinline__ int wmax_i(int v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = max(v, __shfl_xor(v, s, 64));
-    return v;
-}
-__device__ __forceinline__ int wmin_i(int v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = min(v, __shfl_xor(v, s, 64));
-    return v;
-}
+// (fast_rcp, wave.hpp: the policy-evaluation form would forgive a cruder gain in the cost-to-go, but the gain IS the
+// control that is applied.)
 
 template <int NR, int M>
 struct MfLayout {
@@ -292,17 +251,10 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
     if (lane == 0) {
         a.info[0] = -1; a.info[1] = -1; a.info[2] = -1;     // sentinels: see ctrlbox.hip
     }
-    for (int q = lane; q < NR * NR; q += 64) {
-        const int i = q / NR, j = q % NR;
-        Qsym[q] = 0.5 * (a.Q[i * NR + j] + a.Q[j * NR + i]);
-        Qdsym[q] = 0.5 * (a.Qd[i * NR + j] + a.Qd[j * NR + i]);
-    }
-    for (int q = lane; q < M * M; q += 64) {
-        const int i = q / M, j = q % M;
-        Rsym[q] = 0.5 * (a.R[i * M + j] + a.R[j * M + i]);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
+    sym_part(Qsym, a.Q, NR, 0.5, lane);
+    sym_part(Qdsym, a.Qd, NR, 0.5, lane);
+    sym_part(Rsym, a.R, M, 0.5, lane);
+    wave_sync();
     const double* blo = KIND == KIND_ABS_M ? a.ulo : a.dlo;
     const double* bhi = KIND == KIND_ABS_M ? a.uhi : a.dhi;
     const int bs = KIND == KIND_ABS_M ? a.su : a.sd;
@@ -602,10 +554,10 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                 const v4d Gc = __builtin_amdgcn_mfma_f64_16x16x4f64(rg == (col >> 2) ? 1.0 : 0.0, Th[RN], zero4, 0, 0, 0);
                 auto bc = [&](double v, int j) {
                     switch (j) {
-                        case 0: return row_newbcast_d<NHP + 0>(v);
-                        case 1: return row_newbcast_d<(NHP + 1) & 15>(v);
-                        case 2: return row_newbcast_d<(NHP + 2) & 15>(v);
-                        default: return row_newbcast_d<(NHP + 3) & 15>(v);
+                        case 0: return row_bcast_f64<NHP + 0>(v);
+                        case 1: return row_bcast_f64<(NHP + 1) & 15>(v);
+                        case 2: return row_bcast_f64<(NHP + 2) & 15>(v);
+                        default: return row_bcast_f64<(NHP + 3) & 15>(v);
                     }
                 };
 #pragma unroll
@@ -667,12 +619,12 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                     // [p q; q r]^-1 = [r -q; -q p] / (p r - q^2)
                     const double det = fma(p, r, -q * q);
                     spd = spd && p > 0.0 && det > 0.0;
-                    const double id = fast_rcp_m(det);
+                    const double id = fast_rcp(det);
                     ip = r * id; iq = -q * id; ir = p * id;
                 };
                 if constexpr (M == 1) {
                     spd = Hm[0][0] > 0.0;
-                    Hi[0][0] = fast_rcp_m(Hm[0][0]);
+                    Hi[0][0] = fast_rcp(Hm[0][0]);
                 } else if constexpr (M == 2) {
                     inv2(Hm[0][0], Hm[0][1], Hm[1][1], Hi[0][0], Hi[0][1], Hi[1][1]);
                     Hi[1][0] = Hi[0][1];
@@ -966,7 +918,7 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
             double dlt[M];
 #pragma unroll
             for (int j = 0; j < M; ++j) {
-                const double v = readlane_d(Dn[RN], 16 * j);
+                const double v = readlane_f64(Dn[RN], 16 * j);
                 const double lo = lo_[(size_t)t * M + j], hi = hi_[(size_t)t * M + j];
                 const double c = fmin(fmax(v, lo), hi);
                 dlt[j] = c - v;
@@ -1104,9 +1056,9 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                 if (cb != 0ull) chg = max(chg, (qb + 63 - __builtin_clzll(cb)) / M);
             }
             if (single) {
-                const double wm = wmax_d(rworst);
+                const double wm = wave_max(rworst);
                 if (wm > 0.0) {
-                    const int qw = wmin_i(rworst == wm ? rq : 0x7fffffff);      // first index among equals
+                    const int qw = wave_min(rworst == wm ? rq : 0x7fffffff);      // first index among equals
                     if (lane == 0) { act_[qw] = 0.0; sig_[qw / M] = -1.0; }
                     chg = max(chg, qw / M);
                 }
@@ -1155,7 +1107,7 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                 const double nw = u <= lo ? -1.0 : (u >= hi ? 1.0 : 0.0);
                 if (nw != act_[q]) { act_[q] = nw; bnd_[q] = nw < 0.0 ? lo : hi; sig_[q / M] = -1.0; chg = max(chg, q / M); }
             }
-            chg = wmax_i(chg);
+            chg = wave_max(chg);
             rsync();
             t_dirty = max(t_dirty, chg);
             for (int it2 = 0; it2 < a.max_iter && !conv; ++it2) {
@@ -1175,9 +1127,9 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                         if (room < best) { best = room; bq = q; }
                     }
                 }
-                const double alpha = wmin_d(best);
+                const double alpha = wave_min(best);
                 if (alpha < 1.0) {
-                    const int qb = wmin_i(best == alpha ? bq : 0x7fffffff);
+                    const int qb = wave_min(best == alpha ? bq : 0x7fffffff);
                     for (int q = t0 * M + lane; q < T * M; q += 64) {
                         const double u = uu_[q], d = us_[q] - u;
                         if (q == qb) {
@@ -1202,12 +1154,12 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                     const double viol = ac < 0.0 ? -mu : (ac > 0.0 ? mu : 0.0);
                     if (viol > worst) { worst = viol; wq = q; }
                 }
-                const double wmax = wmax_d(worst);
+                const double wmax = wave_max(worst);
                 if (wmax <= tol) {
                     rsync();
                     conv = true;
                 } else {
-                    const int qw = wmin_i(worst == wmax ? wq : 0x7fffffff);
+                    const int qw = wave_min(worst == wmax ? wq : 0x7fffffff);
                     if (lane == 0) { act_[qw] = 0.0; sig_[qw / M] = -1.0; }
                     rsync();
                     t_dirty = qw / M;

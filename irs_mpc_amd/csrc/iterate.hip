@@ -9,6 +9,7 @@
 // irs_mpc_amd/irs_lqr.py routes IrsLqr*.iterate here whenever the sampling object can be drawn on the device
 // (GaussianSmoothing) or the linearisation is exact.
 #include "boxqp.hpp"
+#include "wave.hpp"
 
 namespace {
 
@@ -80,20 +81,11 @@ __global__ void plan_check_kernel(int n, int m, int T, const double* __restrict_
     }
 }
 
-// lane N of every 16-lane row to all lanes of that row (DPP row_newbcast, as in ctrlbox_mfma.hip)
-template <int N>
-__device__ __forceinline__ double pc_row_bcast(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x150 + N, 0xf, 0xf, true);     // bound_ctrl: no destination initialisation
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x150 + N, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-
 // one unrolled step of the walk: x_l to its 16-lane group by DPP, two partial sums per output (half the FMA chain)
 template <int NN, int l = 0>
 struct PcWalk {
     static __device__ __forceinline__ void run(const double* a_r, const double* k_r, double x, double* ax, double* au) {
-        const double xl = pc_row_bcast<l>(x);
+        const double xl = row_bcast_f64<l>(x);
         ax[l & 1] = fma(a_r[l], xl, ax[l & 1]);
         au[l & 1] = fma(k_r[l], xl, au[l & 1]);
         if constexpr (l + 1 < NN) PcWalk<NN, l + 1>::run(a_r, k_r, x, ax, au);

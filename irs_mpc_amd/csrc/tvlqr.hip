@@ -8,19 +8,12 @@
 // elements of every small product; the next step's A,B,c (backward) or K,k (forward)
 // are prefetched into registers while the current step computes.
 #include "irs_common.hpp"
+#include "wave.hpp"
 
 namespace {
 
 constexpr int kMaxN = 32;
 constexpr int kMaxM = 16;
-
-// Orders ONE wave's LDS traffic: the LDS executes a wave's operations in issue order,
-// so this only has to stop the compiler from moving them; it deliberately does not
-// wait for outstanding global loads (the prefetches stay in flight).
-__device__ __forceinline__ void wave_sync() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-}
 
 struct RiccatiArgs {
     const double* At; const double* Bt; const double* ct;
@@ -43,15 +36,6 @@ struct RiccatiLds {
     unsigned char ti[N * (N + 1) / 2], tj[N * (N + 1) / 2];
 };
 
-// 1/d to ~1 ulp: hardware reciprocal + two Newton steps (a correctly rounded f64 divide
-// is ~40 dependent instructions on the critical path of every Riccati step).
-__device__ __forceinline__ double fast_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma(fma(-d, r, 1.0), r, r);
-    r = fma(fma(-d, r, 1.0), r, r);
-    return r;
-}
-
 // Backward pass.  On return K (T,M,N) / k (T,M) are in global memory.
 template <int N, int M>
 __device__ __forceinline__ void riccati_backward(const RiccatiArgs& a, int lane, RiccatiLds<N, M>& S) {
@@ -60,15 +44,9 @@ __device__ __forceinline__ void riccati_backward(const RiccatiArgs& a, int lane,
     const int T = a.T;
 
     // only the symmetric parts of Q, Qd, R enter a quadratic form
-    for (int q = lane; q < NN; q += 64) {
-        int i = q / N, j = q % N;
-        S.P[q] = 0.5 * (a.Qd[q] + a.Qd[j * N + i]);
-        S.Q[q] = 0.5 * (a.Q[q] + a.Q[j * N + i]);
-    }
-    for (int q = lane; q < M * M; q += 64) {
-        int i = q / M, j = q % M;
-        S.R[q] = 0.5 * a.alpha * (a.R[q] + a.R[j * M + i]);
-    }
+    sym_part(S.P, a.Qd, N, 0.5, lane);
+    sym_part(S.Q, a.Q, N, 0.5, lane);
+    sym_part(S.R, a.R, M, 0.5 * a.alpha, lane);
     // (i,j), i <= j, of the q-th upper-triangular element
     for (int q = lane; q < NN; q += 64) {
         int i = q / N, j = q % N;
@@ -450,14 +428,7 @@ __device__ __forceinline__ void riccati_backward_reg(const RiccatiArgs& a, int l
 // (col = lane&15, row = (lane>>4) + 4*reg) IS its B-operand layout (k = (lane>>4) + 4*step),
 // and the A-operand layout of the TRANSPOSE -- so P~ (symmetric), A~' and B~' need no
 // data movement at all.  No LDS traffic, no waits inside a step except the 4x4 solve.
-typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr int kQxMax = 4096;          // doubles of LDS for Q xd_t, t = 0..T
-
-__device__ __forceinline__ double readlane_f64(double v, int src_lane) {
-    int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);
-    int hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-    return __hiloint2double(hi, lo);
-}
 
 // -DIRS_RIC_STAMPS (tuning builds only): s_memtime totals per phase of the matrix-core recursion
 #ifdef IRS_RIC_STAMPS
@@ -721,15 +692,9 @@ __global__ __launch_bounds__(64) void riccati_kernel(RiccatiArgs a) {
     const int ldh = m + 1;
 
     // the symmetric parts, as in the compile-time paths
-    for (int q = lane; q < n * n; q += 64) {
-        const int i = q / n, j = q % n;
-        P[q] = 0.5 * (a.Qd[q] + a.Qd[j * n + i]);
-        Qs[q] = 0.5 * (a.Q[q] + a.Q[j * n + i]);
-    }
-    for (int q = lane; q < m * m; q += 64) {
-        const int i = q / m, j = q % m;
-        Rs[q] = 0.5 * (a.R[q] + a.R[j * m + i]);
-    }
+    sym_part(P, a.Qd, n, 0.5, lane);
+    sym_part(Qs, a.Q, n, 0.5, lane);
+    sym_part(Rs, a.R, m, 0.5, lane);
     if (lane == 0) bad = 0;
     wave_sync();
     if (lane < n) {

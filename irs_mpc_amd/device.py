@@ -57,6 +57,12 @@ class DeviceModel:
         self._np = len(self.params)
         self._ws = {}
 
+    def fill_call(self, c):
+        """The model head every call struct of the C ABI starts with: id, parameter count, parameters."""
+        c.model, c.n_params = self.model_id, self._np
+        for i, v in enumerate(self.params):
+            c.params[i] = v
+
     # ---- DynamicalSystem plugin surface -----------------------------------
     def dynamics_batch(self, X, U):
         B = X.shape[0]
@@ -376,9 +382,7 @@ class DeviceModel:
         need = self.lib.irs_cem_iterate_scratch_bytes(T, m, int(B), int(n_elite))
         scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
         c = _lib.CemIterateCall()
-        c.model, c.n_params = self.model_id, self._np
-        for i, v in enumerate(self.params):
-            c.params[i] = v
+        self.fill_call(c)
         c.T, c.B, c.n_elite, c.n_descents, c.quasistatic = T, int(B), int(n_elite), k, int(bool(quasistatic))
         c.seed, c.iter0 = int(seed), int(iter0)
         c.Q, c.Qd, c.R, c.xd_trj, c.x0 = (_ptr(a, F64) for a in (Q, Qd, R, xd_trj, x0))
@@ -482,9 +486,7 @@ class SmoothPlan:
         T = u_trj.shape[0]
         device = u_trj.device
         c = _lib.SmoothCall()
-        c.model, c.n_params = dm.model_id, dm._np
-        for i, v in enumerate(dm.params):
-            c.params[i] = v
+        dm.fill_call(c)
         c.mode, c.T = mode, T
         if rng is not None:
             N = int(rng["N"])
@@ -551,9 +553,7 @@ class DescentPlan:
                         cost=torch.empty((1,), dtype=F64, device=device),
                         info=torch.empty((1,), dtype=torch.int32, device=device))
         c = _lib.DescentCall()
-        c.model, c.n_params = dm.model_id, dm._np
-        for i, v in enumerate(dm.params):
-            c.params[i] = v
+        dm.fill_call(c)
         c.T, c.alpha_R = T, float(alpha_R)
         self._keep = (At, Bt, ct, Q, Qd, R, xd_trj, x0)
         c.At, c.Bt, c.ct = _ptr(At, F64), _ptr(Bt, F64), _ptr(ct, F64)

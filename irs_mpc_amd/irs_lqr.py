@@ -237,9 +237,7 @@ class IrsLqr:
         n, m, T, dm = self.dim_x, self.dim_u, self.T, self._dm
         device = self._Q.device
         c = _lib.IterateCall()
-        c.model, c.n_params = dm.model_id, dm._np
-        for i, v in enumerate(dm.params):
-            c.params[i] = v
+        dm.fill_call(c)
         c.mode, c.T, c.N, c.n_descents = mode, T, int(N), n_desc
         if smp is not None:
             sx = np.stack([smp.stds(self.iter + i)[0] for i in range(n_desc)]).astype(np.float64)

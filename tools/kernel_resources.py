@@ -7,18 +7,24 @@ Compiles the file for gfx950 with the Makefile's flags plus -Rpass-analysis=kern
 prints, per kernel whose demangled name matches the regular expression, VGPRs / AGPRs / scratch bytes per
 lane / waves per SIMD / spilled VGPRs.  The contact kernels sit at the 256-register boundary between one
 and two waves per SIMD: run this after touching csrc/contact_models.hpp."""
+import os
 import re
 import subprocess
 import sys
 
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=fast"
-SMOOTH_EXTRA = "-ffinite-math-only -fno-signed-zeros"       # csrc/Makefile: smooth.o only
+SMOOTH_EXTRA = "-ffinite-math-only -fno-signed-zeros"       # csrc/Makefile: smooth.o, smooth_ug.o
+EXTRA = {                                                    # the per-unit flags of csrc/Makefile
+    "smooth.hip": SMOOTH_EXTRA,
+    "smooth_ug.hip": SMOOTH_EXTRA + " -fno-slp-vectorize",
+    "ctrlbox_mfma.hip": "-mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -fno-signed-zeros",
+}
 
 
 def main():
     src = sys.argv[1]
     filt = sys.argv[2] if len(sys.argv) > 2 else "."
-    extra = SMOOTH_EXTRA if src.endswith("smooth.hip") else (SMOOTH_EXTRA + " -fno-slp-vectorize" if src.endswith("smooth_ug.hip") else "")
+    extra = EXTRA.get(os.path.basename(src), "")
     cmd = "/opt/rocm/bin/hipcc %s %s -Rpass-analysis=kernel-resource-usage -c %s -o /tmp/kernel_resources.o" % (
         FLAGS, extra, src)
     out = subprocess.run(cmd, shell=True, capture_output=True, text=True).stderr
