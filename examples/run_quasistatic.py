@@ -9,6 +9,7 @@
     python examples/run_quasistatic.py box_pivoting cem --device-rng
     python examples/run_quasistatic.py box_pushing irs_lqr       # examples/box_pushing/run_box_pushing.py
     python examples/run_quasistatic.py planar_hand_spin irs_lqr  # examples/planar_hand/run_planar_hand_spin.py
+    python examples/run_quasistatic.py planar_hand irs_lqr --batch 8   # 8 initial guesses side by side (IrsLqrQuasistaticBatch)
 
 planar_hand: problem data as in run_planar_hand.py:20-153 (h = 0.1, initial grasp, goal
 q_u0 + (0.3, -0.1, 0.5), Q/Qd/R dicts, u_bounds_abs = +-0.5 h, std_u_initial = 0.3 / iter^0.8).
@@ -90,6 +91,28 @@ def problem(T, h=0.1):
     return q_dynamics, x0, u_traj_0, Q_dict, Qd_dict, R_dict, np.tile(xd, (T + 1, 1))
 
 
+def run_batch(q_dynamics, params, a):
+    """--batch B: B copies of the script's problem that differ in the initial guess (u_trj_0 + a fixed perturbation
+    drawn with seed + b; problem 0 keeps the script's) and in the seed of their sample draws."""
+    import copy
+    plist = []
+    for b in range(a.batch):
+        p = copy.copy(params)
+        if b > 0:
+            p.u_trj_0 = params.u_trj_0 + 0.01 * np.random.default_rng(a.seed + b).normal(size=params.u_trj_0.shape)
+        p.device_rng_seed = a.seed + b
+        plist.append(p)
+    solver = amd.IrsLqrQuasistaticBatch(q_dynamics, plist)
+    t0 = time.time()
+    solver.iterate(a.iters)
+    for b in range(a.batch):
+        print("problem %d final cost: %.6f  best: %.6f  %s" % (b, solver.cost[b], solver.cost_best[b],
+                                                              solver.status[b] or "ok"))
+    print("Elapsed time: " + str(time.time() - t0))
+    if a.csv:
+        np.savetxt(a.csv, np.array(solver.cost_all_list).T, delimiter=",")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("system", choices=["planar_hand", "planar_hand_spin", "box_pivoting", "box_pushing"])
@@ -103,6 +126,9 @@ def main():
                     help="default: the reference's set-up files (planar_hand_setup.py:28 first_order; "
                          "box_pivoting_setup.py / box_pushing_setup.py:25 zero_order_B)")
     ap.add_argument("--device-rng", action="store_true")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="irs_lqr: B problems in one IrsLqrQuasistaticBatch -- problem b starts from the script's u_trj_0 "
+                         "plus a fixed, seeded perturbation and draws with seed + b (device RNG)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--csv", default=None)
     ap.add_argument("--quiet", action="store_true")
@@ -145,6 +171,8 @@ def main():
         params.publish_every_iteration = False
         if a.device_rng:
             params.device_rng_seed = a.seed
+        if a.batch > 0:
+            return run_batch(q_dynamics, params, a)
         solver = amd.IrsLqrQuasistatic(q_dynamics=q_dynamics, params=params)
     else:
         params = amd.CemQuasistaticParameters()

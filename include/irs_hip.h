@@ -430,6 +430,40 @@ int irs_quasistatic_box_descent_wsx(int model, const double *params, int n_param
                                     double *act_io, void *workspace, size_t workspace_bytes, void *stream);
 size_t irs_quasistatic_descent_workspace_bytes(int model, int T, int solver);
 
+/* B independent quasistatic descents in ONE launch: solver 3's method (the active-set solver on matrix-core tiles),
+ * one workgroup per problem -- the same program as irs_quasistatic_box_descent_wsx(solver = 3) with a problem index,
+ * so problem b's outputs are, bit for bit, those of the single call on problem b's inputs.  What users of a
+ * contact-rich optimiser run anyway (several initial guesses, start states or goals) then fills the device's compute
+ * units side by side instead of queueing on one.
+ * Per problem, B contiguous blocks, all DEV f64: At (B,T,n,n), Bt (B,T,n,m), ct (B,T,n), xd_trj (B,T+1,n), x0 (B,n),
+ * the bound rows (B,T,m) -- EXACTLY ONE of the pairs u_lo,u_hi (absolute) / du_lo,du_hi (on u_t - u_{t-1}), the other
+ * NULL; +-inf entries allowed -- and the outputs x_new (B,T+1,n), u_new (B,T,m), cost (B) (may be NULL), info (B,3)
+ * int, act_io (B,T,m) (may be NULL; in/out as for irs_quasistatic_box_descent_ws).  Shared by all problems: the
+ * model and its params, T, Q, Qd, R, the kind of bound, max_iter, eps.  State bounds are not served.
+ * Records: in LDS where they fit (irs_quasistatic_descent_batch_workspace_bytes == 0: pass NULL); otherwise in
+ * `workspace` (DEV, 256-byte aligned, uninitialised scratch), where problem b owns the bytes from b * round256(
+ * irs_quasistatic_descent_workspace_bytes(model, T, 3)).  A non-NULL workspace puts the records there at ANY horizon
+ * (as irs_tvlqr_box_descent_wsx does; same results, bit for bit).
+ * IRS_ERR_UNSUPPORTED: the model does not fit the tile; IRS_ERR_INVALID_ARG: B <= 0, both bound pairs or neither;
+ * IRS_ERR_WORKSPACE: no or too small a workspace.                                                            */
+size_t irs_quasistatic_descent_batch_workspace_bytes(int model, int T, int B);   /* no GPU is touched */
+int irs_quasistatic_box_descent_batch(int model, const double *params, int n_params, int T, int B,
+                                      const double *At, const double *Bt, const double *ct,
+                                      const double *Q, const double *Qd, const double *R,
+                                      const double *xd_trj, const double *x0,
+                                      const double *u_lo, const double *u_hi,
+                                      const double *du_lo, const double *du_hi,
+                                      int max_iter, double eps,
+                                      double *x_new, double *u_new, double *cost, int *info,
+                                      double *act_io, void *workspace, size_t workspace_bytes, void *stream);
+/* The trust-region rows of B problems in one launch (irs_lqr_quasistatic.py:303-325): lo, hi (B,T,m) DEV f64 out,
+ * entry (b,t,j) = x_trj[b,t,indices_u_into_x[j]] + offset (rel = 0: rows for u_lo,u_hi; x_trj (B,T+1,n) DEV f64,
+ * indices_u_into_x (m) DEV int32) or the offset alone (rel = 1: rows for du_lo,du_hi; x_trj and the indices are
+ * not read).  offsets DEV f64: (B,2,m) -- lower then upper -- or (B,2,T,m) if per_time.  One f64 add per entry.   */
+int irs_quasistatic_bound_rows_batch(int n, int m, int T, int B, const double *x_trj, const int *indices_u_into_x,
+                                     const double *offsets, int per_time, int rel, double *lo, double *hi,
+                                     void *stream);
+
 /* ---- Cross-entropy-method baseline (irs_lqr/cem.py:151-184) -------------------- */
 
 /* Steps 1-2 of CrossEntropyMethod.local_descent (cem.py:163-168): roll out each of the

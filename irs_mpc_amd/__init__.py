@@ -8,6 +8,7 @@ from .irs_lqr import (IrsLqr, IrsLqrExact, IrsLqrFirstOrder,        # noqa: F401
                       IrsLqrParameters, IrsLqrZeroOrder)
 from .irs_lqr_quasistatic import (IrsLqrQuasistatic,               # noqa: F401
                                    IrsLqrQuasistaticParameters)
+from .irs_lqr_quasistatic_batch import IrsLqrQuasistaticBatch       # noqa: F401
 from .sampling import GaussianSmoothing                             # noqa: F401
 from .systems import (BicycleDynamics, BoxOnBoxDynamics,             # noqa: F401
                       BoxPivotingDynamics, BoxPushingDynamics,

@@ -6,4 +6,5 @@ from .systems import *            # noqa: F401,F403
 from .sampling import *           # noqa: F401,F403
 from .cem import *                # noqa: F401,F403
 from .irs_lqr_quasistatic import *   # noqa: F401,F403
+from .irs_lqr_quasistatic_batch import IrsLqrQuasistaticBatch   # noqa: F401
 from .cem_quasistatic import *       # noqa: F401,F403

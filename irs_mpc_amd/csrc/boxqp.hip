@@ -520,6 +520,22 @@ int launch_box(const BoxArgs& a, const BoxPlan& p, double* ws, hipStream_t st) {
     return launch_box_kernel<Model, DU, true>(a, ws, p.lds, st);
 }
 
+// Trust-region rows of B problems in one launch (IrsLqrQuasistatic._bounds_dev, irs_lqr_quasistatic.py:303-325): entry
+// (b, t, j) of lo / hi (B,T,m) is x_trj[b, t, idx[j]] + offset -- or, rel, the offset alone (bounds on u_t - u_{t-1}) --
+// with offsets (B,2,m), or (B,2,T,m) if per_time.  One f64 add per entry: the bits of the host expression.
+__global__ __launch_bounds__(256) void bound_rows_batch_kernel(int n, int m, int T, long long total, const double* x_trj,
+                                                               const int* idx, const double* off, bool per_time, bool rel,
+                                                               double* lo, double* hi) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (q >= total) return;
+    const int j = (int)(q % m), t = (int)(q / m % T);
+    const long long b = q / m / T;
+    const long long side = per_time ? (long long)T * m : m, o = b * 2 * side + (per_time ? (long long)t * m : 0) + j;
+    const double c = rel ? 0.0 : x_trj[(b * (T + 1) + t) * n + idx[j]];
+    lo[q] = c + off[o];
+    hi[q] = c + off[o + side];
+}
+
 // The ADMM kernel: its records on chip when they fit LDS and no workspace is forced on them; otherwise in HBM,
 // where only the ADMM vectors stay in LDS (hbm_doubles grows by 3 N + 4 M per step: that caps the horizon).
 template <int N, int M>
@@ -558,7 +574,8 @@ BoxPlan irs_box_plan(int model, int T, int kind, BoxWs ws) {
     } else if (kind == IRS_BOX_ACTIVE_SET_MFMA) {
         // the records on chip while they fit, else in the workspace: no horizon cap
         const size_t lds = irs_ctrlbox_mfma_lds_bytes(model, T), rec = irs_ctrlbox_mfma_record_bytes(model, T);
-        if (lds > 0 && lds <= IRS_LDS_BUDGET) p = {BoxPlace::TilesLds, lds, 0, INT_MAX};
+        if (lds > 0 && ws == BoxWs::Always) p = {BoxPlace::TilesHbm, lds - rec, rec, INT_MAX};
+        else if (lds > 0 && lds <= IRS_LDS_BUDGET) p = {BoxPlace::TilesLds, lds, 0, INT_MAX};
         else if (lds > 0 && ws != BoxWs::None) p = {BoxPlace::TilesHbm, lds - rec, rec, INT_MAX};
         else if (lds > 0) p = {BoxPlace::None, lds, rec, INT_MAX};
     }
@@ -827,6 +844,71 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
     rc = solver == 3 ? irs_ctrlbox_mfma_launch(model, a, kind, p, static_cast<double*>(workspace), st)
                      : irs_ctrlbox_launch(model, a, kind, p, st);
     if (rc != IRS_OK) return rc;
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+// ---- B problems per launch (solver 3's method) ---------------------------------------------------------------------
+static size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+size_t irs_quasistatic_descent_batch_workspace_bytes(int model, int T, int B) {
+    if (T <= 0 || B <= 0) return 0;
+    return (size_t)B * round256(irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, BoxWs::IfNeeded).records);
+}
+
+int irs_quasistatic_box_descent_batch(int model, const double* params, int n_params, int T, int B, const double* At,
+                                      const double* Bt, const double* ct, const double* Q, const double* Qd,
+                                      const double* R, const double* xd_trj, const double* x0, const double* u_lo,
+                                      const double* u_hi, const double* du_lo, const double* du_hi, int max_iter,
+                                      double eps, double* x_new, double* u_new, double* cost, int* info, double* act_io,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(T > 0 && B > 0, "T and B must be positive");
+    IRS_CHECK_ARG(At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_new && u_new && info, "bad argument");
+    IRS_CHECK_ARG((u_lo == nullptr) == (u_hi == nullptr) && (du_lo == nullptr) == (du_hi == nullptr),
+                  "give both sides of a bound or neither");
+    IRS_CHECK_ARG((u_lo != nullptr) != (du_lo != nullptr), "give exactly one of the u / du bound pairs");
+    IRS_CHECK_ARG(max_iter > 0 && eps > 0.0, "bad solver parameter");
+    BoxArgs a;
+    int rc = box_args(&a, model, params, n_params, T, At, Bt, ct, Q, Qd, R, 1.0, xd_trj, x0, nullptr, nullptr, u_lo,
+                      u_hi, du_lo, du_hi, true, 10.0, 1.6, max_iter, eps, x_new, u_new, cost, info);
+    if (rc != IRS_OK) return rc;
+    a.act_io = act_io;
+    // a workspace puts the records there at any horizon (as irs_tvlqr_box_descent_wsx does); without one they must
+    // fit LDS
+    const BoxPlan p = irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, workspace != nullptr ? BoxWs::Always : BoxWs::None);
+    if (p.max_T == 0) {
+        irs_set_error(irs_box_plan(model, T, IRS_BOX_ADMM_DU, BoxWs::None).max_T > 0
+                          ? "irs_quasistatic_box_descent_batch: model %d does not fit the 16 x 16 tile"
+                          : "irs_quasistatic_box_descent_batch: model %d is not position controlled", model);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    const size_t stride = round256(p.records);
+    if (p.place == BoxPlace::None || workspace_bytes < (size_t)B * stride) {
+        irs_set_error("irs_quasistatic_box_descent_batch: horizon T=%d, B=%d needs a workspace of %zu bytes (given: %zu)",
+                      T, B, (size_t)B * round256(p.records), workspace_bytes);
+        return IRS_ERR_WORKSPACE;
+    }
+    if (p.place == BoxPlace::TilesHbm && (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
+        irs_set_error("irs_quasistatic_box_descent_batch: the workspace must be 256-byte aligned");
+        return IRS_ERR_INVALID_ARG;
+    }
+    rc = irs_ctrlbox_mfma_launch_batch(model, a, du_lo != nullptr ? 1 : 0, p, static_cast<double*>(workspace), stride, B,
+                                       static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) return rc;
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+int irs_quasistatic_bound_rows_batch(int n, int m, int T, int B, const double* x_trj, const int* indices_u_into_x,
+                                     const double* offsets, int per_time, int rel, double* lo, double* hi,
+                                     void* stream) {
+    IRS_CHECK_ARG(n > 0 && m > 0 && T > 0 && B > 0, "n, m, T and B must be positive");
+    IRS_CHECK_ARG(offsets && lo && hi && (rel || (x_trj && indices_u_into_x)), "bad argument");
+    const long long total = (long long)B * T * m;
+    IRS_CHECK_ARG(total <= 0x7fffffffLL * 256, "too many rows for one launch");
+    hipLaunchKernelGGL(bound_rows_batch_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), n, m, T, total, x_trj, indices_u_into_x, offsets, per_time != 0,
+                       rel != 0, lo, hi);
     IRS_CHECK_LAUNCH();
     return IRS_OK;
 }

@@ -63,3 +63,8 @@ size_t irs_ctrlbox_lds_bytes(int model, int T);
 size_t irs_ctrlbox_mfma_record_bytes(int model, int T);
 size_t irs_ctrlbox_mfma_lds_bytes(int model, int T);
 int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, hipStream_t st);
+// B problems in one launch, one workgroup each: every per-problem array of `a` is B contiguous blocks (problem b's at
+// b times the block's size), Q / Qd / R and the scalars are shared; TilesHbm: problem b's records at ws + b * ws_stride
+// bytes.
+int irs_ctrlbox_mfma_launch_batch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, size_t ws_stride,
+                                  int B, hipStream_t st);

@@ -59,6 +59,14 @@ constexpr int kPdasSingleM = 50;
 constexpr int kLazyPrefixMin = IRS_LAZY_MIN;   // shortest fully pinned head that is left out of the inner sweeps
 constexpr int KIND_ABS_M = 0, KIND_REL_M = 1;
 
+// Batched launch: how far problem b's data lie from problem 0's -- element strides of the per-problem arrays of
+// BoxArgs (bnd: the bound rows of the launch's kind), a byte stride of the record workspace.  A single-problem
+// launch carries the empty BoxSolo instead.
+struct BoxBatch {
+    long long At, Bt, ct, xd, x0, bnd, x_new, u_new, cost, info, act, ws_bytes;
+};
+struct BoxSolo {};
+
 // (fast_rcp, wave.hpp: the policy-evaluation form would forgive a cruder gain in the cost-to-go, but the gain IS the
 // control that is applied.)
 
@@ -92,8 +100,28 @@ struct MfLayout {
 // across the call to the contact step, whose callee (compiled with inter-procedural register allocation,
 // 256 VGPRs + 222 AGPRs, no callee-saved registers) left the caller ~40 registers and a scratch frame to
 // park ~150 values in.
-template <class Model, int KIND, bool LDSREC>
-__global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gws, long long* stamps) {
+//
+// BATCH: B independent problems, one workgroup each (launch dim3(B)).  Everything a problem owns is private to its
+// workgroup already -- LDS, or its slice of the record workspace -- so the only difference is at the ENTRY: the
+// per-problem pointers of `a` and `gws` advance by blockIdx.x strides (scalar adds on kernel arguments); the body
+// below them is the single-problem program, instruction for instruction.  Shared by the problems of a launch: the
+// model and its constants, T, Q / Qd / R, the kind of bound, eps, max_iter.
+template <class Model, int KIND, bool LDSREC, bool BATCH>
+__global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gws, long long* stamps,
+                                                           std::conditional_t<BATCH, BoxBatch, BoxSolo> bat) {
+    if constexpr (BATCH) {
+        const long long b = blockIdx.x;
+        a.At += b * bat.At; a.Bt += b * bat.Bt; a.ct += b * bat.ct; a.xd += b * bat.xd; a.x0 += b * bat.x0;
+        if constexpr (KIND == 0) { a.ulo += b * bat.bnd; a.uhi += b * bat.bnd; }
+        else { a.dlo += b * bat.bnd; a.dhi += b * bat.bnd; }
+        a.x_new += b * bat.x_new; a.u_new += b * bat.u_new; a.info += b * bat.info;
+        if (a.cost) a.cost += b * bat.cost;
+        if (a.act_io) a.act_io += b * bat.act;
+        if constexpr (!LDSREC) gws = reinterpret_cast<double*>(reinterpret_cast<char*>(gws) + b * bat.ws_bytes);
+#ifdef IRS_CBM_STAMPS
+        if (b != 0) stamps = nullptr;                       // the diagnostic build stamps problem 0 only
+#endif
+    }
     constexpr int NR = Model::NX, M = Model::NU;
     using L = MfLayout<NR, M>;
     constexpr int NS = L::NS, NH = L::NH, NHP = L::NHP, KA = L::KA, RN = L::KA;   // RN: register of rows NHP..NHP+3
@@ -1210,13 +1238,32 @@ static long long* cbm_stamps() { return nullptr; }
 template <class Model, int KIND>
 int launch_ctrlbox_mfma(const BoxArgs& a, const BoxPlan& p, double* ws, hipStream_t st) {
     if (p.place == BoxPlace::TilesLds) {
-        constexpr auto kern = ctrlbox_mfma_kernel<Model, KIND, true>;
+        constexpr auto kern = ctrlbox_mfma_kernel<Model, KIND, true, false>;
         const int rc = irs_raise_lds_limit<kern>(p.lds, "irs_quasistatic_box_descent");
         if (rc != IRS_OK) return rc;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(128), p.lds, st, a, (double*)nullptr, cbm_stamps());
+        hipLaunchKernelGGL(kern, dim3(1), dim3(128), p.lds, st, a, (double*)nullptr, cbm_stamps(), BoxSolo{});
     } else {
-        auto kern = ctrlbox_mfma_kernel<Model, KIND, false>;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(128), p.lds, st, a, ws, cbm_stamps());
+        auto kern = ctrlbox_mfma_kernel<Model, KIND, false, false>;
+        hipLaunchKernelGGL(kern, dim3(1), dim3(128), p.lds, st, a, ws, cbm_stamps(), BoxSolo{});
+    }
+    return IRS_OK;
+}
+
+// B problems, one workgroup each; records in HBM: problem b's at ws + b * ws_stride bytes
+template <class Model, int KIND>
+int launch_ctrlbox_mfma_batch(const BoxArgs& a, const BoxPlan& p, double* ws, size_t ws_stride, int B, hipStream_t st) {
+    constexpr long long n = Model::NX, m = Model::NU;
+    const long long T = a.T;
+    const BoxBatch bs{T * n * n, T * n * m, T * n, (T + 1) * n, n, T * m, (T + 1) * n, T * m, 1, 3, T * m,
+                      (long long)ws_stride};
+    if (p.place == BoxPlace::TilesLds) {
+        constexpr auto kern = ctrlbox_mfma_kernel<Model, KIND, true, true>;
+        const int rc = irs_raise_lds_limit<kern>(p.lds, "irs_quasistatic_box_descent_batch");
+        if (rc != IRS_OK) return rc;
+        hipLaunchKernelGGL(kern, dim3(B), dim3(128), p.lds, st, a, (double*)nullptr, cbm_stamps(), bs);
+    } else {
+        auto kern = ctrlbox_mfma_kernel<Model, KIND, false, true>;
+        hipLaunchKernelGGL(kern, dim3(B), dim3(128), p.lds, st, a, ws, cbm_stamps(), bs);
     }
     return IRS_OK;
 }
@@ -1254,6 +1301,19 @@ int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan
             if constexpr (MfLayout<Model::NX, Model::NU>::FITS)
                 rc = kind == KIND_ABS_M ? launch_ctrlbox_mfma<Model, KIND_ABS_M>(a, p, ws, st)
                                         : launch_ctrlbox_mfma<Model, KIND_REL_M>(a, p, ws, st);
+        }
+    });
+    return rc;
+}
+
+int irs_ctrlbox_mfma_launch_batch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, size_t ws_stride,
+                                  int B, hipStream_t st) {
+    int rc = IRS_ERR_UNSUPPORTED;
+    IRS_DISPATCH_MODEL(model, {
+        if constexpr (has_u_into_x<Model>::value) {
+            if constexpr (MfLayout<Model::NX, Model::NU>::FITS)
+                rc = kind == KIND_ABS_M ? launch_ctrlbox_mfma_batch<Model, KIND_ABS_M>(a, p, ws, ws_stride, B, st)
+                                        : launch_ctrlbox_mfma_batch<Model, KIND_REL_M>(a, p, ws, ws_stride, B, st);
         }
     });
     return rc;

@@ -296,6 +296,71 @@ class DeviceModel:
             ws.numel() if ws is not None else 0, _stream()), "irs_quasistatic_box_descent_wsx")
         return o
 
+    # ---- B quasistatic descents per launch ------------------------------------
+    def _descent_batch_workspace(self, T, B, device, force=False):
+        """Cached per (T, B): the records of B problems, where they do not fit LDS (or `force`); else None."""
+        need = self.lib.irs_quasistatic_descent_batch_workspace_bytes(self.model_id, int(T), int(B))
+        if force and need == 0:
+            # records that would fit on chip: their size is affine in T, so two queries beyond the LDS horizon give it
+            f = [self.lib.irs_quasistatic_descent_workspace_bytes(self.model_id, t, 3) for t in (1 << 14, (1 << 14) + 1)]
+            one = f[0] - ((1 << 14) - int(T)) * (f[1] - f[0])
+            need = int(B) * ((one + 255) // 256 * 256)
+        if need == 0:
+            return None
+        key = ("descent_batch", int(T), int(B), device)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty((need,), dtype=torch.uint8, device=device)
+            self._ws[key] = ws
+        return ws
+
+    def quasistatic_box_descent_batch(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, u_lo=None, u_hi=None, du_lo=None,
+                                      du_hi=None, max_iter=5000, eps=1e-8, out=None, act=None, records_in_hbm=False):
+        """B quasistatic descents in one launch (solver 3's method; one workgroup per problem): At (B,T,n,n), Bt
+        (B,T,n,m), ct (B,T,n), xd_trj (B,T+1,n), x0 (B,n), exactly one pair of bound rows (B,T,m); Q, Qd, R shared.
+        `act` (B,T,m) in/out as in quasistatic_box_descent.  records_in_hbm=True puts the per-step records in a
+        workspace at any horizon (same result, bit for bit).  Returns dict(x_new (B,T+1,n), u_new (B,T,m), cost (B),
+        info (B,3)); pass `out` to write into tensors of those shapes (e.g. a slot of a history)."""
+        B, T = At.shape[0], At.shape[1]
+        dev = At.device
+        o = out
+        if o is None:
+            o = dict(x_new=torch.empty((B, T + 1, self.n), dtype=F64, device=dev),
+                     u_new=torch.empty((B, T, self.m), dtype=F64, device=dev),
+                     cost=torch.empty((B,), dtype=F64, device=dev),
+                     info=torch.empty((B, 3), dtype=torch.int32, device=dev))
+        shapes = dict(At=(B, T, self.n, self.n), Bt=(B, T, self.n, self.m), ct=(B, T, self.n),
+                      xd_trj=(B, T + 1, self.n), x0=(B, self.n), x_new=(B, T + 1, self.n), u_new=(B, T, self.m),
+                      cost=(B,), info=(B, 3))
+        given = dict(At=At, Bt=Bt, ct=ct, xd_trj=xd_trj, x0=x0, **o)
+        for name, shape in shapes.items():
+            assert tuple(given[name].shape) == shape, (name, tuple(given[name].shape), shape)
+        for b in (u_lo, u_hi, du_lo, du_hi, act):
+            assert b is None or tuple(b.shape) == (B, T, self.m), (tuple(b.shape), (B, T, self.m))
+        assert o["info"].dtype == torch.int32 and o["info"].is_contiguous()
+        ws = self._descent_batch_workspace(T, B, dev, force=records_in_hbm)
+        check(self.lib.irs_quasistatic_box_descent_batch(
+            self.model_id, self._p, self._np, T, B, _ptr(At, F64), _ptr(Bt, F64), _ptr(ct, F64), _ptr(Q, F64),
+            _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(u_lo, F64), _ptr(u_hi, F64),
+            _ptr(du_lo, F64), _ptr(du_hi, F64), int(max_iter), float(eps), _ptr(o["x_new"], F64), _ptr(o["u_new"], F64),
+            _ptr(o["cost"], F64), o["info"].data_ptr(), _ptr(act, F64), ws.data_ptr() if ws is not None else None,
+            ws.numel() if ws is not None else 0, _stream()), "irs_quasistatic_box_descent_batch")
+        return o
+
+    def quasistatic_bound_rows_batch(self, x_trj, idx, offsets, rel=False, out=None):
+        """Trust-region rows of B problems in one launch: x_trj (B,T+1,n), idx (m) int32 = indices_u_into_x, offsets
+        (B,2,m) or (B,2,T,m) -> lo, hi (B,T,m): x_trj[b,t,idx[j]] + offset, or (rel) the offset alone."""
+        B, T = x_trj.shape[0], x_trj.shape[1] - 1
+        assert tuple(offsets.shape) in ((B, 2, self.m), (B, 2, T, self.m)), tuple(offsets.shape)
+        assert idx.dtype == torch.int32 and idx.is_cuda and idx.is_contiguous() and idx.numel() == self.m
+        lo, hi = out if out is not None else (torch.empty((B, T, self.m), dtype=F64, device=x_trj.device),
+                                              torch.empty((B, T, self.m), dtype=F64, device=x_trj.device))
+        check(self.lib.irs_quasistatic_bound_rows_batch(self.n, self.m, T, B, _ptr(x_trj, F64), idx.data_ptr(),
+                                                        _ptr(offsets, F64), int(offsets.dim() == 4), int(bool(rel)),
+                                                        _ptr(lo, F64), _ptr(hi, F64), _stream()),
+              "irs_quasistatic_bound_rows_batch")
+        return lo, hi
+
     # ---- CEM baseline -------------------------------------------------------
     def cem_rollout_costs(self, u_cand, x0, Q, R, xd_trj):
         """costs (B) of the B candidate sequences u_cand (B,T,m): rollout + evaluate_cost each."""

@@ -79,6 +79,17 @@ class IrsLqrQuasistaticParameters:
         self.qp_eps = 1e-9
 
 
+def decouple_exact_dev(At, Bt, ct, x_trj, u_trj, idx, dim_x, dim_u):
+    """decouple_AB_matrices on the exact pair (in place) and c_t = f - A x - B u rebuilt with it
+    (irs_lqr_quasistatic.py:218-225, 275-284); shared with the batched class, which must compute the same bits."""
+    f = ct + torch.einsum("tij,tj->ti", At, x_trj[:-1]) + torch.einsum("tij,tj->ti", Bt, u_trj)
+    Bt[:, idx, :] = torch.eye(dim_u, dtype=At.dtype, device=At.device)
+    At[:] = torch.eye(dim_x, dtype=At.dtype, device=At.device)
+    At[:, :, idx] = 0.0
+    ct = (f - torch.einsum("tij,tj->ti", At, x_trj[:-1]) - torch.einsum("tij,tj->ti", Bt, u_trj)).contiguous()
+    return At, Bt, ct
+
+
 class IrsLqrQuasistatic(QuasistaticOptimizerBase):
     def __init__(self, q_dynamics, params):
         for name in ("x_bounds_abs", "u_bounds_abs", "x_bounds_rel", "u_bounds_rel", "decouple_AB", "use_workers",
@@ -180,11 +191,7 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
         At, Bt, ct = self._dm.exact_linearize(x_trj, u_trj)
         self._smooth_info = torch.zeros(self.T, dtype=torch.int32, device=x_trj.device)
         if self.decouple_AB:
-            f = ct + torch.einsum("tij,tj->ti", At, x_trj[:-1]) + torch.einsum("tij,tj->ti", Bt, u_trj)
-            Bt[:, self._idx, :] = torch.eye(self.dim_u, dtype=At.dtype, device=At.device)
-            At[:] = torch.eye(self.dim_x, dtype=At.dtype, device=At.device)
-            At[:, :, self._idx] = 0.0
-            ct = (f - torch.einsum("tij,tj->ti", At, x_trj[:-1]) - torch.einsum("tij,tj->ti", Bt, u_trj)).contiguous()
+            At, Bt, ct = decouple_exact_dev(At, Bt, ct, x_trj, u_trj, self._idx, self.dim_x, self.dim_u)
         return At, Bt, ct
 
     def _zero_order_AB_dev(self, x_trj, u_trj, std_u):
