@@ -312,10 +312,15 @@ typedef enum irs_box_kind {
     IRS_BOX_ACTIVE_SET_MFMA = 3
 } irs_box_kind;
 int irs_box_horizon_limit(int model, int kind);
+/* The bytes of per-step records the kernel of `kind` keeps for horizon T when they are placed in a workspace: what
+ * the planner sizes the workspace entries by, at ANY horizon (the *_workspace_bytes queries answer 0 while the records
+ * fit on chip).  0 for T <= 0, an unknown model or kind, a model without that form, and IRS_BOX_ACTIVE_SET (on chip
+ * only: nothing to place).  No GPU.                                                                             */
+size_t irs_box_records_bytes(int model, int T, int kind);
 /* irs_tvlqr_box_descent / irs_tvlqr_box_solve with a workspace: DEV, 256-byte aligned, >= the record bytes of
- * this horizon (BoxLayout stride x T, rounded up to 256; irs_tvlqr_box_workspace_bytes where the records do not
- * fit LDS).  A workspace that is given is used, even where the records would fit on chip; NULL = the entry
- * without it.  IRS_ERR_WORKSPACE if it is too small.                                                           */
+ * this horizon (irs_box_records_bytes: BoxLayout stride x T, rounded up to 256; irs_tvlqr_box_workspace_bytes where
+ * the records do not fit LDS).  A workspace that is given is used, even where the records would fit on chip; NULL =
+ * the entry without it.  IRS_ERR_WORKSPACE if it is too small.                                                 */
 int irs_tvlqr_box_descent_wsx(int model, const double *params, int n_params, int T,
                               const double *At, const double *Bt, const double *ct,
                               const double *Q, const double *Qd, const double *R, double alpha_R,

@@ -155,6 +155,7 @@ SIGNATURES["irs_tvlqr_box_lds_bytes"] = (c_size_t, [c_int, c_int])
 SIGNATURES["irs_tvlqr_box_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int])
 SIGNATURES["irs_tvlqr_box_hbm_lds_bytes"] = (c_size_t, [c_int, c_int, c_int])
 SIGNATURES["irs_box_horizon_limit"] = (c_int, [c_int, c_int])
+SIGNATURES["irs_box_records_bytes"] = (c_size_t, [c_int, c_int, c_int])
 SIGNATURES["irs_tvlqr_box_descent_wsx"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
                                                    c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_double, c_double, c_int,
                                                    c_double, _dp, _dp, _dp, _dp, c_size_t, c_void_p])

@@ -582,12 +582,22 @@ BoxPlan irs_box_plan(int model, int T, int kind, BoxWs ws) {
     return p;
 }
 
-// the ADMM kernel where the plan puts it: records on chip, or in `ws` -- whenever one is given (force_ws), or only
-// where they do not fit LDS
-static int run_admm(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, bool force_ws,
-                    hipStream_t st) {
+static size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// Whether a workspace can hold what plan `p` puts there: `count` slices of round256(p.records) bytes (one per problem
+// of the launch; stride, need: the bytes of one, of all), 256-byte aligned.  The entries word their own errors.
+struct WsFit { size_t stride, need; bool small, misaligned; };
+static WsFit ws_fit(const BoxPlan& p, size_t count, const void* ws, size_t ws_bytes) {
+    const size_t stride = round256(p.records);
+    return {stride, count * stride, ws_bytes < count * stride, (reinterpret_cast<uintptr_t>(ws) & 255) != 0};
+}
+
+// The ADMM kernel on a filled BoxArgs, where the plan puts it: records on chip, or in `ws` -- whenever one is given
+// (policy Always), or only where they do not fit LDS (IfNeeded).  du: the position-controlled form.
+int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, BoxWs policy,
+                        hipStream_t st) {
     const BoxPlan p = irs_box_plan(model, a.T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM,
-                                   ws == nullptr ? BoxWs::None : force_ws ? BoxWs::Always : BoxWs::IfNeeded);
+                                   ws == nullptr ? BoxWs::None : policy);
     if (p.max_T == 0) {
         irs_set_error("%s: model %d is not position controlled", fn, model);
         return IRS_ERR_UNSUPPORTED;
@@ -601,13 +611,16 @@ static int run_admm(const char* fn, int model, bool du, const BoxArgs& a, void* 
                           "its records in HBM (its ADMM vectors need %zu bytes of LDS, max ~160 KB)", a.T, p.max_T, p.lds);
         return IRS_ERR_UNSUPPORTED;
     }
-    if (p.place == BoxPlace::AdmmHbm && ws_bytes < p.records) {
-        irs_set_error("irs_tvlqr_box_descent: workspace %zu < %zu bytes", ws_bytes, p.records);
-        return IRS_ERR_WORKSPACE;
-    }
-    if (p.place == BoxPlace::AdmmHbm && (reinterpret_cast<uintptr_t>(ws) & 255) != 0) {
-        irs_set_error("irs_tvlqr_box_descent: the workspace must be 256-byte aligned");
-        return IRS_ERR_INVALID_ARG;
+    if (p.place == BoxPlace::AdmmHbm) {
+        const WsFit f = ws_fit(p, 1, ws, ws_bytes);
+        if (f.small) {
+            irs_set_error("irs_tvlqr_box_descent: workspace %zu < %zu bytes", ws_bytes, f.need);
+            return IRS_ERR_WORKSPACE;
+        }
+        if (f.misaligned) {
+            irs_set_error("irs_tvlqr_box_descent: the workspace must be 256-byte aligned");
+            return IRS_ERR_INVALID_ARG;
+        }
     }
     double* recs = static_cast<double*>(ws);
     int rc = IRS_ERR_UNSUPPORTED;
@@ -623,43 +636,44 @@ static int run_admm(const char* fn, int model, bool du, const BoxArgs& a, void* 
     return IRS_OK;
 }
 
-// The BoxArgs every entry fills alike.  rows: bounds are per-time rows (strides n / m), else one constant row.  The
-// callers set what is theirs alone: single_tail, act_io, run_flag.
-static int box_args(BoxArgs* a, int model, const double* params, int n_params, int T, const double* At,
-                    const double* Bt, const double* ct, const double* Q, const double* Qd, const double* R, double alpha,
-                    const double* xd, const double* x0, const double* xlo, const double* xhi, const double* ulo,
-                    const double* uhi, const double* dlo, const double* dhi, bool rows, double rho, double relax,
-                    int max_iter, double eps, double* x_new, double* u_new, double* cost, int* info) {
+// What every entry starts its BoxArgs with: all else null / zero, the model's constants, the horizon, and the strides
+// of the bound rows -- per-time rows (n / m), else one constant row (0).  The entry sets the rest by name.
+static int box_begin(BoxArgs* a, int model, const double* params, int n_params, int T, bool rows) {
     *a = BoxArgs{};
     const int rc = irs_load_params(model, params, n_params, &a->p);
     if (rc != IRS_OK) return rc;
     int n = 0, m = 0, np;
     if (rows) irs_model_info(model, &n, &m, &np);
-    a->At = At; a->Bt = Bt; a->ct = ct; a->Q = Q; a->Qd = Qd; a->R = R; a->xd = xd; a->x0 = x0;
-    a->xlo = xlo; a->xhi = xhi; a->ulo = ulo; a->uhi = uhi; a->dlo = dlo; a->dhi = dhi;
-    a->sx = n; a->su = m; a->sd = m;
-    a->x_new = x_new; a->u_new = u_new; a->cost = cost; a->info = info;
-    a->alpha = alpha; a->rho = rho; a->relax = relax; a->eps = eps; a->T = T; a->max_iter = max_iter;
+    a->sx = n; a->su = m; a->sd = m; a->T = T;
     return IRS_OK;
 }
 
-// a workspace the records must go to: 256-byte aligned, large enough
+// a workspace the records must go to (the _wsx entries of the ADMM kernel): 256-byte aligned, large enough
 static int check_box_workspace(const char* fn, int model, int T, int du, const void* ws, size_t ws_bytes) {
     if (ws == nullptr) return IRS_OK;
-    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) {
+    const BoxPlan p = irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::Always);
+    const WsFit f = ws_fit(p, 1, ws, ws_bytes);
+    if (f.misaligned) {
         irs_set_error("%s: the workspace must be 256-byte aligned", fn);
         return IRS_ERR_INVALID_ARG;
     }
-    const BoxPlan p = irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::Always);
     if (p.max_T == 0) {
         irs_set_error("%s: model %d has no %s form", fn, model, du ? "position-controlled" : "plain");
         return IRS_ERR_UNSUPPORTED;
     }
-    if (ws_bytes < p.records) {
-        irs_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, p.records);
+    if (f.small) {
+        irs_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, f.need);
         return IRS_ERR_WORKSPACE;
     }
     return IRS_OK;
+}
+
+// `model` has no active-set form on the tiles: it does not fit them, or it is not position controlled at all
+static int no_tile_form(const char* fn, int model, int T) {
+    irs_set_error(irs_box_plan(model, T, IRS_BOX_ADMM_DU, BoxWs::None).max_T > 0
+                      ? "%s: model %d does not fit the 16 x 16 tile"
+                      : "%s: model %d is not position controlled", fn, model);
+    return IRS_ERR_UNSUPPORTED;
 }
 
 // solver 0 of the quasistatic descent: the tiles where the model fits them and their records have a place, else the
@@ -669,35 +683,6 @@ static int auto_solver(int model, int T, bool one_box, const void* ws, size_t ws
     const BoxPlan tiles = irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, ws ? BoxWs::IfNeeded : BoxWs::None);
     if (tiles.place != BoxPlace::None && ws_bytes >= tiles.records) return 3;
     return irs_box_plan(model, T, IRS_BOX_ACTIVE_SET, BoxWs::None).place == BoxPlace::Lanes ? 2 : 1;
-}
-
-static int box_descent(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                       const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                       const double* xd_trj, const double* x0, const double* xlo, const double* xhi, const double* ulo,
-                       const double* uhi, double rho, double relax, int max_iter, double eps, double* x_new,
-                       double* u_new, double* cost, int* info, const int* run_flag, void* workspace,
-                       size_t workspace_bytes, bool force_ws, void* stream) {
-    BoxArgs a;
-    const int rc = box_args(&a, model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo,
-                            uhi, nullptr, nullptr, false, rho, relax, max_iter, eps, x_new, u_new, cost, info);
-    if (rc != IRS_OK) return rc;
-    a.run_flag = run_flag;
-    return run_admm("irs_tvlqr_box_descent", model, false, a, workspace, workspace_bytes, force_ws,
-                    static_cast<hipStream_t>(stream));
-}
-
-int irs_tvlqr_box_descent_ifw(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                              const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                              const double* xd_trj, const double* x0, const double* xlo, const double* xhi,
-                              const double* ulo, const double* uhi, double rho, double relax, int max_iter, double eps,
-                              double* x_new, double* u_new, double* cost, int* info, const int* run_flag,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
-                  x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
-    return box_descent(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi, rho,
-                       relax, max_iter, eps, x_new, u_new, cost, info, run_flag, workspace, workspace_bytes, false,
-                       stream);
 }
 
 extern "C" {
@@ -717,6 +702,10 @@ size_t irs_tvlqr_box_workspace_bytes(int model, int T, int du) {
 
 size_t irs_tvlqr_box_hbm_lds_bytes(int model, int T, int du) {
     return T > 0 ? irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::Always).lds : 0;
+}
+
+size_t irs_box_records_bytes(int model, int T, int kind) {
+    return T > 0 ? irs_box_plan(model, T, kind, BoxWs::Always).records : 0;
 }
 
 size_t irs_quasistatic_descent_workspace_bytes(int model, int T, int solver) {
@@ -747,9 +736,26 @@ int irs_tvlqr_box_descent_if(int model, const double* params, int n_params, int 
                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
                              double rho, double relax, int max_iter, double eps, double* x_new,
                              double* u_new, double* cost, int* info, const int* run_flag, void* stream) {
-    return irs_tvlqr_box_descent_ifw(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi,
-                                     ulo, uhi, rho, relax, max_iter, eps, x_new, u_new, cost, info, run_flag, nullptr, 0,
-                                     stream);
+    // (both messages keep the name of the internal function that used to make these checks: an entry's error text
+    // does not change)
+    if (!(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi && x_new && u_new &&
+          info)) {
+        irs_set_error("irs_tvlqr_box_descent_ifw: bad argument");
+        return IRS_ERR_INVALID_ARG;
+    }
+    if (!irs_admm_settings_ok(rho, relax, max_iter, eps)) {
+        irs_set_error("irs_tvlqr_box_descent_ifw: bad ADMM parameter");
+        return IRS_ERR_INVALID_ARG;
+    }
+    BoxArgs a;
+    const int rc = box_begin(&a, model, params, n_params, T, false);
+    if (rc != IRS_OK) return rc;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi;
+    a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.max_iter = max_iter; a.eps = eps;
+    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info; a.run_flag = run_flag;
+    return irs_box_admm_launch("irs_tvlqr_box_descent", model, false, a, nullptr, 0, BoxWs::None,
+                               static_cast<hipStream_t>(stream));
 }
 
 int irs_tvlqr_box_descent_wsx(int model, const double* params, int n_params, int T, const double* At,
@@ -760,12 +766,18 @@ int irs_tvlqr_box_descent_wsx(int model, const double* params, int n_params, int
                               double* u_new, int* info, void* workspace, size_t workspace_bytes, void* stream) {
     IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
                   x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+    IRS_CHECK_ARG(irs_admm_settings_ok(rho, relax, max_iter, eps), "bad ADMM parameter");
     int rc = check_box_workspace(__func__, model, T, 0, workspace, workspace_bytes);
     if (rc != IRS_OK) return rc;
-    return box_descent(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo, uhi, rho,
-                       relax, max_iter, eps, x_new, u_new, nullptr, info, nullptr, workspace, workspace_bytes, true,
-                       stream);
+    BoxArgs a;
+    rc = box_begin(&a, model, params, n_params, T, false);
+    if (rc != IRS_OK) return rc;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi;
+    a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.max_iter = max_iter; a.eps = eps;
+    a.x_new = x_new; a.u_new = u_new; a.info = info;
+    return irs_box_admm_launch("irs_tvlqr_box_descent", model, false, a, workspace, workspace_bytes, BoxWs::Always,
+                               static_cast<hipStream_t>(stream));
 }
 
 int irs_quasistatic_box_descent(int model, const double* params, int n_params, int T, const double* At,
@@ -806,14 +818,15 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
                   "solver must be 0 (auto), 1 (ADMM), 2 (active set, lanes) or 3 (active set, matrix-core tiles)");
     IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
                   (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+    IRS_CHECK_ARG(irs_admm_settings_ok(rho, relax, max_iter, eps), "bad ADMM parameter");
     BoxArgs a;
-    int rc = box_args(&a, model, params, n_params, T, At, Bt, ct, Q, Qd, R,
-                      1.0,      // tv_lqr.py:107 adds du'R du as an expression: the full quadratic
-                      xd_trj, x0, x_lo, x_hi, u_lo, u_hi, du_lo, du_hi, true, rho, relax, max_iter, eps, x_new, u_new,
-                      cost, info);
+    int rc = box_begin(&a, model, params, n_params, T, true);
     if (rc != IRS_OK) return rc;
-    a.act_io = act_io;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
+    a.alpha = 1.0;      // tv_lqr.py:107 adds du'R du as an expression: the full quadratic
+    a.rho = rho; a.relax = relax; a.max_iter = max_iter; a.eps = eps;
+    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info; a.act_io = act_io;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // one control box (or none) and no state bounds: the exact active-set solvers apply
     const bool one_box = x_lo == nullptr && !(u_lo != nullptr && du_lo != nullptr);
@@ -823,15 +836,11 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
     }
     if (solver == 0) solver = auto_solver(model, T, one_box, workspace, workspace_bytes);
     if (solver == 1)    // records in the workspace only when they do not fit LDS
-        return run_admm("irs_quasistatic_box_descent", model, true, a, workspace, workspace_bytes, false, st);
+        return irs_box_admm_launch("irs_quasistatic_box_descent", model, true, a, workspace, workspace_bytes,
+                                   BoxWs::IfNeeded, st);
     const BoxPlan p = irs_box_plan(model, T, solver == 3 ? IRS_BOX_ACTIVE_SET_MFMA : IRS_BOX_ACTIVE_SET,
                                    workspace != nullptr ? BoxWs::IfNeeded : BoxWs::None);
-    if (p.max_T == 0) {
-        irs_set_error(irs_box_plan(model, T, IRS_BOX_ADMM_DU, BoxWs::None).max_T > 0
-                          ? "irs_quasistatic_box_descent: model %d does not fit the 16 x 16 tile"
-                          : "irs_quasistatic_box_descent: model %d is not position controlled", model);
-        return IRS_ERR_UNSUPPORTED;
-    }
+    if (p.max_T == 0) return no_tile_form("irs_quasistatic_box_descent", model, T);
     if (p.place == BoxPlace::None || workspace_bytes < p.records) {
         if (solver == 3)
             irs_set_error("irs_quasistatic_box_descent: horizon T=%d needs a %zu-byte workspace for the matrix-core "
@@ -849,8 +858,6 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
 }
 
 // ---- B problems per launch (solver 3's method) ---------------------------------------------------------------------
-static size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
 size_t irs_quasistatic_descent_batch_workspace_bytes(int model, int T, int B) {
     if (T <= 0 || B <= 0) return 0;
     return (size_t)B * round256(irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, BoxWs::IfNeeded).records);
@@ -869,31 +876,28 @@ int irs_quasistatic_box_descent_batch(int model, const double* params, int n_par
     IRS_CHECK_ARG((u_lo != nullptr) != (du_lo != nullptr), "give exactly one of the u / du bound pairs");
     IRS_CHECK_ARG(max_iter > 0 && eps > 0.0, "bad solver parameter");
     BoxArgs a;
-    int rc = box_args(&a, model, params, n_params, T, At, Bt, ct, Q, Qd, R, 1.0, xd_trj, x0, nullptr, nullptr, u_lo,
-                      u_hi, du_lo, du_hi, true, 10.0, 1.6, max_iter, eps, x_new, u_new, cost, info);
+    int rc = box_begin(&a, model, params, n_params, T, true);
     if (rc != IRS_OK) return rc;
-    a.act_io = act_io;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
+    a.alpha = 1.0; a.rho = 10.0; a.relax = 1.6; a.max_iter = max_iter; a.eps = eps;
+    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info; a.act_io = act_io;
     // a workspace puts the records there at any horizon (as irs_tvlqr_box_descent_wsx does); without one they must
     // fit LDS
     const BoxPlan p = irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, workspace != nullptr ? BoxWs::Always : BoxWs::None);
-    if (p.max_T == 0) {
-        irs_set_error(irs_box_plan(model, T, IRS_BOX_ADMM_DU, BoxWs::None).max_T > 0
-                          ? "irs_quasistatic_box_descent_batch: model %d does not fit the 16 x 16 tile"
-                          : "irs_quasistatic_box_descent_batch: model %d is not position controlled", model);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    const size_t stride = round256(p.records);
-    if (p.place == BoxPlace::None || workspace_bytes < (size_t)B * stride) {
+    if (p.max_T == 0) return no_tile_form("irs_quasistatic_box_descent_batch", model, T);
+    const WsFit f = ws_fit(p, (size_t)B, workspace, workspace_bytes);
+    if (p.place == BoxPlace::None || f.small) {
         irs_set_error("irs_quasistatic_box_descent_batch: horizon T=%d, B=%d needs a workspace of %zu bytes (given: %zu)",
-                      T, B, (size_t)B * round256(p.records), workspace_bytes);
+                      T, B, f.need, workspace_bytes);
         return IRS_ERR_WORKSPACE;
     }
-    if (p.place == BoxPlace::TilesHbm && (reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
+    if (p.place == BoxPlace::TilesHbm && f.misaligned) {
         irs_set_error("irs_quasistatic_box_descent_batch: the workspace must be 256-byte aligned");
         return IRS_ERR_INVALID_ARG;
     }
-    rc = irs_ctrlbox_mfma_launch_batch(model, a, du_lo != nullptr ? 1 : 0, p, static_cast<double*>(workspace), stride, B,
-                                       static_cast<hipStream_t>(stream));
+    rc = irs_ctrlbox_mfma_launch(model, a, du_lo != nullptr ? 1 : 0, p, static_cast<double*>(workspace),
+                                 static_cast<hipStream_t>(stream), B, f.stride);
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
@@ -936,16 +940,18 @@ int irs_tvlqr_box_solve_wsx(int model, const double* params, int n_params, int T
     IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
                   (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
     IRS_CHECK_ARG(position_controlled || du_lo == nullptr, "du bounds need the position-controlled form");
-    IRS_CHECK_ARG(rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0, "bad ADMM parameter");
+    IRS_CHECK_ARG(irs_admm_settings_ok(rho, relax, max_iter, eps), "bad ADMM parameter");
     int rc = check_box_workspace(__func__, model, T, position_controlled ? 1 : 0, workspace, workspace_bytes);
     if (rc != IRS_OK) return rc;
     BoxArgs a;
-    rc = box_args(&a, model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, x_lo, x_hi, u_lo, u_hi,
-                  du_lo, du_hi, true, rho, relax, max_iter, eps, x_star, u_star, nullptr, info);
+    rc = box_begin(&a, model, params, n_params, T, true);
     if (rc != IRS_OK) return rc;
-    a.single_tail = 1;
-    return run_admm("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes, true,
-                    static_cast<hipStream_t>(stream));
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
+    a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.max_iter = max_iter; a.eps = eps;
+    a.x_new = x_star; a.u_new = u_star; a.info = info; a.single_tail = 1;
+    return irs_box_admm_launch("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes,
+                               BoxWs::Always, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

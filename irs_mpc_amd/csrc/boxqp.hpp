@@ -50,6 +50,14 @@ struct BoxPlan {
 };
 // boxqp.hip: the one placement decision of every bounded descent and size query.  kind: IRS_BOX_*.  No HIP calls.
 BoxPlan irs_box_plan(int model, int T, int kind, BoxWs ws);
+inline bool irs_admm_settings_ok(double rho, double relax, int max_iter, double eps) {
+    return rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0;
+}
+// boxqp.hip: the ADMM kernel (du: its position-controlled form) on a filled BoxArgs, where the plan puts it.  ws may be
+// null; `policy` says what a workspace that is given is for.  fn: the entry a "model has no such form" error names.
+// The caller has checked the ADMM settings (irs_admm_settings_ok), as every entry does before anything else.
+int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, BoxWs policy,
+                        hipStream_t st);
 
 // ctrlbox.hip: active-set solver for the quasistatic descent with ONE control box.
 // kind 0: bounds on u_t (a.ulo/a.uhi), kind 1: bounds on u_t - u_{t-1} (a.dlo/a.dhi); a bound pair
@@ -62,9 +70,9 @@ size_t irs_ctrlbox_lds_bytes(int model, int T);
 // to keep them on chip.  Launches as planned: TilesLds, or TilesHbm with the records in `ws`.
 size_t irs_ctrlbox_mfma_record_bytes(int model, int T);
 size_t irs_ctrlbox_mfma_lds_bytes(int model, int T);
-int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, hipStream_t st);
-// B problems in one launch, one workgroup each: every per-problem array of `a` is B contiguous blocks (problem b's at
-// b times the block's size), Q / Qd / R and the scalars are shared; TilesHbm: problem b's records at ws + b * ws_stride
-// bytes.
-int irs_ctrlbox_mfma_launch_batch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, size_t ws_stride,
-                                  int B, hipStream_t st);
+// batch_B = 0: the single problem `a`, one workgroup.  batch_B >= 1: the batched kernel over that many problems, one
+// workgroup each (B = 1 too: the batched instantiation, not the single one) -- every per-problem array of `a` is B
+// contiguous blocks (problem b's at b times the block's size), Q / Qd / R and the scalars are shared; TilesHbm: problem
+// b's records at ws + b * ws_stride bytes.
+int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, hipStream_t st,
+                            int batch_B = 0, size_t ws_stride = 0);

@@ -1235,37 +1235,29 @@ static long long* cbm_stamps() {
 static long long* cbm_stamps() { return nullptr; }
 #endif
 
-template <class Model, int KIND>
-int launch_ctrlbox_mfma(const BoxArgs& a, const BoxPlan& p, double* ws, hipStream_t st) {
+// ctrlbox_mfma_kernel<Model, KIND, LDS, BATCH> over B workgroups, as planned: the records on chip (TilesLds) or in `ws`
+// (TilesHbm).  Bat: BoxSolo (B = 1), or the BoxBatch strides of a batch.
+template <class Model, int KIND, class Bat>
+int launch_ctrlbox_mfma(const BoxArgs& a, const BoxPlan& p, double* ws, int B, Bat bat, hipStream_t st) {
+    constexpr bool BATCH = std::is_same_v<Bat, BoxBatch>;
     if (p.place == BoxPlace::TilesLds) {
-        constexpr auto kern = ctrlbox_mfma_kernel<Model, KIND, true, false>;
-        const int rc = irs_raise_lds_limit<kern>(p.lds, "irs_quasistatic_box_descent");
+        constexpr auto kern = ctrlbox_mfma_kernel<Model, KIND, true, BATCH>;
+        const int rc = irs_raise_lds_limit<kern>(p.lds, BATCH ? "irs_quasistatic_box_descent_batch"
+                                                              : "irs_quasistatic_box_descent");
         if (rc != IRS_OK) return rc;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(128), p.lds, st, a, (double*)nullptr, cbm_stamps(), BoxSolo{});
+        hipLaunchKernelGGL(kern, dim3(B), dim3(128), p.lds, st, a, (double*)nullptr, cbm_stamps(), bat);
     } else {
-        auto kern = ctrlbox_mfma_kernel<Model, KIND, false, false>;
-        hipLaunchKernelGGL(kern, dim3(1), dim3(128), p.lds, st, a, ws, cbm_stamps(), BoxSolo{});
+        constexpr auto kern = ctrlbox_mfma_kernel<Model, KIND, false, BATCH>;
+        hipLaunchKernelGGL(kern, dim3(B), dim3(128), p.lds, st, a, ws, cbm_stamps(), bat);
     }
     return IRS_OK;
 }
 
-// B problems, one workgroup each; records in HBM: problem b's at ws + b * ws_stride bytes
-template <class Model, int KIND>
-int launch_ctrlbox_mfma_batch(const BoxArgs& a, const BoxPlan& p, double* ws, size_t ws_stride, int B, hipStream_t st) {
+// how far problem b's blocks lie from problem 0's in a batch of horizon T; records: ws_stride bytes apart
+template <class Model>
+BoxBatch box_batch_strides(long long T, size_t ws_stride) {
     constexpr long long n = Model::NX, m = Model::NU;
-    const long long T = a.T;
-    const BoxBatch bs{T * n * n, T * n * m, T * n, (T + 1) * n, n, T * m, (T + 1) * n, T * m, 1, 3, T * m,
-                      (long long)ws_stride};
-    if (p.place == BoxPlace::TilesLds) {
-        constexpr auto kern = ctrlbox_mfma_kernel<Model, KIND, true, true>;
-        const int rc = irs_raise_lds_limit<kern>(p.lds, "irs_quasistatic_box_descent_batch");
-        if (rc != IRS_OK) return rc;
-        hipLaunchKernelGGL(kern, dim3(B), dim3(128), p.lds, st, a, (double*)nullptr, cbm_stamps(), bs);
-    } else {
-        auto kern = ctrlbox_mfma_kernel<Model, KIND, false, true>;
-        hipLaunchKernelGGL(kern, dim3(B), dim3(128), p.lds, st, a, ws, cbm_stamps(), bs);
-    }
-    return IRS_OK;
+    return {T * n * n, T * n * m, T * n, (T + 1) * n, n, T * m, (T + 1) * n, T * m, 1, 3, T * m, (long long)ws_stride};
 }
 
 }  // namespace
@@ -1294,26 +1286,22 @@ size_t irs_ctrlbox_mfma_lds_bytes(int model, int T) {
     return r;
 }
 
-int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, hipStream_t st) {
+int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, hipStream_t st,
+                            int batch_B, size_t ws_stride) {
     int rc = IRS_ERR_UNSUPPORTED;
     IRS_DISPATCH_MODEL(model, {
         if constexpr (has_u_into_x<Model>::value) {
-            if constexpr (MfLayout<Model::NX, Model::NU>::FITS)
-                rc = kind == KIND_ABS_M ? launch_ctrlbox_mfma<Model, KIND_ABS_M>(a, p, ws, st)
-                                        : launch_ctrlbox_mfma<Model, KIND_REL_M>(a, p, ws, st);
-        }
-    });
-    return rc;
-}
-
-int irs_ctrlbox_mfma_launch_batch(int model, const BoxArgs& a, int kind, const BoxPlan& p, double* ws, size_t ws_stride,
-                                  int B, hipStream_t st) {
-    int rc = IRS_ERR_UNSUPPORTED;
-    IRS_DISPATCH_MODEL(model, {
-        if constexpr (has_u_into_x<Model>::value) {
-            if constexpr (MfLayout<Model::NX, Model::NU>::FITS)
-                rc = kind == KIND_ABS_M ? launch_ctrlbox_mfma_batch<Model, KIND_ABS_M>(a, p, ws, ws_stride, B, st)
-                                        : launch_ctrlbox_mfma_batch<Model, KIND_REL_M>(a, p, ws, ws_stride, B, st);
+            if constexpr (MfLayout<Model::NX, Model::NU>::FITS) {
+                const bool abs = kind == KIND_ABS_M;
+                if (batch_B > 0) {
+                    const BoxBatch bs = box_batch_strides<Model>(a.T, ws_stride);
+                    rc = abs ? launch_ctrlbox_mfma<Model, KIND_ABS_M>(a, p, ws, batch_B, bs, st)
+                             : launch_ctrlbox_mfma<Model, KIND_REL_M>(a, p, ws, batch_B, bs, st);
+                } else {
+                    rc = abs ? launch_ctrlbox_mfma<Model, KIND_ABS_M>(a, p, ws, 1, BoxSolo{}, st)
+                             : launch_ctrlbox_mfma<Model, KIND_REL_M>(a, p, ws, 1, BoxSolo{}, st);
+                }
+            }
         }
     });
     return rc;

@@ -15,15 +15,6 @@ int irs_tvlqr_descent_row(int model, const double* params, int n_params, int T, 
                           const double* xd_trj, const double* x0, double* K, double* k, double* x_new, double* u_new,
                           double* cost, int* info, const int* smooth_info, int* row, void* stream);
 
-// boxqp.hip, for iterate.hip: irs_tvlqr_box_descent_if whose records go to `workspace` (may be null) when they do
-// not fit LDS
-int irs_tvlqr_box_descent_ifw(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                              const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                              const double* xd_trj, const double* x0, const double* xlo, const double* xhi,
-                              const double* ulo, const double* uhi, double rho, double relax, int max_iter, double eps,
-                              double* x_new, double* u_new, double* cost, int* info, const int* run_flag,
-                              void* workspace, size_t workspace_bytes, void* stream);
-
 // The dynamic LDS one workgroup of the bounded-descent kernels may take (160 KB per CU, less a margin).
 constexpr size_t IRS_LDS_BUDGET = 160 * 1024 - 512;
 

@@ -346,6 +346,22 @@ int irs_iterate(const irs_iterate_call* c, irs_timing* timing, void* stream) {
     }
     // the bounded descent runs on chip, or with its records in the tail of the scratch
     const bool box_fits = bounded && box.place != BoxPlace::None;
+    // what every bounded descent of the call shares; the loop sets the start state and the outputs of its descent
+    BoxArgs ba{};
+    if (box_fits) {
+        rc = irs_load_params(c->model, c->params, c->n_params, &ba.p);
+        if (rc != IRS_OK) return rc;
+        ba.At = At; ba.Bt = Bt; ba.ct = ct; ba.Q = c->Q; ba.Qd = c->Qd; ba.R = c->R; ba.xd = c->xd_trj;
+        ba.xlo = c->xlo; ba.xhi = c->xhi; ba.ulo = c->ulo; ba.uhi = c->uhi;
+        ba.alpha = c->alpha_R; ba.T = T; ba.run_flag = box_flag;
+        ba.rho = c->qp_rho > 0 ? c->qp_rho : 10.0; ba.relax = c->qp_relax > 0 ? c->qp_relax : 1.6;
+        ba.max_iter = c->qp_max_iter > 0 ? c->qp_max_iter : 5000; ba.eps = c->qp_eps > 0 ? c->qp_eps : 1e-8;
+        // (the code and text of the bounded-descent entry these descents used to go through)
+        if (!irs_admm_settings_ok(ba.rho, ba.relax, ba.max_iter, ba.eps)) {
+            irs_set_error("irs_tvlqr_box_descent_ifw: bad ADMM parameter");
+            return IRS_ERR_INVALID_ARG;
+        }
+    }
     PhaseTimer tm(timing != nullptr, st);
     const size_t xs = (size_t)(T + 1) * n, us = (size_t)T * m;
     for (int it = 0; it < c->n_descents; ++it) {
@@ -373,13 +389,11 @@ int irs_iterate(const irs_iterate_call* c, irs_timing* timing, void* stream) {
             rc = plan_check_launch(n, m, T, At, Bt, ct, K, k, x_new, c->xlo, c->xhi, c->ulo, c->uhi, box_flag, descent_info,
                                    exact ? nullptr : smooth_info, box_fits ? 0 : 1, c->info_hist + (size_t)it * 8, st);
             if (rc != IRS_OK) return rc;
-            if (box_fits) {
-                rc = irs_tvlqr_box_descent_ifw(c->model, c->params, c->n_params, T, At, Bt, ct, c->Q, c->Qd, c->R,
-                                              c->alpha_R, c->xd_trj, x_nom, c->xlo, c->xhi, c->ulo, c->uhi,
-                                              c->qp_rho > 0 ? c->qp_rho : 10.0, c->qp_relax > 0 ? c->qp_relax : 1.6,
-                                              c->qp_max_iter > 0 ? c->qp_max_iter : 5000, c->qp_eps > 0 ? c->qp_eps : 1e-8,
-                                               x_new, u_new, c->cost_hist + it, c->info_hist + (size_t)it * 8 + 3, box_flag,
-                                               recs, rec_bytes, stream);   // its info lands in the row (zeroed above) if it runs
+            if (box_fits) {     // its info lands in the row (zeroed above) if it runs
+                ba.x0 = x_nom; ba.x_new = x_new; ba.u_new = u_new;
+                ba.cost = c->cost_hist + it; ba.info = c->info_hist + (size_t)it * 8 + 3;
+                rc = irs_box_admm_launch("irs_tvlqr_box_descent", c->model, false, ba, recs, rec_bytes, BoxWs::IfNeeded,
+                                         st);
                 if (rc != IRS_OK) return rc;
             }
         }

@@ -33,6 +33,11 @@ def _ptr(t, dtype):
     return t.data_ptr()
 
 
+def _ws_args(ws):
+    """The (pointer, bytes) pair of an optional workspace tensor."""
+    return (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
+
+
 def to_dev(a, dtype=F64):
     """numpy / tensor -> contiguous device tensor of `dtype`."""
     dev = require_gpu()
@@ -184,20 +189,22 @@ class DeviceModel:
         """The longest horizon the bounded TV-LQR kernel runs (records in HBM; 0: the model has no such form)."""
         return self.lib.irs_box_horizon_limit(self.model_id, _lib.BOX_ADMM_DU if du else _lib.BOX_ADMM)
 
-    def _box_workspace(self, T, du, device, force=False):
-        """Cached per device: the bounded TV-LQR kernel's factor records, when they do not fit LDS (or `force`)."""
-        need = self.lib.irs_tvlqr_box_workspace_bytes(self.model_id, int(T), 1 if du else 0)
-        if force and need == 0:
-            # records that would fit on chip: T x the record stride (the query at 2^14 steps is exactly 2^14 strides)
-            stride = self.lib.irs_tvlqr_box_workspace_bytes(self.model_id, 1 << 14, 1 if du else 0) >> 14
-            need = (int(T) * stride + 255) // 256 * 256
+    def _cached_workspace(self, key, need, device):
+        """A byte buffer of at least `need` bytes, cached under (key, device), grown on demand; None for need == 0."""
         if need == 0:
             return None
-        ws = self._ws.get(("box", device))
+        ws = self._ws.get((key, device))
         if ws is None or ws.numel() < need:
-            ws = torch.empty((need,), dtype=torch.uint8, device=device)
-            self._ws[("box", device)] = ws
+            ws = self._ws[(key, device)] = torch.empty((need,), dtype=torch.uint8, device=device)
         return ws
+
+    def _box_workspace(self, T, du, device, force=False):
+        """The bounded TV-LQR kernel's factor records, when they do not fit LDS (or `force`: at any horizon)."""
+        if force:
+            need = self.lib.irs_box_records_bytes(self.model_id, int(T), _lib.BOX_ADMM_DU if du else _lib.BOX_ADMM)
+        else:
+            need = self.lib.irs_tvlqr_box_workspace_bytes(self.model_id, int(T), 1 if du else 0)
+        return self._cached_workspace("box", need, device)
 
     def tvlqr_box_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, xlo, xhi, ulo, uhi, alpha_R=0.5,
                           rho=10.0, relax=1.6, max_iter=5000, eps=1e-8, records_in_hbm=False):
@@ -216,9 +223,7 @@ class DeviceModel:
                                                  float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(xlo, F64),
                                                  _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64), float(rho),
                                                  float(relax), int(max_iter), float(eps), _ptr(o["x_new"], F64),
-                                                 _ptr(o["u_new"], F64), o["info"].data_ptr(),
-                                                 ws.data_ptr() if ws is not None else None,
-                                                 ws.numel() if ws is not None else 0, _stream()),
+                                                 _ptr(o["u_new"], F64), o["info"].data_ptr(), *_ws_args(ws), _stream()),
               "irs_tvlqr_box_descent_wsx")
         return o
 
@@ -241,9 +246,7 @@ class DeviceModel:
                                                _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64),
                                                float(rho), float(relax), int(max_iter), float(eps),
                                                _ptr(o["x_star"], F64), _ptr(o["u_star"], F64), o["info"].data_ptr(),
-                                               ws.data_ptr() if ws is not None else None,
-                                               ws.numel() if ws is not None else 0, _stream()),
-              "irs_tvlqr_box_solve_wsx")
+                                               *_ws_args(ws), _stream()), "irs_tvlqr_box_solve_wsx")
         return o
 
     SOLVER_AUTO, SOLVER_ADMM, SOLVER_ACTIVE_SET, SOLVER_ACTIVE_SET_MFMA = 0, 1, 2, 3
@@ -257,13 +260,7 @@ class DeviceModel:
 
     def _descent_workspace(self, T, solver, device):
         need = self.lib.irs_quasistatic_descent_workspace_bytes(self.model_id, int(T), int(solver))
-        if need == 0:
-            return None
-        ws = self._ws.get(("descent", device))
-        if ws is None or ws.numel() < need:
-            ws = torch.empty((need,), dtype=torch.uint8, device=device)
-            self._ws[("descent", device)] = ws
-        return ws
+        return self._cached_workspace("descent", need, device)
 
     def quasistatic_box_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo=None, x_hi=None, u_lo=None,
                                 u_hi=None, du_lo=None, du_hi=None, solver=0, rho=10.0, relax=1.6,
@@ -292,27 +289,18 @@ class DeviceModel:
             _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(x_lo, F64), _ptr(x_hi, F64),
             _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64), int(solver), float(rho),
             float(relax), int(max_iter), float(eps), _ptr(o["x_new"], F64), _ptr(o["u_new"], F64), _ptr(o["cost"], F64),
-            o["info"].data_ptr(), _ptr(act, F64), ws.data_ptr() if ws is not None else None,
-            ws.numel() if ws is not None else 0, _stream()), "irs_quasistatic_box_descent_wsx")
+            o["info"].data_ptr(), _ptr(act, F64), *_ws_args(ws), _stream()), "irs_quasistatic_box_descent_wsx")
         return o
 
     # ---- B quasistatic descents per launch ------------------------------------
     def _descent_batch_workspace(self, T, B, device, force=False):
         """Cached per (T, B): the records of B problems, where they do not fit LDS (or `force`); else None."""
-        need = self.lib.irs_quasistatic_descent_batch_workspace_bytes(self.model_id, int(T), int(B))
-        if force and need == 0:
-            # records that would fit on chip: their size is affine in T, so two queries beyond the LDS horizon give it
-            f = [self.lib.irs_quasistatic_descent_workspace_bytes(self.model_id, t, 3) for t in (1 << 14, (1 << 14) + 1)]
-            one = f[0] - ((1 << 14) - int(T)) * (f[1] - f[0])
+        if force:
+            one = self.lib.irs_box_records_bytes(self.model_id, int(T), _lib.BOX_ACTIVE_SET_MFMA)
             need = int(B) * ((one + 255) // 256 * 256)
-        if need == 0:
-            return None
-        key = ("descent_batch", int(T), int(B), device)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty((need,), dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
+        else:
+            need = self.lib.irs_quasistatic_descent_batch_workspace_bytes(self.model_id, int(T), int(B))
+        return self._cached_workspace(("descent_batch", int(T), int(B)), need, device)
 
     def quasistatic_box_descent_batch(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, u_lo=None, u_hi=None, du_lo=None,
                                       du_hi=None, max_iter=5000, eps=1e-8, out=None, act=None, records_in_hbm=False):
@@ -343,8 +331,8 @@ class DeviceModel:
             self.model_id, self._p, self._np, T, B, _ptr(At, F64), _ptr(Bt, F64), _ptr(ct, F64), _ptr(Q, F64),
             _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(u_lo, F64), _ptr(u_hi, F64),
             _ptr(du_lo, F64), _ptr(du_hi, F64), int(max_iter), float(eps), _ptr(o["x_new"], F64), _ptr(o["u_new"], F64),
-            _ptr(o["cost"], F64), o["info"].data_ptr(), _ptr(act, F64), ws.data_ptr() if ws is not None else None,
-            ws.numel() if ws is not None else 0, _stream()), "irs_quasistatic_box_descent_batch")
+            _ptr(o["cost"], F64), o["info"].data_ptr(), _ptr(act, F64), *_ws_args(ws), _stream()),
+            "irs_quasistatic_box_descent_batch")
         return o
 
     def quasistatic_bound_rows_batch(self, x_trj, idx, offsets, rel=False, out=None):
@@ -507,10 +495,8 @@ class DeviceModel:
             info = torch.empty((T,), dtype=torch.int32, device=dev)
         check(self.lib.irs_smooth_finalize_ws(self.model_id, self._p, self._np, mode, T, int(N_total),
                                               _ptr(x_trj, F64), _ptr(u_trj, F64), _ptr(sums, F64), _ptr(At, F64),
-                                              _ptr(Bt, F64), _ptr(ct, F64), info.data_ptr(),
-                                              workspace.data_ptr() if workspace is not None else None,
-                                              workspace.numel() if workspace is not None else 0, _stream()),
-              "irs_smooth_finalize_ws")
+                                              _ptr(Bt, F64), _ptr(ct, F64), info.data_ptr(), *_ws_args(workspace),
+                                              _stream()), "irs_smooth_finalize_ws")
         return At, Bt, ct, info
 
     def exact_linearize(self, x_trj, u_trj):

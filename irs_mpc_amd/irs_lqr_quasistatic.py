@@ -38,6 +38,32 @@ from .quasistatic_base import QuasistaticOptimizerBase, quasistatic_eval_cost  #
 from .tv_lqr import get_solver
 
 
+# gradient_mode -> the sample pass of the modes that have one
+SAMPLED_MODE = {"zero_order_B": SMOOTH_ZERO_ORDER_B, "first_order": SMOOTH_FIRST_ORDER}
+
+# settings of the bounded QPs (extensions of the parameter object) and their defaults
+QP_FIELDS = ("qp_solver", "qp_rho", "qp_max_iter", "qp_eps")
+QP_DEFAULTS = (0, 100.0, 20000, 1e-9)
+
+MSG_SMOOTH = "randomized-smoothing least squares is rank deficient"
+MSG_QP = "TV_LQR failed. Optimization problem is not solved."      # solve_tvlqr's ValueError (tv_lqr.py:139-140)
+
+
+def qp_settings(params):
+    """(qp_solver, qp_rho, qp_max_iter, qp_eps) of a parameter object; a field it lacks is at its default."""
+    return tuple(getattr(params, field, default) for field, default in zip(QP_FIELDS, QP_DEFAULTS))
+
+
+def descent_failure(info, smoothing_failed):
+    """Why a descent cannot be adopted -- the ValueError text of `IrsLqrQuasistatic` -- or None: its smoothing solve
+    failed at some time step, or (info: the descent's three words) a Hessian was not PD or a tail did not converge."""
+    if smoothing_failed:
+        return MSG_SMOOTH
+    if info[0] != 0 or info[2] != 0:
+        return MSG_QP
+    return None
+
+
 class IrsLqrQuasistaticParameters:
     """irs_lqr/irs_lqr_quasistatic.py:12-41."""
 
@@ -73,15 +99,15 @@ class IrsLqrQuasistaticParameters:
 
         # ---- extensions (absent in the reference) ----
         self.device_rng_seed = None     # int: draw the perturbations on the device
-        self.qp_solver = 0              # 0 auto, 1 ADMM, 2 active set (lanes), 3 active set (matrix-core tiles)
-        self.qp_rho = 100.0             # ADMM penalty / iteration limit / tolerance of the bounded QPs
-        self.qp_max_iter = 20000
-        self.qp_eps = 1e-9
+        # qp_solver: 0 auto, 1 ADMM, 2 active set (lanes), 3 active set (matrix-core tiles); qp_rho, qp_max_iter,
+        # qp_eps: ADMM penalty / iteration limit / tolerance of the bounded QPs
+        self.qp_solver, self.qp_rho, self.qp_max_iter, self.qp_eps = QP_DEFAULTS
 
 
-def decouple_exact_dev(At, Bt, ct, x_trj, u_trj, idx, dim_x, dim_u):
-    """decouple_AB_matrices on the exact pair (in place) and c_t = f - A x - B u rebuilt with it
-    (irs_lqr_quasistatic.py:218-225, 275-284); shared with the batched class, which must compute the same bits."""
+def decouple_AB_dev(At, Bt, ct, x_trj, u_trj, idx, dim_x, dim_u):
+    """decouple_AB_matrices on a full pair (in place) and c_t = f - A x - B u rebuilt with it, f recovered from the
+    pair as given (irs_lqr_quasistatic.py:218-225, 275-284); shared with the batched class, which must compute the
+    same bits."""
     f = ct + torch.einsum("tij,tj->ti", At, x_trj[:-1]) + torch.einsum("tij,tj->ti", Bt, u_trj)
     Bt[:, idx, :] = torch.eye(dim_u, dtype=At.dtype, device=At.device)
     At[:] = torch.eye(dim_x, dtype=At.dtype, device=At.device)
@@ -102,7 +128,7 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
                                       "is not implemented on the device")
         dm = q_dynamics.dm()
         one_box = self.x_bounds_abs is None and (self.u_bounds_abs is None or self.u_bounds_rel is None)
-        self._solver = int(getattr(params, "qp_solver", 0))
+        self._solver = int(qp_settings(params)[0])
         if self._solver == 0:
             # one control box: the exact active-set method -- on matrix-core tiles (any horizon: beyond the
             # LDS-resident size its records move to HBM) where the model fits the tile, else on lanes
@@ -133,7 +159,7 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
         if self.gradient_mode == "first_order" and not self.decouple_AB:
             return self._first_order_full_dev(x_trj, u_trj, std_u)
         # "zero_order_B": least-squares fit of B; "first_order": mean of the per-sample derivative
-        MODE = SMOOTH_FIRST_ORDER if self.gradient_mode == "first_order" else SMOOTH_ZERO_ORDER_B
+        MODE = SAMPLED_MODE[self.gradient_mode]
         rank, world = dist_util.rank_world()
         N = self.num_samples
         seed = getattr(self.params, "device_rng_seed", None)
@@ -191,7 +217,7 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
         At, Bt, ct = self._dm.exact_linearize(x_trj, u_trj)
         self._smooth_info = torch.zeros(self.T, dtype=torch.int32, device=x_trj.device)
         if self.decouple_AB:
-            At, Bt, ct = decouple_exact_dev(At, Bt, ct, x_trj, u_trj, self._idx, self.dim_x, self.dim_u)
+            At, Bt, ct = decouple_AB_dev(At, Bt, ct, x_trj, u_trj, self._idx, self.dim_x, self.dim_u)
         return At, Bt, ct
 
     def _zero_order_AB_dev(self, x_trj, u_trj, std_u):
@@ -200,20 +226,12 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
         (`calc_AB_batch_dev`: accumulate the statistics, all-reduce, damp^2 on the Gram diagonal, solve); then
         decouple_AB_matrices (:275-284) and c_t = f - A x - B u with the decoupled pair, f recovered from the
         undecoupled solve."""
-        n, m = self.dim_x, self.dim_u
         At, Bt, ct, self._smooth_info = self.q_dynamics.calc_AB_batch_dev(
             x_trj[:-1], u_trj, self.num_samples, std_u, "zero_order_AB",
             seed=getattr(self.params, "device_rng_seed", None), it=self.current_iter)
-        if not self.decouple_AB:
-            return At, Bt, ct
-        # f = c + A x + B u with the fitted pair; then overwrite the structure and rebuild c
-        f = ct + torch.einsum("tij,tj->ti", At, x_trj[:-1]) + torch.einsum("tij,tj->ti", Bt, u_trj)
-        eye_m = torch.eye(m, dtype=At.dtype, device=At.device)
-        Bt[:, self._idx, :] = eye_m
-        At[:] = torch.eye(n, dtype=At.dtype, device=At.device)
-        At[:, :, self._idx] = 0.0
-        ct = f - torch.einsum("tij,tj->ti", At, x_trj[:-1]) - torch.einsum("tij,tj->ti", Bt, u_trj)
-        return At, Bt, ct.contiguous()
+        if self.decouple_AB:
+            At, Bt, ct = decouple_AB_dev(At, Bt, ct, x_trj, u_trj, self._idx, self.dim_x, self.dim_u)
+        return At, Bt, ct
 
     def get_TV_matrices(self, x_trj, u_trj):
         T = u_trj.shape[0]
@@ -221,7 +239,7 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
         At, Bt, ct = self._get_TV_matrices_dev(dev.to_dev(np.asarray(x_trj, float)),
                                                dev.to_dev(np.asarray(u_trj, float)))
         if bool((self._smooth_info != 0).any().item()):
-            raise ValueError("randomized-smoothing least squares is rank deficient")
+            raise ValueError(MSG_SMOOTH)
         return At.cpu().numpy(), Bt.cpu().numpy(), ct.cpu().numpy()
 
     # the worker pool is the GPU: same launch
@@ -252,16 +270,14 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
 
     def _local_descent_dev(self, x_trj, u_trj):
         At, Bt, ct = self._get_TV_matrices_dev(x_trj, u_trj)
-        p = self.params
+        _, rho, max_iter, eps = qp_settings(self.params)
         if self._solver in (2, 3) and getattr(self, "_act", None) is None:
             # the active set of the first tail, handed from one iteration's descent to the next: consecutive
             # iterations bind nearly the same bounds (the QP's solution does not depend on the start)
             self._act = torch.zeros((self.T, self.dim_u), dtype=dev.F64, device=x_trj.device)
         o = self._dm.quasistatic_box_descent(At, Bt, ct, self._Q, self._Qd, self._R, self._xd,
                                              x_trj[0].contiguous(), *self._bounds_dev(x_trj),
-                                             solver=self._solver, rho=getattr(p, "qp_rho", 100.0),
-                                             max_iter=getattr(p, "qp_max_iter", 20000),
-                                             eps=getattr(p, "qp_eps", 1e-9),
+                                             solver=self._solver, rho=rho, max_iter=max_iter, eps=eps,
                                              act=self._act if self._solver in (2, 3) else None)
         self._last = dict(At=At, Bt=Bt, ct=ct, info=o["info"])
         return o["x_new"], o["u_new"], o["cost"]
@@ -273,12 +289,9 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
         return x_new.cpu().numpy(), u_new.cpu().numpy()
 
     def _check_last(self):
-        info = self._last["info"].cpu().numpy()
-        if bool((self._smooth_info != 0).any().item()):
-            raise ValueError("randomized-smoothing least squares is rank deficient")
-        if info[0] != 0 or info[2] != 0:
-            # like solve_tvlqr's `raise ValueError` when the solver fails (tv_lqr.py:139-140)
-            raise ValueError("TV_LQR failed. Optimization problem is not solved.")
+        failure = descent_failure(self._last["info"].cpu().numpy(), bool((self._smooth_info != 0).any().item()))
+        if failure is not None:
+            raise ValueError(failure)
 
     # ---- outer loop: the trajectory stays on the device ------------------------------------------------
     def iterate(self, max_iterations):
@@ -303,16 +316,9 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
         infos = torch.stack([r[2] for r in recs]).cpu().numpy()
         sbad = torch.stack([(r[3] != 0).any() for r in recs]).cpu().numpy()
         self.current_iter = it0
-        for i in range(len(recs)):
-            if sbad[i]:
-                raise ValueError("randomized-smoothing least squares is rank deficient")
-            if infos[i][0] != 0 or infos[i][2] != 0:
-                raise ValueError("TV_LQR failed. Optimization problem is not solved.")    # tv_lqr.py:139-140
-            cost_new = self._log(xs[i], us[i])
-            if self.current_iter > max_iterations:
-                break
-            self.cost, self.x_trj, self.u_trj = cost_new, xs[i], us[i]
-            self.current_iter += 1
+        failure = self._replay(xs, us, [descent_failure(*r) for r in zip(infos, sbad)], max_iterations)
+        if failure is not None:
+            raise ValueError(failure)
         return self.x_trj, self.u_trj, self.cost
 
     def _start(self):

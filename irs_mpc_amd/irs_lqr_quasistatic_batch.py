@@ -17,12 +17,8 @@ import torch
 
 from . import device as dev
 from . import distributed as dist_util
-from ._lib import SMOOTH_FIRST_ORDER, SMOOTH_ZERO_ORDER_B
-from .irs_lqr_quasistatic import decouple_exact_dev
+from .irs_lqr_quasistatic import QP_FIELDS, SAMPLED_MODE, decouple_AB_dev, descent_failure, qp_settings
 from .quasistatic_base import COST_TERMS, QuasistaticOptimizerBase
-
-MSG_SMOOTH = "randomized-smoothing least squares is rank deficient"      # the ValueErrors of IrsLqrQuasistatic
-MSG_QP = "TV_LQR failed. Optimization problem is not solved."
 
 
 def _same_function(f, g):
@@ -75,8 +71,8 @@ class IrsLqrQuasistaticBatch:
             if (p.u_bounds_abs is None, p.u_bounds_rel is None) != (p0.u_bounds_abs is None, p0.u_bounds_rel is None):
                 raise ValueError("params_list[%d].u_bounds_abs / u_bounds_rel: the problems must have the same kind of "
                                  "bound (abs or rel)" % b)
-            for field, default in (("qp_solver", 0), ("qp_rho", 100.0), ("qp_max_iter", 20000), ("qp_eps", 1e-9)):
-                if getattr(p, field, default) != getattr(p0, field, default):
+            for field, value, value0 in zip(QP_FIELDS, qp_settings(p), qp_settings(p0)):
+                if value != value0:
                     raise ValueError("params_list[%d].%s differs from params_list[0].%s" % (b, field, field))
         # ---- what the batched path serves ----
         if p0.gradient_mode not in ("zero_order_B", "first_order", "exact"):
@@ -91,7 +87,7 @@ class IrsLqrQuasistaticBatch:
             raise NotImplementedError("state bounds are not served by the batched descent")
         if p0.u_bounds_abs is not None and p0.u_bounds_rel is not None:
             raise NotImplementedError("the batched descent takes ONE control box: u_bounds_abs or u_bounds_rel")
-        if int(getattr(p0, "qp_solver", 0)) not in (0, 3):
+        if int(qp_settings(p0)[0]) not in (0, 3):
             raise NotImplementedError("the batched descent is solver 3's method (qp_solver 0 or 3)")
         dm = q_dynamics.dm()
         if not dm.quasistatic_descent_supported(p0.T, 3):
@@ -157,11 +153,11 @@ class IrsLqrQuasistaticBatch:
     def _linearise(self, X, U, it, AT, BT, CT, sinfo):
         """B sample passes through the single-problem entry, back to back on the stream: problem b's with its seed and
         the iteration counter -- the draws of its single twin."""
-        mode = SMOOTH_FIRST_ORDER if self.gradient_mode == "first_order" else SMOOTH_ZERO_ORDER_B
+        mode = SAMPLED_MODE.get(self.gradient_mode)
         for b, p in enumerate(self.params_list):
             if self.gradient_mode == "exact":
                 At, Bt, ct = self._dm.exact_linearize(X[b], U[b])
-                At, Bt, ct = decouple_exact_dev(At, Bt, ct, X[b], U[b], self._idx, self.dim_x, self.dim_u)
+                At, Bt, ct = decouple_AB_dev(At, Bt, ct, X[b], U[b], self._idx, self.dim_x, self.dim_u)
                 AT[b].copy_(At)
                 BT[b].copy_(Bt)
                 CT[b].copy_(ct)
@@ -181,7 +177,8 @@ class IrsLqrQuasistaticBatch:
         if dist_util.rank_world()[1] != 1:
             raise NotImplementedError("the batch runs on one GPU")
         B, T, n, m = self.B, self.T, self.dim_x, self.dim_u
-        dm, p0 = self._dm, self.params_list[0]
+        dm = self._dm
+        _, _, qp_max_iter, qp_eps = qp_settings(self.params_list[0])
         it0 = self.current_iter
         D = max(1, max_iterations - it0 + 2)                 # the single loop: descents until current_iter > max
         X = dev.to_dev(self.x_trj)
@@ -197,8 +194,8 @@ class IrsLqrQuasistaticBatch:
         BT = torch.empty((B, T, n, m), dtype=dev.F64, device=device)
         CT = torch.empty((B, T, n), dtype=dev.F64, device=device)
         if self.gradient_mode != "exact":
-            mode = SMOOTH_FIRST_ORDER if self.gradient_mode == "first_order" else SMOOTH_ZERO_ORDER_B
-            self._sums = torch.empty((B, T, dm.sums_len(mode)), dtype=dev.F64, device=device)
+            P = dm.sums_len(SAMPLED_MODE[self.gradient_mode])
+            self._sums = torch.empty((B, T, P), dtype=dev.F64, device=device)
         if self._act is None:
             # the first tail's active set of every problem, handed from one descent to the next (zeros: cold start)
             self._act = torch.zeros((B, T, m), dtype=dev.F64, device=device)
@@ -215,7 +212,7 @@ class IrsLqrQuasistaticBatch:
             rows = dict(du_lo=self._rows[0], du_hi=self._rows[1]) if self._kind == "rel" else dict(
                 u_lo=self._rows[0], u_hi=self._rows[1])
             dm.quasistatic_box_descent_batch(AT, BT, CT, self._Q, self._Qd, self._R, self._xd, x0,
-                                             max_iter=getattr(p0, "qp_max_iter", 20000), eps=getattr(p0, "qp_eps", 1e-9),
+                                             max_iter=qp_max_iter, eps=qp_eps,
                                              out=dict(x_new=xs[d], u_new=us[d], cost=costs[d], info=infos[d]),
                                              act=self._act, **rows)
             X, U = xs[d], us[d]
@@ -227,17 +224,7 @@ class IrsLqrQuasistaticBatch:
             if self.status[b] is not None:
                 continue                                     # failed in an earlier call: frozen at its last adopted state
             pr.current_iter = it0
-            for i in range(D):
-                if sbad[i, b]:
-                    self.status[b] = MSG_SMOOTH
-                    break
-                if infos_h[i, b, 0] != 0 or infos_h[i, b, 2] != 0:
-                    self.status[b] = MSG_QP
-                    break
-                cost_new = pr._log(xs_h[i, b], us_h[i, b])
-                if pr.current_iter > max_iterations:
-                    break
-                pr.cost, pr.x_trj, pr.u_trj = cost_new, xs_h[i, b], us_h[i, b]
-                pr.current_iter += 1
+            failures = [descent_failure(infos_h[i, b], sbad[i, b]) for i in range(D)]
+            self.status[b] = pr._replay(xs_h[:, b], us_h[:, b], failures, max_iterations)
         self.current_iter = it0 + D - 1
         return self.x_trj, self.u_trj, self.cost

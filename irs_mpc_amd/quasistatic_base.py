@@ -94,6 +94,20 @@ class QuasistaticOptimizerBase:
             self.x_trj_best, self.u_trj_best, self.cost_best = x_trj, u_trj, total
         return total
 
+    def _replay(self, xs, us, failures, max_iterations):
+        """The loop below for descents that have already run, in order: xs[i], us[i] are descent i's host trajectories,
+        failures[i] is None or why it failed.  Stops at the first failure and returns its message -- the lists then hold
+        everything before it -- else logs, adopts and counts as `iterate` does, and returns None."""
+        for x_new, u_new, failure in zip(xs, us, failures):
+            if failure is not None:
+                return failure
+            cost_new = self._log(x_new, u_new)
+            if self.current_iter > max_iterations:
+                break
+            self.cost, self.x_trj, self.u_trj = cost_new, x_new, u_new
+            self.current_iter += 1
+        return None
+
     def iterate(self, max_iterations):
         """max_iterations + 1 descents; the last one is logged (and may become the best) but not
         adopted -- the reference's loop shape (irs_lqr_quasistatic.py:347-390)."""

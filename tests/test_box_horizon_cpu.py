@@ -239,6 +239,78 @@ def test_box_horizon_limit_equals_the_walk(lib):
     assert lib.irs_box_horizon_limit(HAND, 4) == 0 and lib.irs_box_horizon_limit(N_MODELS, 0) == 0
 
 
+PENDULUM = 0
+KIND_ADMM, KIND_ADMM_DU, KIND_ACTIVE_SET, KIND_TILES = 0, 1, 2, 3
+
+
+def round256(v):
+    return (v + 255) // 256 * 256
+
+
+def test_records_bytes_is_the_planner_at_any_horizon(lib):
+    """irs_box_records_bytes: what the workspace queries answer where they answer at all, and the same function of T
+    below the LDS horizon, where they answer 0."""
+    Ts = (1, 10, 50, 80, 200)
+    for model in (HAND, BOX_PIVOT, BICYCLE, QUAD, PENDULUM):
+        for kind in (KIND_ADMM, KIND_ADMM_DU, KIND_TILES):
+            has_form = lib.irs_box_horizon_limit(model, kind) > 0
+            got = [lib.irs_box_records_bytes(model, T, kind) for T in Ts]
+            if kind == KIND_TILES:
+                beyond = [lib.irs_quasistatic_descent_workspace_bytes(model, T, 3) for T in Ts]
+            else:
+                beyond = [lib.irs_tvlqr_box_workspace_bytes(model, T, kind) for T in Ts]
+            for T, g, w in zip(Ts, got, beyond):
+                assert w == 0 or g == w, (model, kind, T, g, w)
+                assert (g > 0) == has_form, (model, kind, T, g)
+            assert got == sorted(got), (model, kind, got)
+            if kind == KIND_TILES:
+                for T, g, w in zip(Ts, got, beyond):
+                    for B in (1, 3):
+                        batch = lib.irs_quasistatic_descent_batch_workspace_bytes(model, T, B)
+                        assert batch == (B * round256(g) if w > 0 else 0), (model, T, B)
+    # the forms the horizons above cover on both sides of LDS, and those that exist at all
+    assert lib.irs_tvlqr_box_workspace_bytes(QUAD, 50, 0) == 0 < lib.irs_tvlqr_box_workspace_bytes(QUAD, 80, 0)
+    assert lib.irs_quasistatic_descent_workspace_bytes(HAND, 50, 3) == 0
+    assert lib.irs_quasistatic_descent_workspace_bytes(HAND, 80, 3) > 0
+    assert lib.irs_box_records_bytes(HAND, 10, KIND_ADMM_DU) > 0 and lib.irs_box_records_bytes(HAND, 10, KIND_TILES) > 0
+    assert lib.irs_box_records_bytes(BICYCLE, 10, KIND_ADMM) == round256(10 * 74 * 8)   # one 74-double record per step
+
+
+def test_records_bytes_is_zero_where_nothing_is_placed(lib):
+    for T in (0, -3):
+        for kind in range(4):
+            assert lib.irs_box_records_bytes(HAND, T, kind) == 0
+    assert lib.irs_box_records_bytes(N_MODELS, 10, KIND_ADMM) == 0
+    assert lib.irs_box_records_bytes(-1, 10, KIND_TILES) == 0
+    assert lib.irs_box_records_bytes(HAND, 10, 4) == 0 and lib.irs_box_records_bytes(HAND, 10, -1) == 0
+    for model in (QUAD, BICYCLE, PENDULUM):           # not position controlled: no du form, no tile form
+        assert lib.irs_box_records_bytes(model, 10, KIND_ADMM_DU) == 0
+        assert lib.irs_box_records_bytes(model, 10, KIND_TILES) == 0
+    for model in (HAND, BOX_PIVOT, QUAD):             # the lanes keep everything on chip
+        for T in (1, 10, 50, 80, 200):
+            assert lib.irs_box_records_bytes(model, T, KIND_ACTIVE_SET) == 0
+
+
+def test_fused_iterate_checks_the_admm_settings_of_its_bounded_descents(lib):
+    """irs_iterate with bounds refuses ADMM settings the stand-alone bounded-descent entries refuse, with their code
+    and text: qp_relax outside (0, 2) (values <= 0 mean the default, so only >= 2 can be wrong).  Exact mode: the
+    call is rejected before any HIP call, so dummy addresses do."""
+    from irs_mpc_amd import _lib
+    one, T = 256, 8
+    c = _lib.IterateCall()
+    c.model, c.n_params = BICYCLE, 1
+    c.params[0] = 0.1
+    c.mode, c.T, c.N, c.n_descents, c.alpha_R = _lib.ITERATE_EXACT, T, 0, 1, 0.5
+    for name in ("Q", "Qd", "R", "xd_trj", "xlo", "xhi", "ulo", "uhi", "x_trj0", "u_trj0", "x_hist", "u_hist",
+                 "cost_hist", "info_hist", "scratch"):
+        setattr(c, name, one)
+    c.scratch_bytes = lib.irs_iterate_scratch_bytes(BICYCLE, _lib.ITERATE_EXACT, T, 0)
+    for relax in (2.0, 2.5, float("inf")):
+        c.qp_relax = relax
+        assert lib.irs_iterate(ctypes.byref(c), None, None) == -1, relax
+        assert lib.irs_last_error() == b"irs_tvlqr_box_descent_ifw: bad ADMM parameter"
+
+
 if __name__ == "__main__":
     # writes the golden table: run from a tree whose package and library predate the planner
     sys.path.insert(0, os.getcwd())

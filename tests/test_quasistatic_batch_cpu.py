@@ -174,3 +174,17 @@ def test_unsupported_parameter_lists_raise_not_implemented():
     ps[1].device_rng_seed = None
     with pytest.raises(NotImplementedError, match="device_rng_seed"):
         amd.IrsLqrQuasistaticBatch(q_dynamics, ps)
+
+
+def test_descent_failure_message():
+    """One function turns a descent's (info row, smoothing-failed flag) into None or the single class's ValueError
+    text; a failed smoothing solve wins over a failed QP, as in both loops."""
+    from irs_mpc_amd.irs_lqr_quasistatic import MSG_QP, MSG_SMOOTH, descent_failure
+    assert MSG_SMOOTH == "randomized-smoothing least squares is rank deficient"
+    assert MSG_QP == "TV_LQR failed. Optimization problem is not solved."
+    clean = np.array([0, 17, 0], np.int32)                # [1]: iterations used, not a failure
+    assert descent_failure(clean, False) is None
+    assert descent_failure(clean, np.bool_(True)) == MSG_SMOOTH
+    for bad in ([3, 0, 0], [0, 5, 2], [1, 1, 1]):         # Hessian not PD at t = 2; two tails at max_iter; both
+        assert descent_failure(np.array(bad, np.int32), False) == MSG_QP
+        assert descent_failure(np.array(bad, np.int32), True) == MSG_SMOOTH
