@@ -61,13 +61,23 @@ def _model_for(n, m, indices_u_into_x):
     return system.dm()
 
 
-def _rows(b, T_rows, width, dv):
-    """(lo, hi) per-time device rows from the reference's (2, rows, width) bound array."""
+def _checked_bound(name, b, T_rows, width):
+    """The bound array `name` as floats, (2, width) or (2, T_rows, width) -- the kernel reads exactly T_rows rows of
+    `width` entries; None passes through.  Anything else is a ValueError."""
+    if b is None:
+        return None
+    b = np.asarray(b, float)
+    if b.shape not in ((2, width), (2, T_rows, width)):
+        raise ValueError("solve_tvlqr: %s has shape %s, expected (2, %d) or (2, %d, %d)"
+                         % (name, b.shape, width, T_rows, width))
+    return b
+
+
+def _rows(b, T_rows, width):
+    """(lo, hi) per-time device rows from a checked (2, width) or (2, T_rows, width) bound array."""
     if b is None:
         return None, None
-    b = np.asarray(b, float)
-    lo = np.broadcast_to(b[0], (b[0].shape[0] if b[0].ndim == 2 else T_rows, width))[:T_rows]
-    hi = np.broadcast_to(b[1], (b[1].shape[0] if b[1].ndim == 2 else T_rows, width))[:T_rows]
+    lo, hi = np.broadcast_to(b[0], (T_rows, width)), np.broadcast_to(b[1], (T_rows, width))
     return dev.to_dev(np.array(lo, dtype=float, copy=True)), dev.to_dev(np.array(hi, dtype=float, copy=True))
 
 
@@ -79,6 +89,10 @@ def solve_tvlqr(At, Bt, ct, Q, Qd, R, x0, x_trj_d, solver=None, indices_u_into_x
     (extensions) tune the bounded solve."""
     At = np.asarray(At, float)
     T, n, m = At.shape[0], At.shape[1], np.asarray(Bt).shape[2]
+    # before anything goes to the device: the kernel reads T + 1 state rows and T control rows
+    x_bound_abs = _checked_bound("x_bound_abs", x_bound_abs, T + 1, n)
+    u_bound_abs = _checked_bound("u_bound_abs", u_bound_abs, T, m)
+    u_bound_rel = _checked_bound("u_bound_rel", u_bound_rel, T, m)
     At_d, Bt_d = dev.to_dev(At), dev.to_dev(np.asarray(Bt, float))
     ct_d = dev.to_dev(np.asarray(ct, float).reshape(T, -1))
     Q_d, Qd_d, R_d = dev.to_dev(np.asarray(Q, float)), dev.to_dev(np.asarray(Qd, float)), dev.to_dev(np.asarray(R, float))
@@ -99,17 +113,15 @@ def solve_tvlqr(At, Bt, ct, Q, Qd, R, x0, x_trj_d, solver=None, indices_u_into_x
         def inside(val, bnd, rows, skip=0):
             if bnd is None:
                 return True
-            b = np.asarray(bnd, float)
-            lo = np.broadcast_to(b[0], (rows,) + val.shape[1:]) if b[0].ndim == 1 else b[0][:rows]
-            hi = np.broadcast_to(b[1], (rows,) + val.shape[1:]) if b[1].ndim == 1 else b[1][:rows]
-            return bool((val[skip:rows] >= lo[skip:rows]).all() and (val[skip:rows] <= hi[skip:rows]).all())
+            lo, hi = (np.broadcast_to(b, (rows,) + val.shape[1:]) for b in bnd)
+            return bool((val[skip:rows] >= lo[skip:]).all() and (val[skip:rows] <= hi[skip:]).all())
 
         if inside(xs, x_bound_abs, T + 1, skip=1) and inside(us, u_bound_abs, T):
             return xs, us
     dm = _model_for(n, m, indices_u_into_x)
-    x_lo, x_hi = _rows(x_bound_abs, T + 1, n, dev)
-    u_lo, u_hi = _rows(u_bound_abs, T, m, dev)
-    du_lo, du_hi = _rows(u_bound_rel, T, m, dev) if position else (None, None)
+    x_lo, x_hi = _rows(x_bound_abs, T + 1, n)
+    u_lo, u_hi = _rows(u_bound_abs, T, m)
+    du_lo, du_hi = _rows(u_bound_rel, T, m) if position else (None, None)
     if not dm.box_descent_supported(T, du=position):
         raise NotImplementedError("solve_tvlqr with bounds: horizon T=%d is beyond the kernel's limit T <= %d"
                                   % (T, dm.box_horizon_limit(du=position)))
