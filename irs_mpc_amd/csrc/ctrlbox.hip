@@ -24,13 +24,11 @@
 // local_descent_quasistatic_as), checked there against the ADMM solution of the same QPs.
 //
 // One solver wave (+ one plant wave), f64, everything in (dynamic) LDS: a latency-bound chain like the Riccati pass.
-#include "boxqp.hpp"
-#include "wave.hpp"
+// The kinds of bound, the cap of phase 1 and the small rules of the setup are shared with the matrix-core form
+// (ctrlbox_mfma.hip) through ctrlbox_common.hpp; the plant wave and phase 2 are the same program in both files.
+#include "ctrlbox_common.hpp"
 
 namespace {
-
-constexpr int kPdasIter = 10;
-constexpr int KIND_ABS = 0, KIND_REL = 1;
 
 // LDS record of one time step (doubles).  Record T holds only P, p.
 template <int NR, int M>
@@ -84,17 +82,10 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
         if (KIND == KIND_ABS && i >= NR && j >= NR) return Rsym[(i - NR) * M + (j - NR)];
         return 0.0;
     };
-    auto wg_barrier = [&]() {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
-    // sentinels: a launch that does not reach its epilogue must not leave a previous launch's values
-    // behind (info = -1 is rejected by the host like any other failure; cost = NaN)
     // ---- the plant wave: barriers S0 (tables up), then per tail A (start state ready), B (control ready) ----
     if (wave == 1) {
         double xr[NR], ur[M], xn[NR], up[M], ub[M];
-        if (lane == 0 && a.cost) a.cost[0] = __builtin_nan("");
+        if (lane == 0 && a.cost) a.cost[0] = __builtin_nan("");      // sentinel, like info (ctrlbox_common.hpp)
 #pragma unroll
         for (int i = 0; i < NR; ++i) xr[i] = a.x0[i];
 #pragma unroll
@@ -173,9 +164,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
     }
 
     // ---- the solver wave: setup ----------------------------------------------------------
-    if (lane == 0) {
-        a.info[0] = -1; a.info[1] = -1; a.info[2] = -1;
-    }
+    ctrlbox_info_sentinel(a.info, lane);
     sym_part(Qsym, a.Q, NR, 0.5, lane);
     sym_part(Qdsym, a.Qd, NR, 0.5, lane);
     sym_part(Rsym, a.R, M, 0.5, lane);
@@ -185,9 +174,9 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
         tri[q] = (i << 8) | (i + r);
     }
     wave_sync();
-    const double* blo = KIND == KIND_ABS ? a.ulo : a.dlo;
-    const double* bhi = KIND == KIND_ABS ? a.uhi : a.dhi;
-    const int bs = KIND == KIND_ABS ? a.su : a.sd;
+    const double *blo, *bhi;
+    int bs;
+    ctrlbox_bounds_of<KIND>(a, blo, bhi, bs);
     for (int t = 0; t < T; ++t) {
         double* rec = rec_(t);
         for (int q = lane; q < NR * NR; q += 64) rec[L::oA + q] = a.At[(size_t)t * NR * NR + q];
@@ -203,11 +192,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
             const double hi_ = bhi ? bhi[(size_t)t * bs + lane] : INF;
             rec[L::olo + lane] = lo_;
             rec[L::ohi + lane] = hi_;
-            // warm start of the first tail (the previous iLQR iteration's converged set), cleaned:
-            // {-1, 0, +1}, and nothing pinned at an infinite bound
-            double a0 = a.act_io ? a.act_io[(size_t)t * M + lane] : 0.0;
-            a0 = a0 < 0.0 ? (lo_ > -INF ? -1.0 : 0.0) : (a0 > 0.0 ? (hi_ < INF ? 1.0 : 0.0) : 0.0);
-            rec[L::oact + lane] = a0;
+            rec[L::oact + lane] = ctrlbox_clean_warm(a.act_io ? a.act_io[(size_t)t * M + lane] : 0.0, lo_, hi_);
             rec[L::ou + lane] = 0.0;
             rec[L::ous + lane] = 0.0;
             rec[L::omu + lane] = 0.0;

@@ -32,8 +32,7 @@
 // LDS round trips and cross-lane traffic inside a step (ctrlbox.hip: 6 LDS phases, ~7000 cycles per
 // backward step; here ~2300 measured with in-kernel cycle stamps: 9 MFMAs at 64-108 cycles each in a
 // dependent chain, ~700 cycles to gather H into every lane, ~200 for the masked inverse).
-#include "boxqp.hpp"
-#include "wave.hpp"
+#include "ctrlbox_common.hpp"
 
 namespace {
 
@@ -42,8 +41,7 @@ namespace {
 // prefetch of the next step's data (measured: 1.8 us per backward step instead of ~0.5)
 typedef const __attribute__((address_space(1))) double* gptr_d;
 
-constexpr int kPdasIterM = 10;
-// Primal-dual iterations that did not settle in kPdasIterM rounds are CYCLING (rate-limited problems: a component
+// Primal-dual iterations that did not settle in kPdasIter rounds are CYCLING (rate-limited problems: a component
 // released from one bound shoots past the other one in the next round, and a whole bang-bang stretch flips with it).
 // Before falling back to the primal method -- one constraint per iteration: 50-140 iterations for such a tail, each a
 // sweep of up to the whole horizon; 3 of 80 tails like that were two thirds of a box-pivoting descent -- the
@@ -52,12 +50,11 @@ constexpr int kPdasIterM = 10;
 // twin on inputs dumped from the device, tests/tools/pdas_study.py): backward steps of the descents that used to fall
 // back 13 641 -> 4 880, 10 210 -> 1 900, 24 122 -> 15 150; descents that never cycled are unchanged.  The QP is
 // strictly convex: whichever rule finds the optimal set finds the same solution.
-constexpr int kPdasSingleM = 50;
+constexpr int kPdasSingle = 50;
 #ifndef IRS_LAZY_MIN
 #define IRS_LAZY_MIN 6
 #endif
 constexpr int kLazyPrefixMin = IRS_LAZY_MIN;   // shortest fully pinned head that is left out of the inner sweeps
-constexpr int KIND_ABS_M = 0, KIND_REL_M = 1;
 
 // Batched launch: how far problem b's data lie from problem 0's -- element strides of the per-problem arrays of
 // BoxArgs (bnd: the bound rows of the launch's kind), a byte stride of the record workspace.  A single-problem
@@ -178,17 +175,12 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
         __builtin_amdgcn_wave_barrier();
     };
 
-    auto wg_barrier = [&]() {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
 
     // ---- the plant wave ------------------------------------------------------------------
     // barriers: S0 (the solver's tables are up), then per tail A (start state ready) and B (control ready)
     if (wave == 1) {
         double xr[NR], ur[M], xn[NR], up[M], ub[M];
-        // sentinel, like info (ctrlbox.hip); stored as a bit pattern: this file is compiled with -fno-honor-nans
+        // sentinel, like info (ctrlbox_common.hpp); stored as a bit pattern: this file is compiled with -fno-honor-nans
         if (lane == 0 && a.cost) *reinterpret_cast<unsigned long long*>(a.cost) = 0x7ff8000000000000ull;
 #pragma unroll
         for (int i = 0; i < NR; ++i) xr[i] = a.x0[i];
@@ -252,7 +244,7 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
             irs_step_along_prepare<Model>(a.p, xr, warm, pre);
             wg_barrier();                                   // B(tau): uctl holds the tail's first control
 #pragma unroll
-            for (int j = 0; j < M; ++j) ur[j] = KIND == KIND_ABS_M ? uctl[j] : ub[j] + uctl[j];
+            for (int j = 0; j < M; ++j) ur[j] = KIND == KIND_ABS ? uctl[j] : ub[j] + uctl[j];
 #pragma unroll
             for (int j = 0; j < M; ++j) dv[j] = ur[j] - (tau == 0 ? ub[j] : up[j]);
 #pragma unroll
@@ -276,25 +268,20 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
     }
 
     // ---- the solver wave: setup ----------------------------------------------------------
-    if (lane == 0) {
-        a.info[0] = -1; a.info[1] = -1; a.info[2] = -1;     // sentinels: see ctrlbox.hip
-    }
+    ctrlbox_info_sentinel(a.info, lane);
     sym_part(Qsym, a.Q, NR, 0.5, lane);
     sym_part(Qdsym, a.Qd, NR, 0.5, lane);
     sym_part(Rsym, a.R, M, 0.5, lane);
     wave_sync();
-    const double* blo = KIND == KIND_ABS_M ? a.ulo : a.dlo;
-    const double* bhi = KIND == KIND_ABS_M ? a.uhi : a.dhi;
-    const int bs = KIND == KIND_ABS_M ? a.su : a.sd;
+    const double *blo, *bhi;
+    int bs;
+    ctrlbox_bounds_of<KIND>(a, blo, bhi, bs);
     for (int q = lane; q < T * M; q += 64) {
         const double lo = blo ? blo[(size_t)(q / M) * bs + q % M] : -INF;
         const double hi = bhi ? bhi[(size_t)(q / M) * bs + q % M] : INF;
         lo_[q] = lo;
         hi_[q] = hi;
-        // warm start of the first tail (the previous iLQR iteration's converged set), cleaned:
-        // {-1, 0, +1}, and nothing pinned at an infinite bound
-        double a0 = a.act_io ? a.act_io[q] : 0.0;
-        a0 = a0 < 0.0 ? (lo > -INF ? -1.0 : 0.0) : (a0 > 0.0 ? (hi < INF ? 1.0 : 0.0) : 0.0);
+        const double a0 = ctrlbox_clean_warm(a.act_io ? a.act_io[q] : 0.0, lo, hi);
         act_[q] = a0;
         bnd_[q] = a0 < 0.0 ? lo : hi;
         uu_[q] = 0.0; us_[q] = 0.0; mu_[q] = 0.0;
@@ -316,7 +303,7 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
         double v = 0.0;
         if (row < NR && col < NR) v = Qsym[row * NR + col];
         else if (row >= NHP && row < NHP + M && col >= NHP && col < NHP + M) v = Ru(row - NHP, col - NHP);
-        if (KIND == KIND_ABS_M) {
+        if (KIND == KIND_ABS) {
             // (u - w)'R(u - w): R on the w block, -R between w and u
             if (row >= NR && row < NS && col >= NR && col < NS) v = Ru(row - NR, col - NR);
             else if (row >= NR && row < NS && col >= NHP && col < NHP + M) v = -Ru(row - NR, col - NHP);
@@ -358,11 +345,11 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
             if (row < NR) {
                 if (col < NR) { fp[r] = gA + row * NR + col; fstr[r] = NR * NR; fld[r] = true; }
                 else if (col < NS) {
-                    if (KIND == KIND_REL_M) { fp[r] = gB + row * M + (col - NR); fstr[r] = NR * M; fld[r] = true; }
+                    if (KIND == KIND_REL) { fp[r] = gB + row * M + (col - NR); fstr[r] = NR * M; fld[r] = true; }
                 } else if (col == NS) { fp[r] = gc_ + row; fstr[r] = NR; fld[r] = true; }
                 else if (col >= NHP && col < NHP + M) { fp[r] = gB + row * M + (col - NHP); fstr[r] = NR * M; fld[r] = true; }
             } else if (row < NS) {
-                if (KIND == KIND_REL_M && col == row) fc[r] = 1.0;
+                if (KIND == KIND_REL && col == row) fc[r] = 1.0;
                 else if (col == NHP + (row - NR)) fc[r] = 1.0;
             } else if (row == NS && col == NS) {
                 fc[r] = 1.0;
@@ -1032,16 +1019,16 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
             }
             return pe;
         };
-        for (int it = 0; it < kPdasIterM + kPdasSingleM && !conv; ++it) {
+        for (int it = 0; it < kPdasIter + kPdasSingle && !conv; ++it) {
             ++iters;
-            const bool single = it >= kPdasIterM;          // release the worst pinned component only
+            const bool single = it >= kPdasIter;          // release the worst pinned component only
             // (a short run is not worth an extra rollout and a later release: measured on the rate-limited box
             // problem, where skipping 1-3 steps cost more iterations than it saved sweeps)
             int pe = t0 - 1;
             // Trust-region (ABS) problems only: their tails start with a long saturated head.  Rate-limited (REL)
             // ones rarely do, and deferring the few releases there costs iterations (measured on the benchmark's
             // box-pivoting loop: 206 -> 187 iterations/s with it, planar hand trust region 579 -> 596).
-            if (KIND == KIND_ABS_M && max(t_dirty, stale_hi) >= t0) {   // (nothing to sweep: no need to know)
+            if (KIND == KIND_ABS && max(t_dirty, stale_hi) >= t0) {   // (nothing to sweep: no need to know)
                 pe = prefix_end();
                 if (pe - t0 + 1 < kLazyPrefixMin) pe = t0 - 1;
             }
@@ -1050,7 +1037,7 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                 if (hi >= lo) backward_sweep(hi, lo);
                 if (hi >= t0) stale_hi = lo - 1;       // what was dirty below lo stays so
             }
-            policy_rollout(t0, uu_, T, KIND == KIND_ABS_M);
+            policy_rollout(t0, uu_, T, KIND == KIND_ABS);
             int chg = -1;
             double rworst = 0.0;
             int rq = 0x7fffffff;
@@ -1292,14 +1279,14 @@ int irs_ctrlbox_mfma_launch(int model, const BoxArgs& a, int kind, const BoxPlan
     IRS_DISPATCH_MODEL(model, {
         if constexpr (has_u_into_x<Model>::value) {
             if constexpr (MfLayout<Model::NX, Model::NU>::FITS) {
-                const bool abs = kind == KIND_ABS_M;
+                const bool abs = kind == KIND_ABS;
                 if (batch_B > 0) {
                     const BoxBatch bs = box_batch_strides<Model>(a.T, ws_stride);
-                    rc = abs ? launch_ctrlbox_mfma<Model, KIND_ABS_M>(a, p, ws, batch_B, bs, st)
-                             : launch_ctrlbox_mfma<Model, KIND_REL_M>(a, p, ws, batch_B, bs, st);
+                    rc = abs ? launch_ctrlbox_mfma<Model, KIND_ABS>(a, p, ws, batch_B, bs, st)
+                             : launch_ctrlbox_mfma<Model, KIND_REL>(a, p, ws, batch_B, bs, st);
                 } else {
-                    rc = abs ? launch_ctrlbox_mfma<Model, KIND_ABS_M>(a, p, ws, 1, BoxSolo{}, st)
-                             : launch_ctrlbox_mfma<Model, KIND_REL_M>(a, p, ws, 1, BoxSolo{}, st);
+                    rc = abs ? launch_ctrlbox_mfma<Model, KIND_ABS>(a, p, ws, 1, BoxSolo{}, st)
+                             : launch_ctrlbox_mfma<Model, KIND_REL>(a, p, ws, 1, BoxSolo{}, st);
                 }
             }
         }

@@ -1,7 +1,7 @@
-// Single-wave f64 primitives of the descent kernels (tvlqr.hip, boxqp.hip, ctrlbox.hip, ctrlbox_mfma.hip, iterate.hip).
+// Wave-level primitives of the descent kernels (tvlqr.hip, boxqp.hip, ctrlbox.hip, ctrlbox_mfma.hip, iterate.hip).
 // Every one of these kernels is one 64-lane wave walking a latency-bound chain (the active-set descents: one solver
-// wave plus one plant wave); the helpers below are what such a wave needs between its lanes.  (The sample pass has its
-// own set in smooth_common.hpp.)
+// wave plus one plant wave, meeting at wg_barrier); the helpers below are what such a wave needs between its lanes.
+// (The sample pass has its own set in smooth_common.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,14 @@ typedef double v4d __attribute__((ext_vector_type(4)));      // operand / accumu
 __device__ __forceinline__ void wave_sync() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
+}
+
+// Workgroup barrier between the solver wave and the plant wave of the active-set descents: everything this wave has
+// written (LDS and global) is complete before it arrives, and nothing of what follows is moved ahead of it.
+__device__ __forceinline__ void wg_barrier() {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
 }
 
 // 1/d to ~1 ulp: hardware reciprocal + two Newton steps (a correctly rounded f64 divide

@@ -1543,7 +1543,7 @@ def ctrlbox_solve(prob, s_start, t0, lo, hi, u, act, W, valid_from, pdas_iter=10
       phase 1: primal-dual active-set iterations (Hintermueller-Ito-Kunisch): all violated bounds
                are pinned and all wrong-signed multipliers released at once; converges in a handful
                of iterations when it converges, but may cycle;
-      phase 1b (iterations pdas_iter+1 .. pdas_iter+single_iter, round 3; csrc/ctrlbox_mfma.hip kPdasSingleM): the
+      phase 1b (iterations pdas_iter+1 .. pdas_iter+single_iter, round 3; csrc/ctrlbox_mfma.hip kPdasSingle): the
                same with a damped release rule -- all violated bounds pinned, only the ONE pinned component with
                the worst multiplier released -- which ends the cycles of rate-limited (bang-bang) tails;
       phase 2 (after that): classic primal active-set from the clipped iterate --

@@ -1635,11 +1635,9 @@ def test_quasistatic_descent_long_horizon(amd, T, kind):
     np.testing.assert_allclose(float(o["cost"].item()), orc.eval_cost_quasistatic(xa, ua, xd, Q, Qd, R, idx), rtol=1e-8)
 
 
-@pytest.mark.parametrize("seed", [1, 2, 3, 4])
-def test_quasistatic_active_set_random_problems(amd, seed, as_solver):
-    """The active-set descent on randomised planar-hand problems (nominal trajectory, goal, bound
-    widths, cost weights): device == oracle twin, both kinds, including tails that need the primal
-    safeguard."""
+def _random_hand_problem(amd, seed):
+    """A randomised planar-hand problem (nominal trajectory, goal, bound width, cost weights) and a function that
+    runs the device's and the oracle's active-set descent on it with that width as bounds of one kind."""
     from irs_mpc_amd import device as dev
     rng = np.random.default_rng(100 + seed)
     T = int(rng.integers(12, 30))
@@ -1655,7 +1653,8 @@ def test_quasistatic_active_set_random_problems(amd, seed, as_solver):
                  (T + 1, 1))
     w = rng.uniform(0.01, 0.08)
     dm = sys_d.dm()
-    for kind in ("abs", "rel"):
+
+    def solve(kind, solver):
         ub = np.array([-np.ones(4) * w, np.ones(4) * w]) if kind == "abs" else None
         rb = np.array([-np.ones(4) * w, np.ones(4) * w]) if kind == "rel" else None
         rows = orc.quasistatic_bounds(x_trj, idx, None, ub, rb)
@@ -1664,12 +1663,41 @@ def test_quasistatic_active_set_random_problems(amd, seed, as_solver):
         assert all(st[1] >= 0 for st in stats)
         kw = dict(u_lo=dev.to_dev(lo), u_hi=dev.to_dev(hi)) if kind == "abs" else \
             dict(du_lo=dev.to_dev(lo), du_hi=dev.to_dev(hi))
-        o = dm.quasistatic_box_descent(*[dev.to_dev(a) for a in (At, Bt, ct, Q, Qd, R, xd, x0)], solver=as_solver,
+        o = dm.quasistatic_box_descent(*[dev.to_dev(a) for a in (At, Bt, ct, Q, Qd, R, xd, x0)], solver=solver,
                                        max_iter=2000, eps=1e-10, **kw)
+        return o, xa, ua
+
+    return solve
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3, 4])
+def test_quasistatic_active_set_random_problems(amd, seed, as_solver):
+    """The active-set descent on randomised planar-hand problems (nominal trajectory, goal, bound
+    widths, cost weights): device == oracle twin, both kinds, including tails that need the primal
+    safeguard."""
+    solve = _random_hand_problem(amd, seed)
+    for kind in ("abs", "rel"):
+        o, xa, ua = solve(kind, as_solver)
         info = o["info"].cpu().numpy()
         assert info[0] == 0 and info[2] == 0, (kind, info)
         np.testing.assert_allclose(o["u_new"].cpu().numpy(), ua, rtol=0, atol=1e-8, err_msg=kind)
         np.testing.assert_allclose(o["x_new"].cpu().numpy(), xa, rtol=0, atol=1e-8, err_msg=kind)
+
+
+def test_quasistatic_active_set_primal_fallback(amd, as_solver):
+    """A rate-limited problem of the same generator whose primal-dual rounds cycle for long enough that BOTH kernels
+    fall back to the primal active-set method (csrc/ctrlbox_common.hpp, ctrlbox_primal_phase): the lanes kernel after
+    its 10 rounds, the tiles kernel after its 10 + 50 (the damped rule ends most cycles: few of the generator's
+    problems outlast it in the oracle twin, oracle/irs_oracle.py ctrlbox_solve; this one does in its first tail).
+    info[1], the largest iteration count of a tail, says that the fallback ran; it converges (info[2] == 0) to the
+    oracle's trajectory."""
+    solve = _random_hand_problem(amd, 62)
+    o, xa, ua = solve("rel", as_solver)
+    info = o["info"].cpu().numpy()
+    assert info[0] == 0 and info[2] == 0, info
+    assert info[1] > (10 if as_solver == 2 else 60), info
+    np.testing.assert_allclose(o["u_new"].cpu().numpy(), ua, rtol=0, atol=1e-8)
+    np.testing.assert_allclose(o["x_new"].cpu().numpy(), xa, rtol=0, atol=1e-8)
 
 
 # ---------------------------------------------------------------- box pivoting (BASELINE configs[4] model, unpinned)
