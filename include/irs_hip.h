@@ -150,6 +150,32 @@ int irs_sums_len(int model, int mode);
 /* Bytes of DEV scratch the irs_smooth* calls need for (T, N) (T <= 1024).        */
 size_t irs_smooth_workspace_bytes(int model, int mode, int T, int N);
 
+/* The launch geometry the irs_smooth* calls use for (model, mode, T, N); rng != 0: device-drawn samples.  Makes
+ * no launch and needs no device.  The sample pass launches exactly what this reports (one planner, csrc/smooth.hip:
+ * smooth_geometry); like the launch it honours IRS_UG, read per call.  out[]:
+ *   [0] family (irs_smooth_family): which sample loop runs
+ *   [1] block   threads per workgroup        [2] nblk  workgroups per timestep (grid = nblk x T)
+ *   [3] chunk0  samples of workgroup 0       [4] chunk samples of every later workgroup: workgroup b >= 1 owns
+ *       [chunk0 + (b-1) chunk, chunk0 + b chunk) cut at N -- possibly empty.  Both 0 for the uniform-geometry
+ *       family, which deals 64-sample blocks round robin to the nblk x 8 waves of a timestep instead
+ *   [5] wg0_rr  trips of workgroup 0 dealt to all four of its waves before the last one sits out (INT_MAX: never)
+ *   [6] branch (irs_smooth_plan): which contact re-planning set chunk0 / chunk      [7] 0 (reserved)           */
+typedef enum {
+    IRS_SMOOTH_FAMILY_LANES_LIGHT = 0,       /* strided lanes; 1024 threads and four samples per lane per trip when
+                                                the samples are supplied and N is small                          */
+    IRS_SMOOTH_FAMILY_LANES_HEAVY = 1,       /* strided lanes, one sample per trip, next row prefetched          */
+    IRS_SMOOTH_FAMILY_GRAM_MATRIX_CORE = 2,  /* a wave per 64 samples, Gram by MFMA                              */
+    IRS_SMOOTH_FAMILY_CONTACT_WAVE_DEALT = 3,/* contact step per lane, 64-sample blocks dealt to waves           */
+    IRS_SMOOTH_FAMILY_CONTACT_PARKED = 4,    /* the same deal + unfinished samples parked in a per-wave ring     */
+    IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY = 5   /* csrc/smooth_ug.hip                                               */
+} irs_smooth_family;
+typedef enum {
+    IRS_SMOOTH_PLAN_NONE = 0,   /* chunk0 == chunk                                                               */
+    IRS_SMOOTH_PLAN_TRIPS = 1,  /* balanced by 64-sample wave trips (wg0_rr finite)                              */
+    IRS_SMOOTH_PLAN_COST = 2    /* workgroup 0 gives up a fixed number of samples per lane                       */
+} irs_smooth_plan;
+int irs_smooth_geometry(int model, int mode, int T, int N, int rng, int out[8]);
+
 /* Zeroes the arrival counters at the head of a freshly allocated workspace.  Call
  * once per allocation; every irs_smooth* call leaves them zero again.  One call in
  * flight per workspace at a time.                                                */

@@ -27,6 +27,10 @@ MODEL_BOX_PUSH_EXACT = 10
 SMOOTH_ZERO_ORDER_AB = 0
 SMOOTH_FIRST_ORDER = 1
 SMOOTH_ZERO_ORDER_B = 2
+# irs_smooth_geometry: out[0] (irs_smooth_family) and out[6] (irs_smooth_plan)
+SMOOTH_FAMILIES = ("lanes_light", "lanes_heavy", "gram_matrix_core", "contact_wave_dealt", "contact_parked",
+                   "uniform_geometry")
+SMOOTH_PLANS = ("none", "trips", "cost")
 BOX_ADMM, BOX_ADMM_DU, BOX_ACTIVE_SET, BOX_ACTIVE_SET_MFMA = 0, 1, 2, 3     # irs_box_horizon_limit kinds
 
 _dp = c_void_p   # device pointers travel as plain addresses
@@ -43,6 +47,7 @@ SIGNATURES = {
     "irs_evaluate_cost": (c_int, [c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_void_p]),
     "irs_sums_len": (c_int, [c_int, c_int]),
     "irs_smooth_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "irs_smooth_geometry": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "irs_workspace_init": (c_int, [_dp, c_size_t, c_void_p]),
     "irs_smooth": (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, c_int, _dp, _dp, _dp, _dp,
                            _dp, _dp, _dp, _dp, _dp, _dp, c_size_t, c_void_p]),

@@ -21,6 +21,9 @@
 //   With several GPUs step 4 is a separate launch (smooth_finalize_kernel) after the
 //   all-reduce of `sums`.
 //
+// Which lane reads which sample is planned on the host in ONE place, smooth_geometry() below (reported by
+// irs_smooth_geometry, restated loop by loop in oracle/smooth_cases.py).
+//
 // Inter-workgroup hand-off follows cdna_hip_programming.md Guideline 16: partials are
 // stored sc1 (agent-scope relaxed atomic stores), every storing wave drains vmcnt, the
 // workgroup barriers, one lane adds to the counter; the consumer does one agent-scope
@@ -33,6 +36,12 @@ template <class Model, int MODE>
 constexpr bool defer_samples() {
     return irs_contact_exact<Model>::value && MODE != IRS_SMOOTH_ZERO_ORDER_AB && contact_rows<Model>() <= 8;
 }
+// the matrix-core Gram loop (256-thread workgroups): zero-order, one 16-wide tile, too many statistics for registers
+template <class Model, int MODE>
+constexpr bool gram_on_matrix_cores() {
+    using TR = SmoothTraits<Model, MODE>;
+    return MODE == IRS_SMOOTH_ZERO_ORDER_AB && TR::d <= 16 && TR::n <= 16 && TR::PP > 64;
+}
 // the f64 nominal step of workgroup 0 costs its wave about this many sample trips (parked-sample kernels)
 constexpr int kNominalTrips = 2;
 
@@ -43,9 +52,7 @@ __global__ __launch_bounds__(BLOCK, (smooth_min_waves<Model, MODE>())) void smoo
     using TR = SmoothTraits<Model, MODE>;
     constexpr int n = TR::n, m = TR::m, d = TR::d, NZ = TR::NZ, Z0 = TR::Z0, P = TR::P;
     constexpr int NW = BLOCK / 64;
-    // matrix-core Gram path: zero-order, one 16-wide tile, too many statistics for registers
-    constexpr bool USE_MFMA = MODE == IRS_SMOOTH_ZERO_ORDER_AB && d <= 16 && n <= 16 && TR::PP > 64 &&
-                              BLOCK == kBlock;
+    constexpr bool USE_MFMA = gram_on_matrix_cores<Model, MODE>() && BLOCK == kBlock;
     // exact contact models in the lane path: unfinished samples wait in a per-wave ring (see the DEFER branch)
     // Used by the u-only modes of the 8-row models (planar hand, T = 50: zero-order-B 102 -> 79 us at N = 1e4 and
     // 820 -> 606 us at 1e5; first-order 112 -> 76 us).  Measured and left on the plain path: the 12-row box models --
@@ -671,7 +678,7 @@ bool uses_parked_samples(int model, int mode) {
 }
 
 int nominal_trips(int model, int mode) {
-    static int ov = env_int("IRS_NOMINAL_TRIPS", -1);
+    static int ov = env_int("IRS_NOMINAL_TRIPS", -1);      // (env_int clamps to >= 1: unset, this is 1 -- DESIGN section 7)
     if (ov >= 0) return ov;
     (void)model; (void)mode;
     return kNominalTrips;      // measured: 1-3 trips are equal for every contact kernel (planar hand exact / sweeps /
@@ -741,6 +748,79 @@ struct SmoothOut {   // finalize outputs; all null = accumulate only
     double* At; double* Bt; double* ct; int* info; long long n_total;
 };
 
+// The launch geometry of one sample pass: the ONE statement of which kernel family runs (T, N) and how its samples
+// are split over workgroups.  smooth_common launches what this returns; irs_smooth_geometry reports it.
+struct SmoothGeometry {
+    int family;      // IRS_SMOOTH_FAMILY_*
+    int block, nblk; // threads per workgroup, workgroups per timestep
+    int chunk0, chunk, wg0_rr;   // SmoothArgs (0, 0, INT_MAX for the uniform-geometry family: it deals 64-sample blocks)
+    int branch;      // IRS_SMOOTH_PLAN_*: which contact re-planning set chunk0 / chunk
+};
+
+bool uses_matrix_cores(int model, int mode) {
+    if (mode != IRS_SMOOTH_ZERO_ORDER_AB) return false;
+    bool r = false;
+    IRS_DISPATCH_MODEL(model, { r = gram_on_matrix_cores<Model, IRS_SMOOTH_ZERO_ORDER_AB>(); });
+    return r;
+}
+
+int smooth_geometry(int model, int mode, int T, int N, bool rng, SmoothGeometry* g) {
+    IRS_CHECK_ARG(T > 0 && N > 0, "T and N must be positive");
+    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
+    if (irs_sums_len(model, mode) <= 0) return IRS_ERR_UNSUPPORTED;
+    g->branch = IRS_SMOOTH_PLAN_NONE;
+    g->wg0_rr = 0x7fffffff;
+    if (irs_smooth_ug_supported(model, mode)) {
+        // exact 8-row contact model, u-only mode: the uniform-geometry pass (smooth_ug.hip)
+        g->family = IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY;
+        g->nblk = irs_smooth_ug_nblk(T, N);
+        g->block = 512;
+        g->chunk = g->chunk0 = 0;
+        return IRS_OK;
+    }
+    const bool contact = has_nominal_in_wg0(model, mode);
+    plan_grid(T, N, is_light(model, mode), rng, &g->chunk, &g->nblk, &g->block, contact);
+    g->chunk0 = g->chunk;
+    g->family = is_light(model, mode) ? IRS_SMOOTH_FAMILY_LANES_LIGHT      // four samples per lane per trip when supplied
+                : uses_matrix_cores(model, mode) ? IRS_SMOOTH_FAMILY_GRAM_MATRIX_CORE
+                : uses_parked_samples(model, mode) ? IRS_SMOOTH_FAMILY_CONTACT_PARKED
+                : contact ? IRS_SMOOTH_FAMILY_CONTACT_WAVE_DEALT : IRS_SMOOTH_FAMILY_LANES_HEAVY;
+    bool planned = false;
+    if (g->nblk >= 2 && g->block == kBlock && contact) {
+        // contact kernels balance by WAVE trips (64 samples): B blocks plus the nominal step's kNominalTrips
+        // over 4 nblk waves -> tt trips each; workgroup 0: tt - kNominalTrips rounds over its four waves, then
+        // kNominalTrips rounds over three.  (Chunks rounded to whole workgroup trips, as below, left three of the
+        // five workgroups of the benchmark's N = 1e4 with 9 trips and one with 5 + the nominal step.)
+        const int NW = kBlock / 64, B = (N + 63) / 64, nw = g->nblk * NW;
+        const int kNom = nominal_trips(model, mode);
+        const int tt = (B + kNom + nw - 1) / nw, rr = tt - kNom;
+        if (rr >= 1) {
+            const int c0b = NW * rr + (NW - 1) * kNom;
+            const int restb = B > c0b ? (B - c0b + (g->nblk - 1) - 1) / (g->nblk - 1) : 0;
+            if (restb <= NW * tt) {
+                g->chunk0 = c0b * 64;
+                g->chunk = restb > 0 ? restb * 64 : 64;
+                g->wg0_rr = rr;
+                g->branch = IRS_SMOOTH_PLAN_TRIPS;
+                planned = true;
+            }
+        }
+    }
+    if (!planned && g->nblk >= 2 && g->block == kBlock && contact) {
+        // workgroup 0 gives up kNominalCost samples per lane and evaluates the f64 nominal step
+        int c0 = g->chunk - kNominalCost * kBlock;
+        if (c0 < kBlock) c0 = kBlock;
+        int rest = (N - c0 + (g->nblk - 1) - 1) / (g->nblk - 1);
+        rest = (rest + kBlock - 1) / kBlock * kBlock;
+        if (c0 < g->chunk && c0 + (long long)(g->nblk - 1) * rest >= N && rest <= g->chunk + kBlock) {
+            g->chunk0 = c0;
+            g->chunk = rest;
+            g->branch = IRS_SMOOTH_PLAN_COST;
+        }
+    }
+    return IRS_OK;
+}
+
 int smooth_common(int model, const double* params, int n_params, int mode, int T, int N,
                   const double* x_trj, const double* u_trj, SmoothArgs& a, bool rng, double* sums,
                   const SmoothOut* out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -757,12 +837,12 @@ int smooth_common(int model, const double* params, int n_params, int mode, int T
     }
     a.x_trj = x_trj; a.u_trj = u_trj;
     a.T = T; a.N = N;
-    if (irs_smooth_ug_supported(model, mode)) {
+    SmoothGeometry g;
+    rc = smooth_geometry(model, mode, T, N, rng, &g);
+    if (rc != IRS_OK) return rc;
+    a.block = g.block; a.nblk = g.nblk; a.chunk0 = g.chunk0; a.chunk = g.chunk; a.wg0_rr = g.wg0_rr;
+    if (g.family == IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY) {
         // exact 8-row contact model, u-only mode: the uniform-geometry pass (smooth_ug.hip)
-        a.nblk = irs_smooth_ug_nblk(T, N);
-        a.block = 512;
-        a.chunk = a.chunk0 = 0;
-        a.wg0_rr = 0x7fffffff;
         a.diag = getenv("IRS_DIAG") ? atoi(getenv("IRS_DIAG")) : 0;      // timing experiments only
         a.counters = static_cast<int*>(workspace);
         a.fnom = reinterpret_cast<double*>(static_cast<char*>(workspace) + kCounterBytes);
@@ -777,40 +857,6 @@ int smooth_common(int model, const double* params, int n_params, int mode, int T
         if (rc != IRS_OK) return rc;
         IRS_CHECK_LAUNCH();
         return IRS_OK;
-    }
-    plan_grid(T, N, is_light(model, mode), rng, &a.chunk, &a.nblk, &a.block, has_nominal_in_wg0(model, mode));
-    a.chunk0 = a.chunk;
-    a.wg0_rr = 0x7fffffff;
-    bool planned = false;
-    if (a.nblk >= 2 && a.block == kBlock && has_nominal_in_wg0(model, mode)) {
-        // contact kernels balance by WAVE trips (64 samples): B blocks plus the nominal step's kNominalTrips
-        // over 4 nblk waves -> tt trips each; workgroup 0: tt - kNominalTrips rounds over its four waves, then
-        // kNominalTrips rounds over three.  (Chunks rounded to whole workgroup trips, as below, left three of the
-        // five workgroups of the benchmark's N = 1e4 with 9 trips and one with 5 + the nominal step.)
-        const int NW = kBlock / 64, B = (N + 63) / 64, nw = a.nblk * NW;
-        const int kNom = nominal_trips(model, mode);
-        const int tt = (B + kNom + nw - 1) / nw, rr = tt - kNom;
-        if (rr >= 1) {
-            const int c0b = NW * rr + (NW - 1) * kNom;
-            const int restb = B > c0b ? (B - c0b + (a.nblk - 1) - 1) / (a.nblk - 1) : 0;
-            if (restb <= NW * tt) {
-                a.chunk0 = c0b * 64;
-                a.chunk = restb > 0 ? restb * 64 : 64;
-                a.wg0_rr = rr;
-                planned = true;
-            }
-        }
-    }
-    if (!planned && a.nblk >= 2 && a.block == kBlock && has_nominal_in_wg0(model, mode)) {
-        // workgroup 0 gives up kNominalCost samples per lane and evaluates the f64 nominal step
-        int c0 = a.chunk - kNominalCost * kBlock;
-        if (c0 < kBlock) c0 = kBlock;
-        int rest = (N - c0 + (a.nblk - 1) - 1) / (a.nblk - 1);
-        rest = (rest + kBlock - 1) / kBlock * kBlock;
-        if (c0 < a.chunk && c0 + (long long)(a.nblk - 1) * rest >= N && rest <= a.chunk + kBlock) {
-            a.chunk0 = c0;
-            a.chunk = rest;
-        }
     }
     { static int dg = getenv("IRS_DIAG") ? atoi(getenv("IRS_DIAG")) : 0; a.diag = dg; }
     a.counters = static_cast<int*>(workspace);
@@ -880,6 +926,16 @@ size_t irs_smooth_workspace_bytes(int model, int mode, int T, int N) {
         if (ug > nblk) nblk = ug;
     }
     return kCounterBytes + fnom_bytes(T) + (size_t)T * nblk * ((P + 3) / 4 * 4) * sizeof(float);
+}
+
+int irs_smooth_geometry(int model, int mode, int T, int N, int rng, int out[8]) {
+    IRS_CHECK_ARG(out != nullptr, "null pointer");
+    SmoothGeometry g;
+    int rc = smooth_geometry(model, mode, T, N, rng != 0, &g);
+    if (rc != IRS_OK) return rc;
+    out[0] = g.family; out[1] = g.block; out[2] = g.nblk; out[3] = g.chunk0; out[4] = g.chunk; out[5] = g.wg0_rr;
+    out[6] = g.branch; out[7] = 0;
+    return IRS_OK;
 }
 
 int irs_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {

@@ -46,6 +46,16 @@ def to_dev(a, dtype=F64):
     return torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
 
 
+def smooth_geometry(model_id, mode, T, N, rng=False):
+    """The launch geometry of the sample pass for (model, mode, T, N) (irs_smooth_geometry): no launch, no device.
+    dict(family, block, nblk, chunk0, chunk, wg0_rr, branch), family / branch by name (_lib.SMOOTH_FAMILIES / _PLANS)."""
+    out = (ctypes.c_int * 8)()
+    check(_lib.load().irs_smooth_geometry(int(model_id), int(mode), int(T), int(N), int(bool(rng)), out),
+          "irs_smooth_geometry")
+    return dict(family=_lib.SMOOTH_FAMILIES[out[0]], block=out[1], nblk=out[2], chunk0=out[3], chunk=out[4],
+                wg0_rr=out[5], branch=_lib.SMOOTH_PLANS[out[6]])
+
+
 class DeviceModel:
     """A registered device functor (irs_model_id) with its constants bound."""
 
@@ -107,6 +117,9 @@ class DeviceModel:
     # ---- smoothing --------------------------------------------------------
     def sums_len(self, mode):
         return self.lib.irs_sums_len(self.model_id, mode)
+
+    def smooth_geometry(self, mode, T, N, rng=False):
+        return smooth_geometry(self.model_id, mode, T, N, rng)
 
     def _workspace(self, mode, T, N, device):
         need = self.lib.irs_smooth_workspace_bytes(self.model_id, mode, T, N)

@@ -1803,6 +1803,9 @@ def test_quasistatic_descent_outputs_are_self_consistent(amd, system, solver, T,
     np.testing.assert_allclose(float(out["cost"].item()), orc.eval_cost_quasistatic(xn, un, xd, Q, Qd, R, idx), rtol=1e-10)
 
 
+GRAM_F32_BOUND = 2.1e-6        # 4 x the 5.18e-7 measured on an MI355X (N = 3000 Gaussian f32 samples, f32 lane sums)
+
+
 def test_contact_model_sums_layout_vs_oracle(amd):
     """Contact models ship [Gram | z (f - xb)' | sum z] (include/irs_hip.h): the two-stage path
     (accumulate -> finalize), the fused launch and the oracle's restatement of the layout agree, in
@@ -1821,7 +1824,12 @@ def test_contact_model_sums_layout_vs_oracle(amd):
     assert dm.sums_len(SMOOTH_ZERO_ORDER_AB) == so.shape[1] == 66 + 77 + 11
     sums = dm.smooth_accumulate(SMOOTH_ZERO_ORDER_AB, xd, ud, dev.to_dev(dx, dev.F32), dev.to_dev(du, dev.F32))
     scale = np.abs(so).max(axis=0) + 1e-9
-    assert np.max(np.abs(sums.cpu().numpy() - so) / scale) < 2e-3          # f32 contact steps + f32 partial sums
+    err = np.abs(sums.cpu().numpy() - so) / scale
+    step = np.zeros(so.shape[1], bool)
+    step[66:66 + 77] = True                                                 # z (f - xb)': through the contact step
+    print("sums vs oracle: contact-step block %.3g, Gram and sum z %.3g" % (err[:, step].max(), err[:, ~step].max()))
+    assert err[:, step].max() < 2e-3                                        # f32 contact steps + f32 partial sums
+    assert err[:, ~step].max() < GRAM_F32_BOUND                             # f32 sums of products of the f32 samples
     At, Bt, ct, info = dm.smooth_finalize(SMOOTH_ZERO_ORDER_AB, N, xd, ud, sums)
     Ao, Bo, co = orc.zero_order_from_sums(sys_o, x_trj, u_trj, sums.cpu().numpy())
     assert int(info.abs().sum().item()) == 0
