@@ -203,6 +203,45 @@ int irs_smooth_rng(int model, const double *params, int n_params, int mode, int 
                    double *At, double *Bt, double *ct, int *info,
                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* The sample passes of B independent problems in ONE launch: irs_smooth_rng with a problem index, grid (nblk, B T).
+ * Row (b, t) executes the instructions of the single call on problem b's inputs, so problem b's outputs are, bit for
+ * bit, those of irs_smooth_rng(model, ..., T, N, x_trj_b, u_trj_b, NULL, std_u_b, seed_b, iter, ...):
+ *   - every row gets the launch geometry irs_smooth_geometry(model, mode, T, N, 1) reports for the PER-PROBLEM (T, N)
+ *     (nblk, block, chunk0, chunk, wg0_rr; IRS_UG is honoured per call, like the single entry); samples are dealt to
+ *     waves in the same order and the partial sums are added in the same fixed order;
+ *   - the Philox counters take the time step WITHIN the problem, problem b's seed, the shared `iter`, sample_offset 0;
+ *   - every draw is scaled by problem b's std_u, converted f64 -> f32 by the round-to-nearest conversion the single
+ *     entry applies on the host.
+ * Served: what the uniform-geometry kernel (csrc/smooth_ug.hip) serves -- IRS_MODEL_PLANAR_HAND_EXACT in
+ * IRS_SMOOTH_ZERO_ORDER_B and IRS_SMOOTH_FIRST_ORDER, the u-only modes (std_x does not exist), while IRS_UG is not 0.
+ * The general kernel (csrc/smooth.hip: the other contact models, and the planar hand under IRS_UG=0) has no batched
+ * form: its translation unit is SLP-vectorised under -ffp-contract=fast, and a problem index in front of its body
+ * changed which products the compiler fuses, i.e. the last bits of the f32 sums.
+ * In:  x_trj DEV f64, problem b's nominal states from x_trj + b x_stride (ELEMENTS), T rows of n read: x_stride =
+ *      (T+1) n takes a (B,T+1,n) trajectory tensor as it is, T n stacked nominal points; u_trj likewise with u_stride
+ *      >= T m; std_u (B,m) DEV f64; seed (B) DEV; iter shared by the problems.
+ * Out: B contiguous blocks of the single call's outputs: sums (B,T,P), At (B,T,n,n), Bt (B,T,n,m), ct (B,T,n) DEV
+ *      f64, info (B,T) DEV int.
+ * Workspace (DEV, 256-byte aligned): B slices of the single-problem layout, each with its own arrival counters,
+ * nominal steps and partial sums; problem b owns the bytes from b * round256(irs_smooth_workspace_bytes(model, mode,
+ * T, N)), and irs_smooth_batch_workspace_bytes is B times that (0: model / mode not served, or B <= 0).
+ * irs_smooth_batch_workspace_init zeroes the whole buffer, once per allocation -- and again before the buffer serves
+ * another (model, mode, T, N), whose slices start elsewhere; every call leaves all counters zero again.  One call in
+ * flight per workspace at a time.  No allocation, no host synchronisation: the call enqueues one
+ * launch on `stream`.  Every argument error is decided before the first HIP call:
+ *   IRS_ERR_INVALID_ARG  B, T or N <= 0; T > 1024; B T > 65535 (grid rows); a problem's partial sums beyond 4 GiB; a
+ *                        null pointer; x_stride < T n or u_stride < T m; wrong n_params
+ *   IRS_ERR_UNSUPPORTED  IRS_SMOOTH_ZERO_ORDER_AB, an analytic model (one with a Jacobian), an unknown model, a model
+ *                        or setting (IRS_UG=0) that runs the general kernel
+ *   IRS_ERR_WORKSPACE    workspace null, too small or not 256-byte aligned                                        */
+size_t irs_smooth_batch_workspace_bytes(int model, int mode, int T, int N, int B);   /* no GPU is touched */
+int irs_smooth_batch_workspace_init(void *workspace, size_t workspace_bytes, void *stream);
+int irs_smooth_rng_batch(int model, const double *params, int n_params, int mode, int T, int N, int B,
+                         const double *x_trj, long long x_stride, const double *u_trj, long long u_stride,
+                         const double *std_u, const uint64_t *seed, uint32_t iter,
+                         double *sums, double *At, double *Bt, double *ct, int *info,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* Sample pass, samples SUPPLIED (parity mode; "identical seeds" = the host draws
  * them exactly as the reference's `sampling(x_t,u_t,iter)` closure does, e.g.
  * examples/pendulum/pendulum_zero_order.py:38-43).

@@ -180,6 +180,11 @@ SIGNATURES["irs_quasistatic_descent_batch_workspace_bytes"] = (c_size_t, [c_int,
 SIGNATURES["irs_quasistatic_box_descent_batch"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, _dp, _dp, _dp, _dp,
                                                            _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, c_int, c_double, _dp,
                                                            _dp, _dp, _dp, _dp, _dp, c_size_t, c_void_p])
+SIGNATURES["irs_smooth_batch_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int, c_int, c_int])
+SIGNATURES["irs_smooth_batch_workspace_init"] = (c_int, [_dp, c_size_t, c_void_p])
+SIGNATURES["irs_smooth_rng_batch"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, c_int, c_int, _dp, c_longlong,
+                                              _dp, c_longlong, _dp, _dp, c_uint32, _dp, _dp, _dp, _dp, _dp, _dp, c_size_t,
+                                              c_void_p])
 SIGNATURES["irs_quasistatic_bound_rows_batch"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, c_int, c_int, _dp, _dp,
                                                           c_void_p])
 SIGNATURES["irs_tvlqr_box_solve"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_double,

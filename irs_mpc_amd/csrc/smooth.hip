@@ -905,9 +905,99 @@ int check_samples(const float* dx, const float* du, int model, int mode) {
     return IRS_OK;
 }
 
+// ---- B problems per launch --------------------------------------------------------------------------------
+size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// what the batched sample pass serves: what the uniform-geometry kernel serves (IRS_UG is read per call)
+int smooth_batch_supported(int model, int mode, int* n, int* m, int* np) {
+    const int rc = irs_model_info(model, n, m, np);
+    if (rc != IRS_OK) return rc;
+    return irs_smooth_ug_supported(model, mode) ? IRS_OK : IRS_ERR_UNSUPPORTED;
+}
+
 }  // namespace
 
 extern "C" {
+
+size_t irs_smooth_batch_workspace_bytes(int model, int mode, int T, int N, int B) {
+    int n, m, np;
+    if (B <= 0 || smooth_batch_supported(model, mode, &n, &m, &np) != IRS_OK) return 0;
+    return (size_t)B * round256(irs_smooth_workspace_bytes(model, mode, T, N));
+}
+
+int irs_smooth_batch_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(workspace != nullptr && workspace_bytes > 0, "no workspace");
+    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) { irs_set_error("irs_smooth_batch_workspace_init: %s", hipGetErrorString(e)); return IRS_ERR_HIP; }
+    return IRS_OK;
+}
+
+int irs_smooth_rng_batch(int model, const double* params, int n_params, int mode, int T, int N, int B,
+                         const double* x_trj, long long x_stride, const double* u_trj, long long u_stride,
+                         const double* std_u, const uint64_t* seed, uint32_t iter,
+                         double* sums, double* At, double* Bt, double* ct, int* info,
+                         void* workspace, size_t workspace_bytes, void* stream) {
+    // every argument error is decided before the first HIP call
+    IRS_CHECK_ARG(B > 0 && T > 0 && N > 0, "B, T and N must be positive");
+    IRS_CHECK_ARG((size_t)T * sizeof(int) <= kCounterBytes, "T too large for the arrival counters (max 1024)");
+    IRS_CHECK_ARG((long long)B * T <= 65535, "B * T beyond the grid's 65535 rows");
+    IRS_CHECK_ARG(x_trj && u_trj && std_u && seed && sums && At && Bt && ct && info, "null pointer");
+    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
+    int n = 0, m = 0, np = 0;
+    int rc = smooth_batch_supported(model, mode, &n, &m, &np);
+    if (rc != IRS_OK) {
+        irs_set_error("irs_smooth_rng_batch: model %d, mode %d: the batched sample pass serves the uniform-geometry kernel "
+                      "(IRS_MODEL_PLANAR_HAND_EXACT in IRS_SMOOTH_ZERO_ORDER_B and IRS_SMOOTH_FIRST_ORDER, IRS_UG not 0)",
+                      model, mode);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (params == nullptr || n_params != np) {
+        irs_set_error("irs_smooth_rng_batch: model %d expects %d params, got %d", model, np, n_params);
+        return IRS_ERR_INVALID_ARG;
+    }
+    IRS_CHECK_ARG(x_stride >= (long long)T * n && u_stride >= (long long)T * m,
+                  "x_stride / u_stride shorter than a problem's T rows");
+    SmoothArgs a;
+    memset(&a, 0, sizeof(a));
+    rc = irs_load_params(model, params, n_params, &a.p);
+    if (rc != IRS_OK) return rc;
+    SmoothGeometry g;
+    rc = smooth_geometry(model, mode, T, N, true, &g);
+    if (rc != IRS_OK) return rc;
+    const int P4 = (irs_sums_len(model, mode) + 3) / 4 * 4;
+    IRS_CHECK_ARG((size_t)T * g.nblk * P4 * sizeof(float) <= 0xffffffffull,
+                  "a problem's partial sums exceed the hand-off's 32-bit buffer size");
+    if (g.family != IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY) {
+        irs_set_error("irs_smooth_rng_batch: no batched kernel for the planned kernel family %d", g.family);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    // B slices of the single-problem layout, 256-byte aligned
+    const size_t stride = round256(irs_smooth_workspace_bytes(model, mode, T, N)), need = (size_t)B * stride;
+    if (workspace == nullptr || workspace_bytes < need) {
+        irs_set_error("irs_smooth_rng_batch: workspace %zu < %zu bytes (%d slices of %zu)", workspace_bytes, need, B, stride);
+        return IRS_ERR_WORKSPACE;
+    }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
+        irs_set_error("irs_smooth_rng_batch: the workspace must be 256-byte aligned");
+        return IRS_ERR_WORKSPACE;
+    }
+    // problem 0's arguments; the kernel's entry moves them to the row's problem (SmoothRow)
+    a.x_trj = x_trj; a.u_trj = u_trj;
+    a.T = T; a.N = N;
+    a.block = g.block; a.nblk = g.nblk; a.chunk0 = g.chunk0; a.chunk = g.chunk; a.wg0_rr = g.wg0_rr;
+    a.iter = iter;
+    a.diag = getenv("IRS_DIAG") ? atoi(getenv("IRS_DIAG")) : 0;      // timing experiments only, as the single entry
+    a.counters = static_cast<int*>(workspace);
+    a.fnom = reinterpret_cast<double*>(static_cast<char*>(workspace) + kCounterBytes);
+    a.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + kCounterBytes + fnom_bytes(T));
+    a.sums = sums; a.At = At; a.Bt = Bt; a.ct = ct; a.info = info;
+    a.n_total = (double)N;
+    const SmoothBatch bat{x_stride, u_stride, (long long)stride, reinterpret_cast<const unsigned long long*>(seed), std_u};
+    rc = irs_smooth_ug_launch_batch(model, mode, a, bat, B, static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) return rc;
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
 
 int irs_sums_len(int model, int mode) {
     if (mode < 0 || mode > 2) { irs_set_error("irs_sums_len: unknown mode %d", mode); return IRS_ERR_INVALID_ARG; }

@@ -36,10 +36,25 @@ struct SmoothArgs {
     double n_total;
 };
 
+// What a BATCHED launch (B problems, grid (nblk, B T): row b T + t is time step t of problem b) adds to SmoothArgs,
+// which then describes problem 0: the strides from one problem to the next, and what the single-problem launch carries
+// by value -- the seed and the command standard deviations -- per problem in device memory.  The outputs (sums, At, Bt,
+// ct, info) are B contiguous blocks of the single-problem shapes and need no stride.  A single-problem launch carries
+// the empty SmoothSolo instead.
+struct SmoothBatch {
+    long long x_stride, u_stride;        // elements between the problems of x_trj / u_trj
+    long long ws_stride;                 // BYTES between the workspace slices (counters, fnom and partial move together)
+    const unsigned long long* seed;      // DEV (B)
+    const double* std_u;                 // DEV (B, m)
+};
+struct SmoothSolo {};
+
 // smooth_ug.hip: the uniform-geometry sample pass (exact 8-row contact models, u-only modes)
 bool irs_smooth_ug_supported(int model, int mode);
 int irs_smooth_ug_nblk(int T, int N);
 int irs_smooth_ug_launch(int model, int mode, const SmoothArgs& a, bool rng, bool fuse, hipStream_t st);
+// the same pass over B problems (device-drawn samples, fused solve)
+int irs_smooth_ug_launch_batch(int model, int mode, const SmoothArgs& a, const SmoothBatch& bat, int B, hipStream_t st);
 
 namespace {
 
@@ -419,6 +434,82 @@ __device__ __forceinline__ void finalize_timestep(const ModelParams& p, const do
     if (lane == 0) info[t] = L.bad;
 }
 
+// BATCH: B independent problems in one launch, grid (nblk, B T).  Everything a time step owns is private to the
+// workgroups of its row already -- LDS, its arrival counter, its rows of the partials and of the outputs -- so the
+// only difference is at the ENTRY of a kernel: row -> (problem b, time step t), the per-problem pointers advance by b
+// strides (scalar arithmetic on kernel arguments), and the seed and the command standard deviations come from problem
+// b's rows (uniform addresses) into the fields the single-problem launch fills on the host -- converted f64 -> f32 by
+// the same round-to-nearest conversion, held in scalar registers like the kernel arguments they replace.  Below that
+// the body is the single-problem program on t: T stays the per-problem T, the Philox counters take t.
+// SmoothRow is what the body then reads in place of the kernel argument: the fields of SmoothArgs by name, with the
+// model constants by REFERENCE to the argument -- a private copy of the whole struct whose `p` is handed to a model
+// functor stays in scratch memory (392 bytes per lane, measured), this one dissolves into registers.
+// Bit-equality with the single-problem kernel is a property of the COMPILED code, not of the source: it holds for
+// smooth_ug.hip (built without SLP vectorisation; certified by tests/test_smooth_batch_gpu.py).  The same entry in
+// front of smooth.hip's kernel did not give it: that unit is SLP-vectorised under -ffp-contract=fast, any change in
+// front of the body -- even this view holding unchanged copies -- moved which products the compiler fuses with which
+// sums deep inside the contact solve, and the f32 sums differed in their last bits.
+struct SmoothRow {
+    const ModelParams& p;
+    const double* x_trj;
+    const double* u_trj;
+    const float* dx;
+    const float* du;
+    float std[32];
+    unsigned long long seed, sample_offset;
+    unsigned int iter;
+    int T, N, chunk, nblk, block, diag;
+    int* counters;
+    float* partial;
+    double* fnom;
+    int chunk0, wg0_rr;
+    double* sums;
+    double* At;
+    double* Bt;
+    double* ct;
+    int* info;
+    double n_total;
+    int t;             // the time step within the problem
+};
+
+template <class Model, int MODE>
+__device__ __forceinline__ SmoothRow smooth_batch_row(const SmoothArgs& a, const SmoothBatch& bat, int row) {
+    using TR = SmoothTraits<Model, MODE>;
+    constexpr int n = TR::n, m = TR::m;
+    const int b = row / a.T;
+    const long long wsb = b * bat.ws_stride;
+    const size_t rows = (size_t)b * a.T;
+    // (by name: the view repeats the fields of SmoothArgs, and a positional list would misassign silently)
+    SmoothRow r{.p = a.p,
+                .x_trj = a.x_trj + b * bat.x_stride,
+                .u_trj = a.u_trj + b * bat.u_stride,
+                .dx = nullptr, .du = nullptr,
+                .std = {},
+                .seed = bat.seed[b], .sample_offset = 0ull, .iter = a.iter,
+                .T = a.T, .N = a.N, .chunk = a.chunk, .nblk = a.nblk, .block = a.block, .diag = a.diag,
+                .counters = reinterpret_cast<int*>(reinterpret_cast<char*>(a.counters) + wsb),
+                .partial = reinterpret_cast<float*>(reinterpret_cast<char*>(a.partial) + wsb),
+                .fnom = reinterpret_cast<double*>(reinterpret_cast<char*>(a.fnom) + wsb),
+                .chunk0 = a.chunk0, .wg0_rr = a.wg0_rr,
+                .sums = a.sums + rows * TR::P, .At = a.At + rows * (n * n), .Bt = a.Bt + rows * (n * m),
+                .ct = a.ct + rows * n, .info = a.info + rows,
+                .n_total = a.n_total, .t = row - b * a.T};
+#pragma unroll
+    for (int j = 0; j < m; ++j)
+        r.std[n + j] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)bat.std_u[(size_t)b * m + j])));
+    return r;
+}
+
+// what a kernel's body calls `a`, and its time step: the kernel argument itself and the grid row, or (BATCH) the row's view
+template <class Model, int MODE>
+__device__ __forceinline__ const SmoothArgs& smooth_row(const SmoothArgs& a, const SmoothSolo&, int) { return a; }
+template <class Model, int MODE>
+__device__ __forceinline__ SmoothRow smooth_row(const SmoothArgs& a, const SmoothBatch& bat, int row) {
+    return smooth_batch_row<Model, MODE>(a, bat, row);
+}
+__device__ __forceinline__ int smooth_row_t(const SmoothArgs&, int row) { return row; }
+__device__ __forceinline__ int smooth_row_t(const SmoothRow& r, int) { return r.t; }
+
 template <class Model, class = void>
 struct contact_rows_of { static constexpr int value = 0; };
 template <class Model>
@@ -432,8 +523,8 @@ constexpr int contact_rows() { return contact_rows_of<Model>::value; }
 // the last arriver of the timestep adds the nblk partials in a FIXED order in f64 -> sums[t] and (FUSE) solves.
 // `fnom_t`: the f64 nominal step of this timestep if a wave of the launch evaluated it (else the solve does).
 // FNOM_ONLY: the solve never evaluates the model's step itself (kernels that must stay register-lean).
-template <class Model, int MODE, bool FUSE, int BLOCK, bool FNOM_ONLY = false>
-__device__ __forceinline__ void smooth_finish(const SmoothArgs& a, float* red, double* red64, double* tot,
+template <class Model, int MODE, bool FUSE, int BLOCK, bool FNOM_ONLY = false, class Args = SmoothArgs>
+__device__ __forceinline__ void smooth_finish(const Args& a, float* red, double* red64, double* tot,
                                               FinalizeLds<Model, MODE>& fin, int& s_ticket, int t, int blk, int tid,
                                               const double* fnom_t) {
     using TR = SmoothTraits<Model, MODE>;

@@ -367,8 +367,8 @@ struct UgNomLds {
 
 // (a) the f64 geometry: independent of the f32 prologue and of the table, so the nominal wave runs it BEFORE the
 // workgroup's first barrier, beside wave 0's f32 assembly.  Leaves J, q, D^-1, b in LDS and returns r_c on lane c.
-template <class Model>
-__device__ __forceinline__ double ug_nominal_geometry(const SmoothArgs& a, UgNomLds& L, int t, int lane) {
+template <class Model, class Args>
+__device__ __forceinline__ double ug_nominal_geometry(const Args& a, UgNomLds& L, int t, int lane) {
     constexpr int NC = Model::NC, n = Model::NX, m = Model::NU;
     double x64[n], u64[m], q[n], Dinv[n], b[n], J[NC][n], phi[NC];
 #pragma unroll
@@ -398,8 +398,8 @@ __device__ __forceinline__ double ug_nominal_geometry(const SmoothArgs& a, UgNom
 }
 
 // (b) after the table exists: the f32 pipeline's active set at du = 0, then the cooperative f64 solve and its check
-template <class Model>
-__device__ __forceinline__ void ug_nominal(const SmoothArgs& a, const UgUni<Model::NC>& U, const UgLds<Model>& S,
+template <class Model, class Args>
+__device__ __forceinline__ void ug_nominal(const Args& a, const UgUni<Model::NC>& U, const UgLds<Model>& S,
                                            UgNomLds& L, double rr, int t, int lane) {
     constexpr int NC = Model::NC, n = Model::NX, m = Model::NU;
     static_assert(NC == 8 && n <= 8, "lane (i,k) = 8 i + k owns entry (i,k) of the 8 x 8 dual Hessian");
@@ -508,8 +508,9 @@ __device__ unsigned long long ug_stamps[kUgStampWgs * kUgStampSlots];
 #define UG_STAMP(slot) do {} while (0)
 #endif
 
-template <class Model, int MODE, bool RNG, bool FUSE>
-__global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs a) {
+// BATCH (smooth_common.hpp, SmoothRow): grid (nblk, B T); `a` is then the view of the row's problem, set up at the entry
+template <class Model, int MODE, bool RNG, bool FUSE, bool BATCH>
+__global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, std::conditional_t<BATCH, SmoothBatch, SmoothSolo> bat) {
     using TR = SmoothTraits<Model, MODE>;
     constexpr int n = TR::n, m = TR::m, P = TR::P, NC = Model::NC;
     constexpr int BLOCK = kUgBlock, NW = BLOCK / 64;
@@ -531,7 +532,8 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs a) {
     __shared__ FinalizeLds<Model, MODE> fin;
     __shared__ int s_ticket;
 
-    const int t = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+    decltype(auto) a = smooth_row<Model, MODE>(args, bat, (int)blockIdx.y);
+    const int t = smooth_row_t(a, (int)blockIdx.y), blk = blockIdx.x, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
 
     UG_STAMP(0);
@@ -811,7 +813,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs a) {
         if (tid < P) red[tid] = out;
     }
     UG_STAMP(4);
-    smooth_finish<Model, MODE, FUSE, BLOCK, true>(a, red, red64, tot, fin, s_ticket, t, blk, tid, a.fnom + (size_t)t * n);
+    smooth_finish<Model, MODE, FUSE, BLOCK, true, std::remove_cv_t<std::remove_reference_t<decltype(a)>>>(a, red, red64, tot, fin, s_ticket, t, blk, tid, a.fnom + (size_t)t * n);
     UG_STAMP(5);
 }
 
@@ -819,12 +821,18 @@ template <class Model, int MODE>
 void ug_launch_m(const SmoothArgs& a, bool rng, bool fuse, hipStream_t st) {
     dim3 grid(a.nblk, a.T), block(kUgBlock);
     if (rng) {
-        if (fuse) hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, true, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, true, false>), grid, block, 0, st, a);
+        if (fuse) hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, true, true, false>), grid, block, 0, st, a, SmoothSolo{});
+        else hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, true, false, false>), grid, block, 0, st, a, SmoothSolo{});
     } else {
-        if (fuse) hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, false, true>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, false, false>), grid, block, 0, st, a);
+        if (fuse) hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, false, true, false>), grid, block, 0, st, a, SmoothSolo{});
+        else hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, false, false, false>), grid, block, 0, st, a, SmoothSolo{});
     }
+}
+
+template <class Model, int MODE>
+void ug_launch_batch_m(const SmoothArgs& a, const SmoothBatch& bat, int B, hipStream_t st) {
+    dim3 grid(a.nblk, B * a.T), block(kUgBlock);
+    hipLaunchKernelGGL((smooth_ug_kernel<Model, MODE, true, true, true>), grid, block, 0, st, a, bat);
 }
 
 }  // namespace
@@ -865,6 +873,14 @@ int irs_smooth_ug_launch(int model, int mode, const SmoothArgs& a, bool rng, boo
     if (model != IRS_MODEL_PLANAR_HAND_EXACT) return IRS_ERR_UNSUPPORTED;
     if (mode == IRS_SMOOTH_ZERO_ORDER_B) ug_launch_m<PlanarHandExactModel, IRS_SMOOTH_ZERO_ORDER_B>(a, rng, fuse, st);
     else if (mode == IRS_SMOOTH_FIRST_ORDER) ug_launch_m<PlanarHandExactModel, IRS_SMOOTH_FIRST_ORDER>(a, rng, fuse, st);
+    else return IRS_ERR_UNSUPPORTED;
+    return IRS_OK;
+}
+
+int irs_smooth_ug_launch_batch(int model, int mode, const SmoothArgs& a, const SmoothBatch& bat, int B, hipStream_t st) {
+    if (model != IRS_MODEL_PLANAR_HAND_EXACT) return IRS_ERR_UNSUPPORTED;
+    if (mode == IRS_SMOOTH_ZERO_ORDER_B) ug_launch_batch_m<PlanarHandExactModel, IRS_SMOOTH_ZERO_ORDER_B>(a, bat, B, st);
+    else if (mode == IRS_SMOOTH_FIRST_ORDER) ug_launch_batch_m<PlanarHandExactModel, IRS_SMOOTH_FIRST_ORDER>(a, bat, B, st);
     else return IRS_ERR_UNSUPPORTED;
     return IRS_OK;
 }

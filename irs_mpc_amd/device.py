@@ -168,6 +168,58 @@ class DeviceModel:
                                       _stream()), "irs_smooth_rng")
         return o
 
+    # ---- B sample passes per launch ------------------------------------------
+    def smooth_batch_supported(self, mode):
+        """Whether smooth_rng_batch serves this model in `mode`: what the uniform-geometry kernel serves (the exact
+        planar hand's u-only modes; IRS_UG is read per call)."""
+        return self.lib.irs_smooth_batch_workspace_bytes(self.model_id, int(mode), 1, 1, 1) > 0
+
+    def smooth_rng_batch(self, mode, X, U, N, std_u_dev, seed_dev, it, out=None):
+        """The sample passes of B problems in one launch (irs_smooth_rng_batch): problem b's outputs are, bit for bit,
+        those of smooth_rng(mode, X[b], U[b], N, None, std_u[b], seed[b], it).  X (B,T+1,n) or (B,T,n) -- T rows of
+        each problem are read -- and U (B,>=T,m) f64, contiguous in their last two dimensions (the problem stride is
+        taken from the tensor); T = the rows of `out`, else of U.  std_u_dev (B,m) f64, seed_dev (B) int64 holding the
+        uint64 bits, both on the device.  Returns dict(sums (B,T,P), At (B,T,n,n), Bt (B,T,n,m), ct (B,T,n), info
+        (B,T)); pass `out` to write into tensors of those shapes."""
+        B = U.shape[0]
+        T = out["info"].shape[1] if out is not None else U.shape[1]
+        dev = U.device
+        for name, t, cols in (("X", X, self.n), ("U", U, self.m)):
+            assert t.is_cuda and t.dtype == F64 and t.dim() == 3 and t.shape[0] == B and t.shape[1] >= T, name
+            assert t.shape[2] == cols and t.stride(2) == 1 and t.stride(1) == cols, (name, t.shape, t.stride())
+            assert B == 1 or t.stride(0) >= T * cols, (name, t.stride())
+        assert tuple(std_u_dev.shape) == (B, self.m) and tuple(seed_dev.shape) == (B,) and seed_dev.dtype == torch.int64
+        assert seed_dev.is_cuda and seed_dev.is_contiguous()
+        o = out
+        if o is None:
+            o = dict(sums=torch.empty((B, T, self.sums_len(mode)), dtype=F64, device=dev),
+                     At=torch.empty((B, T, self.n, self.n), dtype=F64, device=dev),
+                     Bt=torch.empty((B, T, self.n, self.m), dtype=F64, device=dev),
+                     ct=torch.empty((B, T, self.n), dtype=F64, device=dev),
+                     info=torch.empty((B, T), dtype=torch.int32, device=dev))
+        shapes = dict(sums=(B, T, self.sums_len(mode)), At=(B, T, self.n, self.n), Bt=(B, T, self.n, self.m),
+                      ct=(B, T, self.n), info=(B, T))
+        for name, shape in shapes.items():
+            assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
+        assert o["info"].dtype == torch.int32 and o["info"].is_contiguous()
+        need = self.lib.irs_smooth_batch_workspace_bytes(self.model_id, int(mode), T, int(N), B)
+        if need == 0:
+            raise NotImplementedError("smooth_rng_batch: model %d, mode %d is not served" % (self.model_id, mode))
+        key = ("smooth_batch", int(mode), T, int(N))         # one slice layout per buffer: the counters stay where they are
+        before = self._ws.get((key, dev))
+        ws = self._cached_workspace(key, need, dev)
+        if ws is not before:                                 # a fresh allocation: its counters are zeroed once
+            check(self.lib.irs_smooth_batch_workspace_init(ws.data_ptr(), ws.numel(), _stream()),
+                  "irs_smooth_batch_workspace_init")
+        xs = X.stride(0) if B > 1 else X.shape[1] * self.n
+        us = U.stride(0) if B > 1 else U.shape[1] * self.m
+        check(self.lib.irs_smooth_rng_batch(self.model_id, self._p, self._np, int(mode), T, int(N), B, X.data_ptr(), xs,
+                                            U.data_ptr(), us, _ptr(std_u_dev, F64), seed_dev.data_ptr(), int(it),
+                                            _ptr(o["sums"], F64), _ptr(o["At"], F64), _ptr(o["Bt"], F64),
+                                            _ptr(o["ct"], F64), o["info"].data_ptr(), ws.data_ptr(), ws.numel(),
+                                            _stream()), "irs_smooth_rng_batch")
+        return o
+
     def tvlqr_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, alpha_R=0.5, out=None):
         """Riccati backward pass + closed-loop rollout + cost in one launch."""
         T = At.shape[0]

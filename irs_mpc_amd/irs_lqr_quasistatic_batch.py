@@ -4,9 +4,13 @@ An iteration of `IrsLqrQuasistatic` is a sample pass followed by one bounded des
 unit for ~98 % of its time.  Users of a contact-rich optimiser run the same task from several initial guesses, start
 states or goals anyway; as separate `IrsLqrQuasistatic` objects those descents queue behind each other on that one
 unit.  Here the B descents of an iteration are ONE launch (`irs_quasistatic_box_descent_batch`: the same kernel with
-a problem index, one workgroup per problem), their trust-region rows one more, and the B sample passes go through the
-single-problem entry back to back on the stream -- each with its problem's seed and the iteration counter, so every
-problem sees the draws, and computes the bits, of an `IrsLqrQuasistatic` given the same parameters.
+a problem index, one workgroup per problem), their trust-region rows one more, and the B sample passes a third
+(`irs_smooth_rng_batch`: the sample-pass kernel over B x T rows, every row with the launch geometry, the draws and the
+summation order of the single call) -- each problem with its seed, its `std_u` schedule and the shared iteration
+counter, so every problem sees the draws, and computes the bits, of an `IrsLqrQuasistatic` given the same parameters.
+`batched_sample_pass=False` (or a model / mode the batched pass does not serve) sends the B sample passes through the
+single-problem entry back to back on the stream instead: the same bits, B launches and B library calls.  Exact mode
+linearises per problem either way.
 
 The problems share the model, `T`, the cost dictionaries, `gradient_mode`, `num_samples`, `sampling`, the kind of
 bound and the QP settings; they may differ in `x0`, `x_trj_d`, `u_trj_0`, the bound values, `std_u_initial` and
@@ -50,7 +54,7 @@ class _Problem(QuasistaticOptimizerBase):
 
 
 class IrsLqrQuasistaticBatch:
-    def __init__(self, q_dynamics, params_list):
+    def __init__(self, q_dynamics, params_list, batched_sample_pass=True):
         ps = list(params_list)
         if not ps:
             raise ValueError("params_list is empty")
@@ -117,6 +121,13 @@ class IrsLqrQuasistaticBatch:
         self._offsets = dev.to_dev(np.ascontiguousarray(np.stack(offs)))
         self._rows = None
         self._act = None
+        # the sample passes of an iteration as one launch, where the library serves the model and the mode
+        mode = SAMPLED_MODE.get(self.gradient_mode)
+        self.batched_sample_pass = bool(batched_sample_pass) and mode is not None and dm.smooth_batch_supported(mode)
+        if self.batched_sample_pass:
+            seeds = np.array([int(p.device_rng_seed) & 0xFFFFFFFFFFFFFFFF for p in ps], dtype=np.uint64)
+            self._seeds = torch.as_tensor(seeds.view(np.int64)).to(device)          # the uint64 bits, uploaded once
+        self._std_u = None
 
     # ---- results, per problem ---------------------------------------------------------------------
     @property
@@ -150,10 +161,21 @@ class IrsLqrQuasistaticBatch:
         raise AttributeError(name)
 
     # ---- one descent of all problems ----------------------------------------------------------------
-    def _linearise(self, X, U, it, AT, BT, CT, sinfo):
-        """B sample passes through the single-problem entry, back to back on the stream: problem b's with its seed and
-        the iteration counter -- the draws of its single twin."""
+    def _std_u_schedule(self, it0, D):
+        """(D, B, m): every problem's std_u at the iterations it0 .. it0 + D - 1, evaluated on the host."""
+        return np.array([[np.broadcast_to(np.asarray(p.sampling(p.std_u_initial, it0 + d), float), (self.dim_u,))
+                          for p in self.params_list] for d in range(D)], dtype=float)
+
+    def _linearise(self, X, U, it, AT, BT, CT, sinfo, d=0):
+        """The B sample passes: ONE launch over B x T rows (`batched_sample_pass`; `self._std_u[d]` holds the problems'
+        std_u of this descent), or B calls of the single-problem entry back to back on the stream.  Either way problem
+        b's pass takes its seed and the iteration counter -- the draws of its single twin."""
         mode = SAMPLED_MODE.get(self.gradient_mode)
+        # (asked again per descent: IRS_UG is read per call, and IRS_UG=0 sends the planar hand to the general kernel)
+        if self.batched_sample_pass and self._dm.smooth_batch_supported(mode):
+            self._dm.smooth_rng_batch(mode, X, U, self.num_samples, self._std_u[d], self._seeds, it,
+                                      out=dict(sums=self._sums, At=AT, Bt=BT, ct=CT, info=sinfo))
+            return
         for b, p in enumerate(self.params_list):
             if self.gradient_mode == "exact":
                 At, Bt, ct = self._dm.exact_linearize(X[b], U[b])
@@ -168,12 +190,12 @@ class IrsLqrQuasistaticBatch:
             self._dm.smooth_rng(mode, X[b], U[b], self.num_samples, None, std_u, int(p.device_rng_seed), it, out=out)
 
     def iterate(self, max_iterations):
-        """The quiet loop of `IrsLqrQuasistatic.iterate` over all problems: every descent is B sample passes, one
-        bound-rows launch and ONE batched descent that writes straight into its slot of the history; nothing waits for
-        the device until the one read-back at the end, where each problem's bookkeeping (history lists, five cost
-        terms, best-so-far) is replayed as the single class does.  A problem whose smoothing solve or QP failed does
-        not raise: it stops adopting at that descent, `status[b]` holds the message the single class raises, and the
-        others finish.  Returns (x_trj (B,T+1,n), u_trj (B,T,m), cost (B))."""
+        """The quiet loop of `IrsLqrQuasistatic.iterate` over all problems: every descent is the B sample passes (one
+        launch, or B with `batched_sample_pass=False`), one bound-rows launch and ONE batched descent that writes
+        straight into its slot of the history; nothing waits for the device until the one read-back at the end, where
+        each problem's bookkeeping (history lists, five cost terms, best-so-far) is replayed as the single class does.
+        A problem whose smoothing solve or QP failed does not raise: it stops adopting at that descent, `status[b]`
+        holds the message the single class raises, and the others finish.  Returns (x_trj (B,T+1,n), u_trj (B,T,m), cost (B))."""
         if dist_util.rank_world()[1] != 1:
             raise NotImplementedError("the batch runs on one GPU")
         B, T, n, m = self.B, self.T, self.dim_x, self.dim_u
@@ -204,9 +226,11 @@ class IrsLqrQuasistaticBatch:
                           torch.empty((B, T, m), dtype=dev.F64, device=device))
             if self._kind == "rel":                          # bounds on u_t - u_{t-1}: the offsets, once
                 dm.quasistatic_bound_rows_batch(X, self._idx32, self._offsets, rel=True, out=self._rows)
+        if self.batched_sample_pass:                         # the std_u schedule of all D descents: one upload
+            self._std_u = dev.to_dev(self._std_u_schedule(it0, D))
         it = it0
         for d in range(D):
-            self._linearise(X, U, it, AT, BT, CT, sinfo[d])
+            self._linearise(X, U, it, AT, BT, CT, sinfo[d], d)
             if self._kind != "rel":
                 dm.quasistatic_bound_rows_batch(X, self._idx32, self._offsets, rel=False, out=self._rows)
             rows = dict(du_lo=self._rows[0], du_hi=self._rows[1]) if self._kind == "rel" else dict(

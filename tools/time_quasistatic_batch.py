@@ -1,6 +1,8 @@
-"""Times B quasistatic descents in one launch (irs_quasistatic_box_descent_batch) and a whole batched iteration
-(B sample passes + one bound-rows launch + the batched descent) beside B x the single-problem call, at the benchmark's
-sizes: planar hand T=50 N=1e4, box pivoting T=80 N=6250.  Device-event times, 5 repetitions after a warm-up.
+"""Times B quasistatic descents in one launch (irs_quasistatic_box_descent_batch), the B sample passes -- as B calls
+of the single-problem entry and, where it is served (the planar hand), as ONE batched launch (irs_smooth_rng_batch) --
+and a whole batched iteration (sample passes + one bound-rows launch + the batched descent, for both settings of
+`batched_sample_pass`) beside B x the single-problem call, at the benchmark's sizes: planar hand T=50 N=1e4, box
+pivoting T=80 N=6250.  Device-event times, 5 repetitions after a warm-up.
 
     python tools/time_quasistatic_batch.py [planar_hand|box_pivoting] [--B 1,8,64,256,512] [--distinct] [--single-only]
 
@@ -109,20 +111,35 @@ def time_batch(p, B, distinct):
         for b in range(B):
             p.smooth(b if distinct else 0, out=outs[b])
 
+    # the same passes as one launch: problem b's trajectory, seed and std_u from device tensors
+    U = p.u_trj.unsqueeze(0).repeat(B, 1, 1).contiguous()
+    std_dev = dev.to_dev(np.tile(np.asarray(p.std_u, float), (B, 1)))
+    seed_dev = torch.as_tensor(np.array([b if distinct else 0 for b in range(B)], dtype=np.int64)).cuda()
+    bout = dict(sums=sums, At=AT, Bt=BT, ct=CT, info=info)
+
+    def batched_pass():
+        dm.smooth_rng_batch(p.w.mode, X, U, p.N, std_dev, seed_dev, 1, out=bout)
+
     def descent():
         act.zero_()
         out.update(dm.quasistatic_box_descent_batch(AT, BT, CT, p.Q, p.Qd, p.R, XD, X0, max_iter=2000, eps=1e-9, act=act,
                                                     out=out or None, **rows))
 
-    def iteration():
-        passes()
+    def iteration(linearise=passes):
+        linearise()
         dm.quasistatic_bound_rows_batch(X, idx32, off, rel=p.kind == "rel", out=(lo, hi))
         descent()
 
     passes()
+    want = {k: v.clone() for k, v in bout.items()}
     d, s, i = event_ms(descent), event_ms(passes), event_ms(iteration)
+    if not dm.smooth_batch_supported(p.w.mode):          # the general kernel has no batched sample pass
+        sb = ib = same = None
+    else:
+        sb, ib = event_ms(batched_pass), event_ms(lambda: iteration(batched_pass))
+        same = all(torch.equal(bout[k], want[k]) for k in bout)    # the one launch wrote the bits of the B calls
     bad = int((out["info"][:, 0] != 0).sum().item() + (out["info"][:, 2] != 0).sum().item())
-    return d, s, i, bad, int(out["info"][:, 1].max().item())
+    return d, s, i, bad, int(out["info"][:, 1].max().item()), sb, ib, same
 
 
 def main():
@@ -141,10 +158,15 @@ def main():
         return
     md, mi = float(np.median(sd)), float(np.median(si))
     for B in Bs:
-        d, s, i, bad, itmax = time_batch(p, B, "--distinct" in sys.argv)
+        d, s, i, bad, itmax, sb, ib, same = time_batch(p, B, "--distinct" in sys.argv)
         print("B=%-4d descent %s (B x single %9.3f)   sample passes %s   iteration %s (B x single %9.3f)   "
               "%8.0f problem-iterations/s   failed %d, most iterations %d"
               % (B, fmt(d), B * md, fmt(s), fmt(i), B * mi, B / (float(np.median(i)) * 1e-3), bad, itmax), flush=True)
+        if sb is None:
+            print("       batched sample pass: not served for this model (general kernel)", flush=True)
+            continue
+        print("       batched sample pass %s   iteration with it %s   %8.0f problem-iterations/s   bits equal: %s"
+              % (fmt(sb), fmt(ib), B / (float(np.median(ib)) * 1e-3), same), flush=True)
 
 
 if __name__ == "__main__":
