@@ -58,7 +58,11 @@ def bicycle(T=100, hard=False):
 
 
 def bicycle_hard(T=100):
-    return bicycle(T, hard=True)
+    # the scale of the bounded QPs moves by orders of magnitude along this curve: no one ADMM penalty serves them all
+    # (OSQP, which the reference's script calls, adapts its own)
+    sysd, p, smoothing, cem, iterations = bicycle(T, hard=True)
+    p.qp_adaptive_rho = True
+    return sysd, p, smoothing, cem, iterations
 
 
 def three_cart(T=100):

@@ -476,6 +476,61 @@ int irs_tvlqr_box_solve_wsx(int model, const double *params, int n_params, int T
                             double rho, double relax, int max_iter, double eps,
                             double *x_star, double *u_star, int *info, void *workspace, size_t workspace_bytes,
                             void *stream);
+/* The ADMM settings of the bounded TV-LQR as one struct, with the adaptive penalty: OSQP, which the reference calls,
+ * adapts its rho by itself, and the speed of the ADMM depends strongly on rho relative to the problem's scale.
+ * rho, relax, eps, max_iter: as the positional arguments of the entries above (rho: the penalty the launch starts from).
+ * adaptive != 0: after every check_every-th iteration of a tail QP that has not converged the residuals are
+ * balanced (the quantities are maxima over the tail's bounded components; y: the scaled duals):
+ *     ratio = sqrt((rp / pn) / (rd / dn)), clipped to [1e-2, 1e2],   rp = |z - w|, rd = rho |w - w_prev|,
+ *                                                                    pn = max(|z|, |w|), dn = rho |y|;
+ * when ratio > trigger or ratio < 1 / trigger: rho <- rho ratio, y <- y / ratio (the multipliers rho y stay), and the
+ * kernel rebuilds its Riccati factor -- at most max_refactor times per tail.  The new rho stays for the following
+ * warm-started tails of the launch.  The stopping test is unchanged: max(rp, rd) < eps with the current rho.
+ * adaptive == 0: check_every, trigger and max_refactor are not read, and the launch is that of the positional entry.
+ * IRS_ADMM_CHECK_EVERY, _TRIGGER, _MAX_REFACTOR: the constants the Python classes pass.           */
+#define IRS_ADMM_CHECK_EVERY 1000
+#define IRS_ADMM_TRIGGER 5.0
+#define IRS_ADMM_MAX_REFACTOR 4
+typedef struct {
+    double rho, relax, eps;
+    int max_iter;
+    int adaptive;
+    int check_every;
+    double trigger;
+    int max_refactor;
+} irs_admm_settings;
+/* irs_tvlqr_box_descent_wsx, irs_tvlqr_box_solve_wsx and the ADMM form (solver 1; any other solver is refused) of
+ * irs_quasistatic_box_descent_wsx with `settings` in place of (rho, relax, max_iter, eps); every other argument as
+ * there.  adapt_out (3) DEV f64, may be NULL, written by the adaptive form only: [0] the Riccati factorisations of the
+ * launch (1 = rho never moved), [1] the rho it ended with, [2] its ADMM iterations, all tails.  info keeps its meaning.  Records on chip or in the
+ * workspace: bit-identical results, as for the fixed penalty.                                                      */
+int irs_tvlqr_box_descent_set(int model, const double *params, int n_params, int T,
+                              const double *At, const double *Bt, const double *ct,
+                              const double *Q, const double *Qd, const double *R, double alpha_R,
+                              const double *xd_trj, const double *x0,
+                              const double *xlo, const double *xhi, const double *ulo, const double *uhi,
+                              const irs_admm_settings *settings,
+                              double *x_new, double *u_new, int *info, double *adapt_out,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int irs_tvlqr_box_solve_set(int model, const double *params, int n_params, int T,
+                            const double *At, const double *Bt, const double *ct,
+                            const double *Q, const double *Qd, const double *R, double alpha_R,
+                            const double *xd_trj, const double *x0, int position_controlled,
+                            const double *x_lo, const double *x_hi, const double *u_lo, const double *u_hi,
+                            const double *du_lo, const double *du_hi,
+                            const irs_admm_settings *settings,
+                            double *x_star, double *u_star, int *info, double *adapt_out,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int irs_quasistatic_box_descent_set(int model, const double *params, int n_params, int T,
+                                    const double *At, const double *Bt, const double *ct,
+                                    const double *Q, const double *Qd, const double *R,
+                                    const double *xd_trj, const double *x0,
+                                    const double *x_lo, const double *x_hi,
+                                    const double *u_lo, const double *u_hi,
+                                    const double *du_lo, const double *du_hi,
+                                    int solver, const irs_admm_settings *settings,
+                                    double *x_new, double *u_new, double *cost, int *info, double *adapt_out,
+                                    void *workspace, size_t workspace_bytes, void *stream);
 /* IrsLqrZeroOrder.compute_least_squares (irs_lqr/irs_lqr_zero_order.py:27-36) stand-alone: dxdu (N, n+m),
  * deltaf (N, n) DEV f64 -> A (n,n), B (n,m) with [A | B] = lstsq(dxdu, deltaf)[0]'.  Normal equations in f64,
  * Jacobi-scaled Cholesky (the solve the sample pass ends with).  info (1): 0, the failed pivot (1-based: a

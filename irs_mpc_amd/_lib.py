@@ -193,6 +193,34 @@ SIGNATURES["irs_tvlqr_box_solve"] = (c_int, [c_int, POINTER(c_double), c_int, c_
 SIGNATURES["irs_tvlqr_box_solve_wsx"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
                                                  c_double, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_double,
                                                  c_double, c_int, c_double, _dp, _dp, _dp, _dp, c_size_t, c_void_p])
+
+
+class AdmmSettings(ctypes.Structure):
+    """irs_admm_settings (include/irs_hip.h)."""
+    _fields_ = [("rho", c_double), ("relax", c_double), ("eps", c_double), ("max_iter", c_int), ("adaptive", c_int),
+                ("check_every", c_int), ("trigger", c_double), ("max_refactor", c_int)]
+
+
+# IRS_ADMM_CHECK_EVERY, IRS_ADMM_TRIGGER, IRS_ADMM_MAX_REFACTOR
+ADMM_CHECK_EVERY, ADMM_TRIGGER, ADMM_MAX_REFACTOR = 1000, 5.0, 4
+
+
+def admm_settings(rho, relax, max_iter, eps, adaptive=False, check_every=ADMM_CHECK_EVERY, trigger=ADMM_TRIGGER,
+                  max_refactor=ADMM_MAX_REFACTOR):
+    return AdmmSettings(float(rho), float(relax), float(eps), int(max_iter), 1 if adaptive else 0, int(check_every),
+                        float(trigger), int(max_refactor))
+
+
+SIGNATURES["irs_tvlqr_box_descent_set"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                   c_double, _dp, _dp, _dp, _dp, _dp, _dp, POINTER(AdmmSettings), _dp, _dp,
+                                                   _dp, _dp, _dp, c_size_t, c_void_p])
+SIGNATURES["irs_tvlqr_box_solve_set"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                 c_double, _dp, _dp, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                 POINTER(AdmmSettings), _dp, _dp, _dp, _dp, _dp, c_size_t, c_void_p])
+SIGNATURES["irs_quasistatic_box_descent_set"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp,
+                                                         _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, c_int,
+                                                         POINTER(AdmmSettings), _dp, _dp, _dp, _dp, _dp, _dp, c_size_t,
+                                                         c_void_p])
 SIGNATURES["irs_least_squares"] = (c_int, [c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_smooth_run"] = (c_int, [POINTER(SmoothCall), c_void_p])
 SIGNATURES["irs_descent_run"] = (c_int, [POINTER(DescentCall), c_void_p])

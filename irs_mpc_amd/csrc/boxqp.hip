@@ -56,8 +56,10 @@ typedef double v2d __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) v2d gv2d;    // global: a generic pointer would make these flat accesses,
                                                         // which also count in lgkmcnt and would stall at every wave_sync
 
-template <class Model, bool DU, bool HBM>
-__global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs) {
+// ADAPT: the penalty rho follows the residuals (the rule: see the MPC loop below), and the factorisation runs again
+// with each new rho.  ADAPT = false reads nothing of `ad` and is the fixed-rho kernel, instruction for instruction.
+template <class Model, bool DU, bool HBM, bool ADAPT>
+__global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs, BoxAdapt ad) {
     if (a.run_flag != nullptr && *a.run_flag == 0) return;          // uniform
     constexpr int NR = Model::NX, M = Model::NU;      // real state / control sizes
     constexpr int N = NR + (DU ? M : 0);              // size of the QP's state (z = [x; u_prev] if DU)
@@ -127,162 +129,15 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
     for (int q = lane; q < (T + 1) * N; q += 64) { wx[q] = 0.0; yx[q] = 0.0; zx[q] = 0.0; }
     for (int q = lane; q < T * M; q += 64) { wu[q] = 0.0; yu[q] = 0.0; zu[q] = 0.0; kk[q] = 0.0; }
     wave_sync();
-    const double hr = 0.5 * a.rho;
+    double rho = a.rho, hr = 0.5 * rho;              // (ADAPT = false: never written again)
     auto qs = [&](const double* Qm, int i, int j) -> double {
         return (i < NR && j < NR) ? 0.5 * (Qm[i * NR + j] + Qm[j * NR + i]) : 0.0;
     };
-    // P_T = Qd + rho/2 Mx ; qx_T = Qd xd_T
-    for (int q = lane; q < N * N; q += 64) {
-        int i = q / N, j = q % N;
-        P[q] = qs(a.Qd, i, j) + (i == j ? hr * mxv[i] : 0.0);
-    }
-    if (lane < N) {
-        double s = 0.0;
-        for (int j = 0; j < N; ++j) s += qs(a.Qd, lane, j) * xd_(T, j);
-        qxT[lane] = s;
-    }
-    wave_sync();
-
-    // ---- factorisation: backward Riccati with Q^ = Q + rho/2 Mx, R^ = alpha R + rho/2 Mu --
+    // ---- factorisation (boxqp_factor.inc), the whole horizon ----------------------------
     int bad = 0;
-    for (int t = T - 1; t >= 0; --t) {
-        // HBM: records T-1 and T-2 are built in the ring slots the first sweep reads them from, the rest in the third
-        double* rec = HBM ? F + (size_t)((t >= T - 2 ? t : T - 3) % L::RING) * L::SP : F + (size_t)t * L::S;
-        for (int q = lane; q < N * N; q += 64) Am[q] = A_(t, q / N, q % N);
-        for (int q = lane; q < N * M; q += 64) rec[L::oB + q] = B_(t, q / M, q % M);
-        if (lane < N) {
-            rec[L::oC + lane] = c_(t, lane);
-            double s = 0.0;
-            for (int j = 0; j < N; ++j) s += qs(a.Q, lane, j) * xd_(t, j);
-            rec[L::oQx + lane] = s;
-        }
-        wave_sync();
-        const double* B = rec + L::oB;
-        // PB = P B ; d = P c
-        for (int q = lane; q < N * M; q += 64) {
-            int i = q / M, j = q % M;
-            double s = 0.0;
-            for (int l = 0; l < N; ++l) s += P[i * N + l] * B[l * M + j];
-            PB[q] = s;
-        }
-        if (lane < N) {
-            double s = 0.0;
-            for (int l = 0; l < N; ++l) s += P[lane * N + l] * rec[L::oC + l];
-            rec[L::oD + lane] = s;
-        }
-        wave_sync();
-        // H = R^ + B'PB
-        for (int q = lane; q < M * M; q += 64) {
-            int i = q / M, j = q % M;
-            double s = 0.5 * a.alpha * (a.R[i * M + j] + a.R[j * M + i]) + (i == j ? hr * muv[i] : 0.0);
-            for (int l = 0; l < N; ++l) s += B[l * M + i] * PB[l * M + j];
-            Hs[q] = s;
-        }
-        wave_sync();
-        // H^-1 by LDL' in registers (every lane), lane j < M keeps column j
-        {
-            double Lm[M][M], Dg[M], Dinv[M];
-#pragma unroll
-            for (int j = 0; j < M; ++j) {
-                double dj = Hs[j * M + j];
-#pragma unroll
-                for (int l = 0; l < j; ++l) dj -= Lm[j][l] * Lm[j][l] * Dg[l];
-                if (!(dj > 0.0) && bad == 0) bad = t + 1;
-                Dg[j] = dj;
-                Dinv[j] = 1.0 / dj;
-#pragma unroll
-                for (int i = j + 1; i < M; ++i) {
-                    double s = Hs[i * M + j];
-#pragma unroll
-                    for (int l = 0; l < j; ++l) s -= Lm[i][l] * Lm[j][l] * Dg[l];
-                    Lm[i][j] = s * Dinv[j];
-                }
-            }
-            if (lane < M) {
-                double y[M];
-#pragma unroll
-                for (int i = 0; i < M; ++i) {
-                    double s = (i == lane) ? 1.0 : 0.0;
-#pragma unroll
-                    for (int l = 0; l < i; ++l) s -= Lm[i][l] * y[l];
-                    y[i] = s;
-                }
-#pragma unroll
-                for (int i = M - 1; i >= 0; --i) {
-                    double s = y[i] * Dinv[i];
-#pragma unroll
-                    for (int l = i + 1; l < M; ++l) s -= Lm[l][i] * y[l];
-                    y[i] = s;
-                }
-#pragma unroll
-                for (int i = 0; i < M; ++i) rec[L::oHinv + i * M + lane] = y[i];
-            }
-        }
-        wave_sync();
-        // Minv = H^-1 B' (M x N)
-        for (int q = lane; q < M * N; q += 64) {
-            int i = q / N, j = q % N;
-            double s = 0.0;
-            for (int l = 0; l < M; ++l) s += rec[L::oHinv + i * M + l] * B[j * M + l];
-            rec[L::oMinv + q] = s;
-        }
-        // W = P A
-        for (int q = lane; q < N * N; q += 64) {
-            int i = q / N, j = q % N;
-            double s = 0.0;
-            for (int l = 0; l < N; ++l) s += P[i * N + l] * Am[l * N + j];
-            Wm[q] = s;
-        }
-        wave_sync();
-        // K = -Minv W  (= -H^-1 B'P A)
-        for (int q = lane; q < M * N; q += 64) {
-            int i = q / N, j = q % N;
-            double s = 0.0;
-            for (int l = 0; l < N; ++l) s -= rec[L::oMinv + i * N + l] * Wm[l * N + j];
-            rec[L::oK + q] = s;
-        }
-        wave_sync();
-        // Acl = A + B K
-        for (int q = lane; q < N * N; q += 64) {
-            int i = q / N, j = q % N;
-            double s = Am[q];
-            for (int l = 0; l < M; ++l) s += B[i * M + l] * rec[L::oK + l * N + j];
-            rec[L::oAcl + q] = s;
-        }
-        wave_sync();
-        // P <- Q^ + sym(W' Acl)   (W' Acl = A'P Acl)
-        double pn[(N * N + 63) / 64];
-#pragma unroll
-        for (int r = 0; r < (N * N + 63) / 64; ++r) {
-            int q = lane + 64 * r;
-            pn[r] = 0.0;
-            if (q < N * N) {
-                int i = q / N, j = q % N;
-                double s = 0.0, s2 = 0.0;
-                for (int l = 0; l < N; ++l) {
-                    s += Wm[l * N + i] * rec[L::oAcl + l * N + j];
-                    s2 += Wm[l * N + j] * rec[L::oAcl + l * N + i];
-                }
-                pn[r] = qs(a.Q, i, j) + (i == j ? hr * mxv[i] : 0.0) + 0.5 * (s + s2);
-            }
-        }
-        wave_sync();
-#pragma unroll
-        for (int r = 0; r < (N * N + 63) / 64; ++r) {
-            int q = lane + 64 * r;
-            if (q < N * N) P[q] = pn[r];
-        }
-        if constexpr (HBM) {                             // the finished record, once, to the workspace
-            const v2d* src = reinterpret_cast<const v2d*>(rec);
-            gv2d* dst = (gv2d*)(recs + (size_t)t * L::SP);
-            for (int c = lane; c < L::SP / 2; c += 64) dst[c] = src[c];
-        }
-        wave_sync();
-    }
-    if constexpr (HBM) {                                 // the sweeps read them back: the stores are done first
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-    }
+#define BOX_FACTOR_FROM 0
+#include "boxqp_factor.inc"
+#undef BOX_FACTOR_FROM
 
     // ---- HBM records: staging through the LDS ring -------------------------------------------
     // record t = L::SP / 2 16-byte chunks; lane l moves chunks l, l + 64, ..  (global_load_dwordx4 into registers;
@@ -322,6 +177,8 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
     };
     int it_max = 0, n_fail = 0;
     const double al = a.relax;
+    int n_factor = 1;                                  // ADAPT: factorisations and ADMM iterations of the launch,
+    long long n_iter = 0;                              // reported in ad.out
     for (int tau = 0; tau < T; ++tau) {
         // the tail problem starts from the realised state; for DU its u_prev block is the
         // realised actuated position x_tau[idx] (tv_lqr.py:99-100 at the tail's local t = 0)
@@ -348,6 +205,7 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
         wave_sync();
         int it = 0;
         bool conv = false;
+        int n_refactor = 0;                            // ADAPT: of this tail, at most ad.max_refactor
         while (it < a.max_iter && !conv) {
             ++it;
             // backward affine sweep: p_T = -(Qd xd_T + rho/2 mx (w - y)_T)
@@ -446,11 +304,54 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
                     wu[q] = wn;
                 }
             }
-            const double res = wave_max(fmax(rp, a.rho * rd));
+            const double res = wave_max(fmax(rp, rho * rd));
             conv = res < a.eps;
             wave_sync();
+            if constexpr (ADAPT) {
+                // Residual balancing, every ad.check_every iterations of a tail that has not converged: with the
+                // residuals relative to their scales -- zn = max(|z|, |w|), yn = rho max |y| (the multipliers), over
+                // the tail's bounded components like rp and rd -- rho <- rho sqrt((rp / zn) / (rd / yn)) (the factor
+                // clipped to [1e-2, 1e2]) when that factor leaves [1 / trigger, trigger].  The multipliers rho y
+                // stay: y <- y rho_old / rho_new.  The new rho stays for the tails that follow.  All of it uniform.
+                if (!conv && it % ad.check_every == 0 && n_refactor < ad.max_refactor) {
+                    double zn = 0.0, yn = 0.0;          // (each lane reads back the entries it has just written)
+                    for (int q = (tau + 1) * N + lane; q < (T + 1) * N; q += 64)
+                        if (mxv[q % N] != 0.0) {
+                            zn = fmax(zn, fmax(fabs(zx[q]), fabs(wx[q])));
+                            yn = fmax(yn, fabs(yx[q]));
+                        }
+                    for (int q = tau * M + lane; q < T * M; q += 64)
+                        if (muv[q % M] != 0.0) {
+                            zn = fmax(zn, fmax(fabs(zu[q]), fabs(wu[q])));
+                            yn = fmax(yn, fabs(yu[q]));
+                        }
+                    zn = wave_max(zn);
+                    yn = rho * wave_max(yn);
+                    const double rpa = wave_max(rp), rda = rho * wave_max(rd);
+                    if (rpa > 0.0 && rda > 0.0 && zn > 0.0 && yn > 0.0) {
+                        const double ratio = fmin(fmax(sqrt((rpa / zn) / (rda / yn)), 1e-2), 1e2);
+                        if (ratio > ad.trigger || ratio * ad.trigger < 1.0) {
+                            const double sc = 1.0 / ratio;
+                            rho *= ratio;
+                            hr = 0.5 * rho;
+                            for (int q = (tau + 1) * N + lane; q < (T + 1) * N; q += 64) yx[q] *= sc;
+                            for (int q = tau * M + lane; q < T * M; q += 64) yu[q] *= sc;
+                            wave_sync();
+                            // HBM: the ring holds records T-1 and T-2 of the old factor (where a forward sweep leaves
+                            // them) and no load is in flight; the factorisation builds the new T-1 and T-2 in those
+                            // same slots and uses the third, which the next sweep fills before it reads it
+#define BOX_FACTOR_FROM tau
+#include "boxqp_factor.inc"
+#undef BOX_FACTOR_FROM
+                            ++n_refactor;
+                            ++n_factor;
+                        }
+                    }
+                }
+            }
         }
         it_max = max(it_max, it);
+        if constexpr (ADAPT) n_iter += it;
         n_fail += conv ? 0 : 1;
         if (a.single_tail) {
             // solve_tvlqr's return value: the plan of this one QP (xt_star (T+1,n), ut_star (T,m)) -- the
@@ -460,6 +361,9 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
                 a.u_new[q] = DU ? zx[(size_t)(q / M + 1) * N + NR + q % M] : zu[q];
             if (lane == 0) {
                 a.info[0] = bad; a.info[1] = it_max; a.info[2] = n_fail;
+            }
+            if constexpr (ADAPT) {
+                if (lane == 0 && ad.out != nullptr) { ad.out[0] = (double)n_factor; ad.out[1] = rho; ad.out[2] = (double)n_iter; }
             }
             return;
         }
@@ -503,21 +407,29 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
         a.info[0] = bad; a.info[1] = it_max; a.info[2] = n_fail;
         if (a.cost) a.cost[0] = cost;
     }
+    if constexpr (ADAPT) {
+        if (lane == 0 && ad.out != nullptr) { ad.out[0] = (double)n_factor; ad.out[1] = rho; ad.out[2] = (double)n_iter; }
+    }
 }
 
-template <class Model, bool DU, bool HBM>
-int launch_box_kernel(const BoxArgs& a, double* recs, size_t bytes, hipStream_t st) {
-    constexpr auto kern = box_descent_kernel<Model, DU, HBM>;
+template <class Model, bool DU, bool HBM, bool ADAPT>
+int launch_box_kernel(const BoxArgs& a, double* recs, size_t bytes, const BoxAdapt& ad, hipStream_t st) {
+    constexpr auto kern = box_descent_kernel<Model, DU, HBM, ADAPT>;
     const int rc = irs_raise_lds_limit<kern>(bytes, "irs_tvlqr_box_descent");
     if (rc != IRS_OK) return rc;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(64), bytes, st, a, recs);
+    hipLaunchKernelGGL(kern, dim3(1), dim3(64), bytes, st, a, recs, ad);
     return IRS_OK;
 }
 
+// adapt: null = the fixed-rho kernel
 template <class Model, bool DU>
-int launch_box(const BoxArgs& a, const BoxPlan& p, double* ws, hipStream_t st) {
-    if (p.place != BoxPlace::AdmmHbm) return launch_box_kernel<Model, DU, false>(a, nullptr, p.lds, st);
-    return launch_box_kernel<Model, DU, true>(a, ws, p.lds, st);
+int launch_box(const BoxArgs& a, const BoxPlan& p, double* ws, const BoxAdapt* adapt, hipStream_t st) {
+    const bool hbm = p.place == BoxPlace::AdmmHbm;
+    if (adapt == nullptr)
+        return hbm ? launch_box_kernel<Model, DU, true, false>(a, ws, p.lds, BoxAdapt{}, st)
+                   : launch_box_kernel<Model, DU, false, false>(a, nullptr, p.lds, BoxAdapt{}, st);
+    return hbm ? launch_box_kernel<Model, DU, true, true>(a, ws, p.lds, *adapt, st)
+               : launch_box_kernel<Model, DU, false, true>(a, nullptr, p.lds, *adapt, st);
 }
 
 // Trust-region rows of B problems in one launch (IrsLqrQuasistatic._bounds_dev, irs_lqr_quasistatic.py:303-325): entry
@@ -595,7 +507,7 @@ static WsFit ws_fit(const BoxPlan& p, size_t count, const void* ws, size_t ws_by
 // The ADMM kernel on a filled BoxArgs, where the plan puts it: records on chip, or in `ws` -- whenever one is given
 // (policy Always), or only where they do not fit LDS (IfNeeded).  du: the position-controlled form.
 int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, BoxWs policy,
-                        hipStream_t st) {
+                        hipStream_t st, const BoxAdapt* adapt) {
     const BoxPlan p = irs_box_plan(model, a.T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM,
                                    ws == nullptr ? BoxWs::None : policy);
     if (p.max_T == 0) {
@@ -625,10 +537,10 @@ int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, vo
     double* recs = static_cast<double*>(ws);
     int rc = IRS_ERR_UNSUPPORTED;
     if (!du) {
-        IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, p, recs, st); });
+        IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, p, recs, adapt, st); });
     } else {
         IRS_DISPATCH_MODEL(model, {
-            if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, p, recs, st);
+            if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, p, recs, adapt, st);
         });
     }
     if (rc != IRS_OK) return rc;
@@ -683,6 +595,29 @@ static int auto_solver(int model, int T, bool one_box, const void* ws, size_t ws
     const BoxPlan tiles = irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, ws ? BoxWs::IfNeeded : BoxWs::None);
     if (tiles.place != BoxPlace::None && ws_bytes >= tiles.records) return 3;
     return irs_box_plan(model, T, IRS_BOX_ACTIVE_SET, BoxWs::None).place == BoxPlace::Lanes ? 2 : 1;
+}
+
+// The checks of an irs_admm_settings (fn: the entry, for the message) and what the launch takes from it: *adapt is
+// left null for adaptive == 0 -- the fixed-rho kernel -- and else points at *ad, filled with the rule's constants.
+static int read_admm_settings(const char* fn, const irs_admm_settings* s, double* adapt_out, BoxAdapt* ad,
+                              const BoxAdapt** adapt) {
+    *adapt = nullptr;
+    if (s == nullptr) {
+        irs_set_error("%s: settings must not be NULL", fn);
+        return IRS_ERR_INVALID_ARG;
+    }
+    if (!irs_admm_settings_ok(s->rho, s->relax, s->max_iter, s->eps)) {
+        irs_set_error("%s: bad ADMM parameter", fn);
+        return IRS_ERR_INVALID_ARG;
+    }
+    if (s->adaptive == 0) return IRS_OK;
+    if (!irs_admm_adapt_ok(s->check_every, s->trigger, s->max_refactor)) {
+        irs_set_error("%s: the adaptive penalty needs check_every > 0, trigger > 1 and max_refactor >= 0", fn);
+        return IRS_ERR_INVALID_ARG;
+    }
+    *ad = BoxAdapt{s->check_every, s->max_refactor, s->trigger, adapt_out};
+    *adapt = ad;
+    return IRS_OK;
 }
 
 extern "C" {
@@ -780,6 +715,32 @@ int irs_tvlqr_box_descent_wsx(int model, const double* params, int n_params, int
                                static_cast<hipStream_t>(stream));
 }
 
+int irs_tvlqr_box_descent_set(int model, const double* params, int n_params, int T, const double* At,
+                              const double* Bt, const double* ct, const double* Q, const double* Qd,
+                              const double* R, double alpha_R, const double* xd_trj, const double* x0,
+                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
+                              const irs_admm_settings* settings, double* x_new, double* u_new, int* info,
+                              double* adapt_out, void* workspace, size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
+                  x_new && u_new && info, "bad argument");
+    BoxAdapt ad;
+    const BoxAdapt* adapt;
+    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
+    if (rc != IRS_OK) return rc;
+    rc = check_box_workspace(__func__, model, T, 0, workspace, workspace_bytes);
+    if (rc != IRS_OK) return rc;
+    BoxArgs a;
+    rc = box_begin(&a, model, params, n_params, T, false);
+    if (rc != IRS_OK) return rc;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi;
+    a.alpha = alpha_R; a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter;
+    a.eps = settings->eps;
+    a.x_new = x_new; a.u_new = u_new; a.info = info;
+    return irs_box_admm_launch("irs_tvlqr_box_descent", model, false, a, workspace, workspace_bytes, BoxWs::Always,
+                               static_cast<hipStream_t>(stream), adapt);
+}
+
 int irs_quasistatic_box_descent(int model, const double* params, int n_params, int T, const double* At,
                                 const double* Bt, const double* ct, const double* Q, const double* Qd,
                                 const double* R, const double* xd_trj, const double* x0,
@@ -855,6 +816,35 @@ int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_param
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
+}
+
+// the ADMM form (solver 1) alone, with its settings in a struct: the adaptive penalty is the ADMM kernel's
+int irs_quasistatic_box_descent_set(int model, const double* params, int n_params, int T, const double* At,
+                                    const double* Bt, const double* ct, const double* Q, const double* Qd,
+                                    const double* R, const double* xd_trj, const double* x0,
+                                    const double* x_lo, const double* x_hi, const double* u_lo,
+                                    const double* u_hi, const double* du_lo, const double* du_hi,
+                                    int solver, const irs_admm_settings* settings, double* x_new, double* u_new,
+                                    double* cost, int* info, double* adapt_out, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_new && u_new && info, "bad argument");
+    IRS_CHECK_ARG(solver == 1, "solver must be 1 (ADMM): the settings are the ADMM kernel's");
+    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
+                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
+    BoxAdapt ad;
+    const BoxAdapt* adapt;
+    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
+    if (rc != IRS_OK) return rc;
+    BoxArgs a;
+    rc = box_begin(&a, model, params, n_params, T, true);
+    if (rc != IRS_OK) return rc;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
+    a.alpha = 1.0;      // tv_lqr.py:107, as irs_quasistatic_box_descent_wsx
+    a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter; a.eps = settings->eps;
+    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info;
+    return irs_box_admm_launch("irs_quasistatic_box_descent", model, true, a, workspace, workspace_bytes,
+                               BoxWs::IfNeeded, static_cast<hipStream_t>(stream), adapt);
 }
 
 // ---- B problems per launch (solver 3's method) ---------------------------------------------------------------------
@@ -952,6 +942,35 @@ int irs_tvlqr_box_solve_wsx(int model, const double* params, int n_params, int T
     a.x_new = x_star; a.u_new = u_star; a.info = info; a.single_tail = 1;
     return irs_box_admm_launch("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes,
                                BoxWs::Always, static_cast<hipStream_t>(stream));
+}
+
+int irs_tvlqr_box_solve_set(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
+                            const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
+                            const double* xd_trj, const double* x0, int position_controlled,
+                            const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
+                            const double* du_lo, const double* du_hi, const irs_admm_settings* settings,
+                            double* x_star, double* u_star, int* info, double* adapt_out, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_star && u_star && info, "bad argument");
+    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
+                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
+    IRS_CHECK_ARG(position_controlled || du_lo == nullptr, "du bounds need the position-controlled form");
+    BoxAdapt ad;
+    const BoxAdapt* adapt;
+    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
+    if (rc != IRS_OK) return rc;
+    rc = check_box_workspace(__func__, model, T, position_controlled ? 1 : 0, workspace, workspace_bytes);
+    if (rc != IRS_OK) return rc;
+    BoxArgs a;
+    rc = box_begin(&a, model, params, n_params, T, true);
+    if (rc != IRS_OK) return rc;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
+    a.alpha = alpha_R; a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter;
+    a.eps = settings->eps;
+    a.x_new = x_star; a.u_new = u_star; a.info = info; a.single_tail = 1;
+    return irs_box_admm_launch("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes,
+                               BoxWs::Always, static_cast<hipStream_t>(stream), adapt);
 }
 
 }  // extern "C"

@@ -53,11 +53,24 @@ BoxPlan irs_box_plan(int model, int T, int kind, BoxWs ws);
 inline bool irs_admm_settings_ok(double rho, double relax, int max_iter, double eps) {
     return rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0;
 }
+// The adaptive penalty of the ADMM kernel (irs_admm_settings with adaptive != 0): every check_every iterations of a
+// tail the residuals are balanced -- rho is rescaled when the factor leaves [1 / trigger, trigger], and the Riccati
+// factor rebuilt, at most max_refactor times per tail.  out (DEV, 3, may be null): [0] factorisations of the launch,
+// [1] the rho it ended with, [2] its ADMM iterations, all tails.  Travels beside BoxArgs, whose layout every bounded-descent kernel shares.
+struct BoxAdapt {
+    int check_every, max_refactor;
+    double trigger;
+    double* out;
+};
+inline bool irs_admm_adapt_ok(int check_every, double trigger, int max_refactor) {
+    return check_every > 0 && trigger > 1.0 && max_refactor >= 0;
+}
 // boxqp.hip: the ADMM kernel (du: its position-controlled form) on a filled BoxArgs, where the plan puts it.  ws may be
 // null; `policy` says what a workspace that is given is for.  fn: the entry a "model has no such form" error names.
 // The caller has checked the ADMM settings (irs_admm_settings_ok), as every entry does before anything else.
+// adapt: null = fixed rho; else the adaptive form of the kernel (checked by the caller: irs_admm_adapt_ok).
 int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, BoxWs policy,
-                        hipStream_t st);
+                        hipStream_t st, const BoxAdapt* adapt = nullptr);
 
 // ctrlbox.hip: active-set solver for the quasistatic descent with ONE control box.
 // kind 0: bounds on u_t (a.ulo/a.uhi), kind 1: bounds on u_t - u_{t-1} (a.dlo/a.dhi); a bound pair

@@ -46,6 +46,9 @@ class IrsLqrParameters:
         self.xbound = None
         self.ubound = None
         self.solver_name = "osqp"
+        # extension (absent in the reference): the bounded QPs' ADMM adapts its penalty from qp_rho on, as OSQP does
+        # by itself (irs_admm_settings); the loop then runs descent by descent, not through irs_iterate
+        self.qp_adaptive_rho = False
 
 
 class IrsLqr:
@@ -154,11 +157,16 @@ class IrsLqr:
                                         x_trj[0].contiguous(), *box, alpha_R=0.5,
                                         rho=getattr(self.params, "qp_rho", 10.0),
                                         max_iter=getattr(self.params, "qp_max_iter", 5000),
-                                        eps=getattr(self.params, "qp_eps", 1e-8))
+                                        eps=getattr(self.params, "qp_eps", 1e-8),
+                                        adaptive_rho=self._adaptive_rho())
         cost = dev.evaluate_cost(ob["x_new"], ob["u_new"], self._Q, self._R, self._xd)
-        self._last = dict(At=At, Bt=Bt, ct=ct, K=None, k=None, info=ob["info"][:1], box_info=ob["info"])
+        self._last = dict(At=At, Bt=Bt, ct=ct, K=None, k=None, info=ob["info"][:1], box_info=ob["info"],
+                          box_adapt=ob.get("adapt"))
         self._box_used = True
         return ob["x_new"], ob["u_new"], cost
+
+    def _adaptive_rho(self):
+        return bool(getattr(self.params, "qp_adaptive_rho", False))
 
     def _box_bounds(self):
         """(xlo, xhi, ulo, uhi) device vectors (+-inf where a component is unbounded), or None when
@@ -300,7 +308,7 @@ class IrsLqr:
         (`_iterate_fused`); otherwise, per iteration: 2 kernel launches (3 with host-drawn samples' upload)
         and one read-back of (x_new, u_new, cost) for the history lists.  `timing` (a dict, fused path only):
         filled with the library's per-phase device times (irs_timing)."""
-        spec = self._fused_spec()
+        spec = None if self._adaptive_rho() else self._fused_spec()     # irs_iterate's descent has a fixed penalty
         if spec is not None and not self.verbose:
             return self._iterate_fused(max_iterations, spec, timing)
         x_dev = dev.to_dev(np.asarray(self.x_trj, float))

@@ -102,6 +102,8 @@ class IrsLqrQuasistaticParameters:
         # qp_solver: 0 auto, 1 ADMM, 2 active set (lanes), 3 active set (matrix-core tiles); qp_rho, qp_max_iter,
         # qp_eps: ADMM penalty / iteration limit / tolerance of the bounded QPs
         self.qp_solver, self.qp_rho, self.qp_max_iter, self.qp_eps = QP_DEFAULTS
+        # the ADMM (solver 1) adapts its penalty from qp_rho on (irs_admm_settings); the active-set solvers have none
+        self.qp_adaptive_rho = False
 
 
 def decouple_AB_dev(At, Bt, ct, x_trj, u_trj, idx, dim_x, dim_u):
@@ -278,8 +280,10 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
         o = self._dm.quasistatic_box_descent(At, Bt, ct, self._Q, self._Qd, self._R, self._xd,
                                              x_trj[0].contiguous(), *self._bounds_dev(x_trj),
                                              solver=self._solver, rho=rho, max_iter=max_iter, eps=eps,
-                                             act=self._act if self._solver in (2, 3) else None)
-        self._last = dict(At=At, Bt=Bt, ct=ct, info=o["info"])
+                                             act=self._act if self._solver in (2, 3) else None,
+                                             adaptive_rho=self._solver == 1 and
+                                             bool(getattr(self.params, "qp_adaptive_rho", False)))
+        self._last = dict(At=At, Bt=Bt, ct=ct, info=o["info"], adapt=o.get("adapt"))
         return o["x_new"], o["u_new"], o["cost"]
 
     def local_descent(self, x_trj, u_trj):

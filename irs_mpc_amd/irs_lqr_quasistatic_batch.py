@@ -93,6 +93,9 @@ class IrsLqrQuasistaticBatch:
             raise NotImplementedError("the batched descent takes ONE control box: u_bounds_abs or u_bounds_rel")
         if int(qp_settings(p0)[0]) not in (0, 3):
             raise NotImplementedError("the batched descent is solver 3's method (qp_solver 0 or 3)")
+        if any(getattr(p, "qp_adaptive_rho", False) for p in ps):
+            raise NotImplementedError("qp_adaptive_rho belongs to the ADMM (solver 1); the batched descent is solver "
+                                      "3's method")
         dm = q_dynamics.dm()
         if not dm.quasistatic_descent_supported(p0.T, 3):
             raise NotImplementedError("the model does not fit the matrix-core tile of the batched descent")
