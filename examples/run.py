@@ -34,11 +34,16 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--csv", default=None)
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--lazy-bounds", action="store_true",
+                    help="irs-lqr methods: params.qp_lazy_bounds = True -- the bounded QPs put their penalty only on the "
+                         "bounds a plan would break (the scripts' +-1e4 / +-1e5 'no bound' entries then cost nothing)")
     a = ap.parse_args()
 
     sysd, params, sm, cem, iters = PROBLEMS[a.system](*([a.T] if a.T else []))
     iters = a.iters if a.iters is not None else iters
     N = a.N or sm["N"]
+    if a.lazy_bounds:
+        params.qp_lazy_bounds = True
     np.random.seed(a.seed)
     if a.method == "cem":
         cp = amd.CemParameters()

@@ -132,6 +132,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--csv", default=None)
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--lazy-bounds", action="store_true",
+                    help="irs_lqr: params.qp_lazy_bounds = True, with the ADMM (qp_solver = 1) it belongs to")
     a = ap.parse_args()
 
     h = 0.1
@@ -171,6 +173,8 @@ def main():
         params.publish_every_iteration = False
         if a.device_rng:
             params.device_rng_seed = a.seed
+        if a.lazy_bounds:
+            params.qp_solver, params.qp_lazy_bounds = 1, True
         if a.batch > 0:
             return run_batch(q_dynamics, params, a)
         solver = amd.IrsLqrQuasistatic(q_dynamics=q_dynamics, params=params)

@@ -531,6 +531,55 @@ int irs_quasistatic_box_descent_set(int model, const double *params, int n_param
                                     int solver, const irs_admm_settings *settings,
                                     double *x_new, double *u_new, double *cost, int *info, double *adapt_out,
                                     void *workspace, size_t workspace_bytes, void *stream);
+/* The three entries above with the box bounds enforced lazily (constraint generation inside the kernel).  A component
+ * -- of [x (n) | u (m)], or in the position-controlled form of [x (n) | u abs (m) | du (m)] -- carries the ADMM's rho
+ * term and is projected only while it is in the enforced set S.  When a tail QP has converged, every component with a
+ * finite bound outside S is compared with its bounds on the tail's rows of the plan (plain < / >, no tolerance); those
+ * that leave them join S (their w = clip(z), y = 0), the kernel rebuilds its Riccati factor from the tail's first step
+ * and the same tail goes on, its iterations running on against max_iter.  Exactness: a converged plan that keeps every
+ * dropped bound is feasible for the full QP and optimal for a relaxation of it, hence the full QP's solution, to the
+ * ADMM's tolerance.  S only grows (at most one factorisation per component) and stays for the launch's following
+ * warm-started tails; a tail that ends at max_iter is not checked and counts in info[2]; the first control of a tail
+ * is clipped to all bounds, as ever.  Scripts that write "no bound" as a large finite number keep the rho term off
+ * those components this way -- on them it only damps the iteration.  Works with the fixed and the adaptive penalty.
+ * enforced_io DEV int, (n + m) or position controlled (n + 2 m), may be NULL.  In: nonzero = in S from the start
+ * (ignored where the component has no finite bound; NULL: S starts empty).  Out: 1 where in S when the launch ends,
+ * else 0 -- what the next descent over the same bounds should start from.
+ * lazy_out (3) DEV f64, may be NULL: [0] activation events (one extra factorisation each), [1] the last tail that
+ * activated something, -1 if none, [2] the ADMM iterations of the launch, all tails.
+ * adapt_out as above, written with adaptive == 0 too; its [0] counts the lazy factorisations as well.  The two new
+ * arguments stand before `stream`, which stays last as in every entry.  Results need not equal the _set entries' bit
+ * for bit (the iteration differs); records on chip or in the workspace give identical bits.                          */
+int irs_tvlqr_box_descent_lazy(int model, const double *params, int n_params, int T,
+                               const double *At, const double *Bt, const double *ct,
+                               const double *Q, const double *Qd, const double *R, double alpha_R,
+                               const double *xd_trj, const double *x0,
+                               const double *xlo, const double *xhi, const double *ulo, const double *uhi,
+                               const irs_admm_settings *settings,
+                               double *x_new, double *u_new, int *info, double *adapt_out,
+                               void *workspace, size_t workspace_bytes,
+                               int *enforced_io, double *lazy_out, void *stream);
+int irs_tvlqr_box_solve_lazy(int model, const double *params, int n_params, int T,
+                             const double *At, const double *Bt, const double *ct,
+                             const double *Q, const double *Qd, const double *R, double alpha_R,
+                             const double *xd_trj, const double *x0, int position_controlled,
+                             const double *x_lo, const double *x_hi, const double *u_lo, const double *u_hi,
+                             const double *du_lo, const double *du_hi,
+                             const irs_admm_settings *settings,
+                             double *x_star, double *u_star, int *info, double *adapt_out,
+                             void *workspace, size_t workspace_bytes,
+                             int *enforced_io, double *lazy_out, void *stream);
+int irs_quasistatic_box_descent_lazy(int model, const double *params, int n_params, int T,
+                                     const double *At, const double *Bt, const double *ct,
+                                     const double *Q, const double *Qd, const double *R,
+                                     const double *xd_trj, const double *x0,
+                                     const double *x_lo, const double *x_hi,
+                                     const double *u_lo, const double *u_hi,
+                                     const double *du_lo, const double *du_hi,
+                                     int solver, const irs_admm_settings *settings,
+                                     double *x_new, double *u_new, double *cost, int *info, double *adapt_out,
+                                     void *workspace, size_t workspace_bytes,
+                                     int *enforced_io, double *lazy_out, void *stream);
 /* IrsLqrZeroOrder.compute_least_squares (irs_lqr/irs_lqr_zero_order.py:27-36) stand-alone: dxdu (N, n+m),
  * deltaf (N, n) DEV f64 -> A (n,n), B (n,m) with [A | B] = lstsq(dxdu, deltaf)[0]'.  Normal equations in f64,
  * Jacobi-scaled Cholesky (the solve the sample pass ends with).  info (1): 0, the failed pivot (1-based: a

@@ -221,6 +221,10 @@ SIGNATURES["irs_quasistatic_box_descent_set"] = (c_int, [c_int, POINTER(c_double
                                                          _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, c_int,
                                                          POINTER(AdmmSettings), _dp, _dp, _dp, _dp, _dp, _dp, c_size_t,
                                                          c_void_p])
+# the _set entries with lazily enforced bounds: + enforced_io (DEV int), lazy_out (DEV f64, 3) before the stream
+for _name in ("irs_tvlqr_box_descent", "irs_tvlqr_box_solve", "irs_quasistatic_box_descent"):
+    _res, _args = SIGNATURES[_name + "_set"]
+    SIGNATURES[_name + "_lazy"] = (_res, _args[:-1] + [_dp, _dp] + _args[-1:])
 SIGNATURES["irs_least_squares"] = (c_int, [c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_smooth_run"] = (c_int, [POINTER(SmoothCall), c_void_p])
 SIGNATURES["irs_descent_run"] = (c_int, [POINTER(DescentCall), c_void_p])

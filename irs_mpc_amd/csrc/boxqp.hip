@@ -58,8 +58,19 @@ typedef __attribute__((address_space(1))) v2d gv2d;    // global: a generic poin
 
 // ADAPT: the penalty rho follows the residuals (the rule: see the MPC loop below), and the factorisation runs again
 // with each new rho.  ADAPT = false reads nothing of `ad` and is the fixed-rho kernel, instruction for instruction.
-template <class Model, bool DU, bool HBM, bool ADAPT>
-__global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs, BoxAdapt ad) {
+//
+// LAZY (on top of ADAPT): the bounds are enforced lazily -- constraint generation.  Only the components of a set S
+// carry a rho term and are projected: mxv / muv are then "finite bound AND in S" (what the factorisation, the sweeps,
+// the projection, the residuals and the adaptive rule's norms read), and the "finite bound" masks move to fxv / fuv.
+// When a tail has converged, every dropped component's plan entry is compared with its bounds; components that leave
+// them join S (w = clip(z), y = 0 on the tail's rows), the factorisation runs again from the tail's first step, and
+// the same tail goes on.  A converged plan that keeps every dropped bound is feasible for the full QP and optimal for
+// a relaxation of it: it is the full QP's solution, to the ADMM's tolerance.  S only grows, and stays for the tails
+// that follow.  LAZY = false reads nothing of ad.lazy (the parameter is then a plain BoxAdapt).
+template <class Model, bool DU, bool HBM, bool ADAPT, bool LAZY = false>
+__global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs,
+                                                         std::conditional_t<LAZY, BoxAdaptLazy, BoxAdapt> ad) {
+    static_assert(ADAPT || !LAZY, "the lazy form is compiled on top of the adaptive one");
     if (a.run_flag != nullptr && *a.run_flag == 0) return;          // uniform
     constexpr int NR = Model::NX, M = Model::NU;      // real state / control sizes
     constexpr int N = NR + (DU ? M : 0);              // size of the QP's state (z = [x; u_prev] if DU)
@@ -114,6 +125,10 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
     double* mxv = sv + N;                              // bounded masks (any finite bound at any t)
     double* muv = mxv + N;                             // (M)
     double* Hs = muv + M;                              // M x M scratch (<= 16)
+    double* fxv = Hs + M * M;                          // LAZY: the finite-bound masks (N), (M), in the layout's slack
+    double* fuv = fxv + N;
+    static_assert(!LAZY || (5 * N + 2 * M + M * M <= 8 * N + 4 * M + 64 && M <= N), "no room for the lazy masks");
+    (void)fxv; (void)fuv;
 
     // ---- setup ------------------------------------------------------------------------
     if (lane < N) {
@@ -125,6 +140,17 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
         bool any = false;
         for (int t = 0; t < T; ++t) any = any || isfinite(vlo_(t, lane)) || isfinite(vhi_(t, lane));
         muv[lane] = any ? 1.0 : 0.0;
+    }
+    if constexpr (LAZY) {                              // (each lane: the entry it has just written)
+        const int* e = ad.lazy.enforced_io;
+        if (lane < N) {
+            fxv[lane] = mxv[lane];
+            if (e == nullptr || e[lane] == 0) mxv[lane] = 0.0;
+        }
+        if (lane < M) {
+            fuv[lane] = muv[lane];
+            if (e == nullptr || e[N + lane] == 0) muv[lane] = 0.0;
+        }
     }
     for (int q = lane; q < (T + 1) * N; q += 64) { wx[q] = 0.0; yx[q] = 0.0; zx[q] = 0.0; }
     for (int q = lane; q < T * M; q += 64) { wu[q] = 0.0; yu[q] = 0.0; zu[q] = 0.0; kk[q] = 0.0; }
@@ -179,6 +205,7 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
     const double al = a.relax;
     int n_factor = 1;                                  // ADAPT: factorisations and ADMM iterations of the launch,
     long long n_iter = 0;                              // reported in ad.out
+    int n_lazy = 0, last_lazy = -1;                    // LAZY: activation events, the last tail that had one
     for (int tau = 0; tau < T; ++tau) {
         // the tail problem starts from the realised state; for DU its u_prev block is the
         // realised actuated position x_tau[idx] (tv_lqr.py:99-100 at the tail's local t = 0)
@@ -349,6 +376,56 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
                     }
                 }
             }
+            if constexpr (LAZY) {
+                // A converged tail: the dropped components (finite bound, not enforced) against their bounds on the
+                // tail's rows of the plan, no tolerance.  The flags go through gv / sv, idle between sweeps; every
+                // lane reads the same flags back, so the decision is uniform.
+                if (conv) {
+                    if (lane < N) gv[lane] = 0.0;
+                    else if (lane < N + M) sv[lane - N] = 0.0;
+                    wave_sync();
+                    for (int q = (tau + 1) * N + lane; q < (T + 1) * N; q += 64) {
+                        const int i = q % N, t = q / N;
+                        if (fxv[i] != 0.0 && mxv[i] == 0.0 && (zx[q] < zlo_(t, i) || zx[q] > zhi_(t, i))) gv[i] = 1.0;
+                    }
+                    for (int q = tau * M + lane; q < T * M; q += 64) {
+                        const int j = q % M, t = q / M;
+                        if (fuv[j] != 0.0 && muv[j] == 0.0 && (zu[q] < vlo_(t, j) || zu[q] > vhi_(t, j))) sv[j] = 1.0;
+                    }
+                    wave_sync();
+                    bool grow = false;
+                    for (int i = 0; i < N; ++i) grow = grow || gv[i] != 0.0;
+                    for (int j = 0; j < M; ++j) grow = grow || sv[j] != 0.0;
+                    if (grow) {
+                        // they join the set: w = clip(z), y = 0 on the tail's rows, and a factor with their rho terms
+                        for (int q = (tau + 1) * N + lane; q < (T + 1) * N; q += 64) {
+                            const int i = q % N, t = q / N;
+                            if (gv[i] != 0.0) {
+                                wx[q] = fmin(fmax(zx[q], zlo_(t, i)), zhi_(t, i));
+                                yx[q] = 0.0;
+                            }
+                        }
+                        for (int q = tau * M + lane; q < T * M; q += 64) {
+                            const int j = q % M, t = q / M;
+                            if (sv[j] != 0.0) {
+                                wu[q] = fmin(fmax(zu[q], vlo_(t, j)), vhi_(t, j));
+                                yu[q] = 0.0;
+                            }
+                        }
+                        if (lane < N) { if (gv[lane] != 0.0) mxv[lane] = 1.0; }
+                        else if (lane < N + M) { if (sv[lane - N] != 0.0) muv[lane - N] = 1.0; }
+                        wave_sync();
+                        // HBM: the ring is where a forward sweep leaves it, as for a new rho above
+#define BOX_FACTOR_FROM tau
+#include "boxqp_factor.inc"
+#undef BOX_FACTOR_FROM
+                        ++n_factor;
+                        ++n_lazy;
+                        last_lazy = tau;
+                        conv = false;
+                    }
+                }
+            }
         }
         it_max = max(it_max, it);
         if constexpr (ADAPT) n_iter += it;
@@ -364,6 +441,14 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
             }
             if constexpr (ADAPT) {
                 if (lane == 0 && ad.out != nullptr) { ad.out[0] = (double)n_factor; ad.out[1] = rho; ad.out[2] = (double)n_iter; }
+            }
+            if constexpr (LAZY) {
+                int* e = ad.lazy.enforced_io;
+                if (e != nullptr && lane < N) e[lane] = mxv[lane] != 0.0 ? 1 : 0;
+                if (e != nullptr && lane < M) e[N + lane] = muv[lane] != 0.0 ? 1 : 0;
+                if (lane == 0 && ad.lazy.out != nullptr) {
+                    ad.lazy.out[0] = (double)n_lazy; ad.lazy.out[1] = (double)last_lazy; ad.lazy.out[2] = (double)n_iter;
+                }
             }
             return;
         }
@@ -410,21 +495,38 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
     if constexpr (ADAPT) {
         if (lane == 0 && ad.out != nullptr) { ad.out[0] = (double)n_factor; ad.out[1] = rho; ad.out[2] = (double)n_iter; }
     }
+    if constexpr (LAZY) {
+        int* e = ad.lazy.enforced_io;
+        if (e != nullptr && lane < N) e[lane] = mxv[lane] != 0.0 ? 1 : 0;
+        if (e != nullptr && lane < M) e[N + lane] = muv[lane] != 0.0 ? 1 : 0;
+        if (lane == 0 && ad.lazy.out != nullptr) {
+            ad.lazy.out[0] = (double)n_lazy; ad.lazy.out[1] = (double)last_lazy; ad.lazy.out[2] = (double)n_iter;
+        }
+    }
 }
 
-template <class Model, bool DU, bool HBM, bool ADAPT>
-int launch_box_kernel(const BoxArgs& a, double* recs, size_t bytes, const BoxAdapt& ad, hipStream_t st) {
-    constexpr auto kern = box_descent_kernel<Model, DU, HBM, ADAPT>;
+template <class Model, bool DU, bool HBM, bool ADAPT, bool LAZY = false>
+int launch_box_kernel(const BoxArgs& a, double* recs, size_t bytes,
+                      const std::conditional_t<LAZY, BoxAdaptLazy, BoxAdapt>& ad, hipStream_t st) {
+    constexpr auto kern = box_descent_kernel<Model, DU, HBM, ADAPT, LAZY>;
     const int rc = irs_raise_lds_limit<kern>(bytes, "irs_tvlqr_box_descent");
     if (rc != IRS_OK) return rc;
     hipLaunchKernelGGL(kern, dim3(1), dim3(64), bytes, st, a, recs, ad);
     return IRS_OK;
 }
 
-// adapt: null = the fixed-rho kernel
+// adapt: null = the fixed-rho kernel; lazy: null = every finite bound enforced, else the lazy form (with adapt)
 template <class Model, bool DU>
-int launch_box(const BoxArgs& a, const BoxPlan& p, double* ws, const BoxAdapt* adapt, hipStream_t st) {
+int launch_box(const BoxArgs& a, const BoxPlan& p, double* ws, const BoxAdapt* adapt, const BoxLazy* lazy,
+               hipStream_t st) {
     const bool hbm = p.place == BoxPlace::AdmmHbm;
+    if (lazy != nullptr) {
+        BoxAdaptLazy al;
+        static_cast<BoxAdapt&>(al) = *adapt;
+        al.lazy = *lazy;
+        return hbm ? launch_box_kernel<Model, DU, true, true, true>(a, ws, p.lds, al, st)
+                   : launch_box_kernel<Model, DU, false, true, true>(a, nullptr, p.lds, al, st);
+    }
     if (adapt == nullptr)
         return hbm ? launch_box_kernel<Model, DU, true, false>(a, ws, p.lds, BoxAdapt{}, st)
                    : launch_box_kernel<Model, DU, false, false>(a, nullptr, p.lds, BoxAdapt{}, st);
@@ -507,7 +609,7 @@ static WsFit ws_fit(const BoxPlan& p, size_t count, const void* ws, size_t ws_by
 // The ADMM kernel on a filled BoxArgs, where the plan puts it: records on chip, or in `ws` -- whenever one is given
 // (policy Always), or only where they do not fit LDS (IfNeeded).  du: the position-controlled form.
 int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, BoxWs policy,
-                        hipStream_t st, const BoxAdapt* adapt) {
+                        hipStream_t st, const BoxAdapt* adapt, const BoxLazy* lazy) {
     const BoxPlan p = irs_box_plan(model, a.T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM,
                                    ws == nullptr ? BoxWs::None : policy);
     if (p.max_T == 0) {
@@ -537,10 +639,10 @@ int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, vo
     double* recs = static_cast<double*>(ws);
     int rc = IRS_ERR_UNSUPPORTED;
     if (!du) {
-        IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, p, recs, adapt, st); });
+        IRS_DISPATCH_MODEL(model, { rc = launch_box<Model, false>(a, p, recs, adapt, lazy, st); });
     } else {
         IRS_DISPATCH_MODEL(model, {
-            if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, p, recs, adapt, st);
+            if constexpr (has_u_into_x<Model>::value) rc = launch_box<Model, true>(a, p, recs, adapt, lazy, st);
         });
     }
     if (rc != IRS_OK) return rc;
@@ -618,6 +720,14 @@ static int read_admm_settings(const char* fn, const irs_admm_settings* s, double
     *ad = BoxAdapt{s->check_every, s->max_refactor, s->trigger, adapt_out};
     *adapt = ad;
     return IRS_OK;
+}
+
+// The lazy entries: the kernel's lazy form is compiled on top of the adaptive one, so a fixed penalty (adaptive == 0:
+// *adapt null after read_admm_settings) runs there with a rule that never fires -- max_refactor = 0.
+static void lazy_adapt(double* adapt_out, BoxAdapt* ad, const BoxAdapt** adapt) {
+    if (*adapt != nullptr) return;
+    *ad = BoxAdapt{1, 0, 2.0, adapt_out};
+    *adapt = ad;
 }
 
 extern "C" {
@@ -971,6 +1081,97 @@ int irs_tvlqr_box_solve_set(int model, const double* params, int n_params, int T
     a.x_new = x_star; a.u_new = u_star; a.info = info; a.single_tail = 1;
     return irs_box_admm_launch("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes,
                                BoxWs::Always, static_cast<hipStream_t>(stream), adapt);
+}
+
+// ---- lazily enforced bounds: the _set entries plus the set and its counters ------------------------------------------
+int irs_tvlqr_box_descent_lazy(int model, const double* params, int n_params, int T, const double* At,
+                               const double* Bt, const double* ct, const double* Q, const double* Qd,
+                               const double* R, double alpha_R, const double* xd_trj, const double* x0,
+                               const double* xlo, const double* xhi, const double* ulo, const double* uhi,
+                               const irs_admm_settings* settings, double* x_new, double* u_new, int* info,
+                               double* adapt_out, void* workspace, size_t workspace_bytes, int* enforced_io,
+                               double* lazy_out, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
+                  x_new && u_new && info, "bad argument");
+    BoxAdapt ad;
+    const BoxAdapt* adapt;
+    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
+    if (rc != IRS_OK) return rc;
+    rc = check_box_workspace(__func__, model, T, 0, workspace, workspace_bytes);
+    if (rc != IRS_OK) return rc;
+    BoxArgs a;
+    rc = box_begin(&a, model, params, n_params, T, false);
+    if (rc != IRS_OK) return rc;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi;
+    a.alpha = alpha_R; a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter;
+    a.eps = settings->eps;
+    a.x_new = x_new; a.u_new = u_new; a.info = info;
+    lazy_adapt(adapt_out, &ad, &adapt);
+    const BoxLazy lazy{enforced_io, lazy_out};
+    return irs_box_admm_launch("irs_tvlqr_box_descent", model, false, a, workspace, workspace_bytes, BoxWs::Always,
+                               static_cast<hipStream_t>(stream), adapt, &lazy);
+}
+
+int irs_tvlqr_box_solve_lazy(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
+                             const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
+                             const double* xd_trj, const double* x0, int position_controlled,
+                             const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
+                             const double* du_lo, const double* du_hi, const irs_admm_settings* settings,
+                             double* x_star, double* u_star, int* info, double* adapt_out, void* workspace,
+                             size_t workspace_bytes, int* enforced_io, double* lazy_out, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_star && u_star && info, "bad argument");
+    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
+                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
+    IRS_CHECK_ARG(position_controlled || du_lo == nullptr, "du bounds need the position-controlled form");
+    BoxAdapt ad;
+    const BoxAdapt* adapt;
+    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
+    if (rc != IRS_OK) return rc;
+    rc = check_box_workspace(__func__, model, T, position_controlled ? 1 : 0, workspace, workspace_bytes);
+    if (rc != IRS_OK) return rc;
+    BoxArgs a;
+    rc = box_begin(&a, model, params, n_params, T, true);
+    if (rc != IRS_OK) return rc;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
+    a.alpha = alpha_R; a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter;
+    a.eps = settings->eps;
+    a.x_new = x_star; a.u_new = u_star; a.info = info; a.single_tail = 1;
+    lazy_adapt(adapt_out, &ad, &adapt);
+    const BoxLazy lazy{enforced_io, lazy_out};
+    return irs_box_admm_launch("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes,
+                               BoxWs::Always, static_cast<hipStream_t>(stream), adapt, &lazy);
+}
+
+int irs_quasistatic_box_descent_lazy(int model, const double* params, int n_params, int T, const double* At,
+                                     const double* Bt, const double* ct, const double* Q, const double* Qd,
+                                     const double* R, const double* xd_trj, const double* x0,
+                                     const double* x_lo, const double* x_hi, const double* u_lo,
+                                     const double* u_hi, const double* du_lo, const double* du_hi,
+                                     int solver, const irs_admm_settings* settings, double* x_new, double* u_new,
+                                     double* cost, int* info, double* adapt_out, void* workspace,
+                                     size_t workspace_bytes, int* enforced_io, double* lazy_out, void* stream) {
+    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_new && u_new && info, "bad argument");
+    IRS_CHECK_ARG(solver == 1, "solver must be 1 (ADMM): the lazily enforced bounds are the ADMM kernel's");
+    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
+                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
+    BoxAdapt ad;
+    const BoxAdapt* adapt;
+    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
+    if (rc != IRS_OK) return rc;
+    BoxArgs a;
+    rc = box_begin(&a, model, params, n_params, T, true);
+    if (rc != IRS_OK) return rc;
+    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
+    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
+    a.alpha = 1.0;      // tv_lqr.py:107, as irs_quasistatic_box_descent_wsx
+    a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter; a.eps = settings->eps;
+    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info;
+    lazy_adapt(adapt_out, &ad, &adapt);
+    const BoxLazy lazy{enforced_io, lazy_out};
+    return irs_box_admm_launch("irs_quasistatic_box_descent", model, true, a, workspace, workspace_bytes,
+                               BoxWs::IfNeeded, static_cast<hipStream_t>(stream), adapt, &lazy);
 }
 
 }  // extern "C"

@@ -65,12 +65,26 @@ struct BoxAdapt {
 inline bool irs_admm_adapt_ok(int check_every, double trigger, int max_refactor) {
     return check_every > 0 && trigger > 1.0 && max_refactor >= 0;
 }
+// Lazily enforced bounds (the LAZY form of the ADMM kernel, compiled on top of the adaptive one; a fixed penalty is
+// max_refactor = 0).  Components: the QP's state, then its control -- [x (n) | u (m)], or position controlled
+// [x (n) | u abs (m) | du (m)].  enforced_io (DEV, may be null): in, nonzero = enforced from the start (ignored where
+// the component has no finite bound; null: none); out, 1 where enforced when the launch ends, else 0.  out (DEV, 3, may
+// be null): [0] activation events (each one factorisation), [1] the last tail that activated something or -1, [2] the
+// ADMM iterations of the launch.  The lazy kernel takes BoxAdaptLazy where the others take BoxAdapt.
+struct BoxLazy {
+    int* enforced_io;
+    double* out;
+};
+struct BoxAdaptLazy : BoxAdapt {
+    BoxLazy lazy;
+};
 // boxqp.hip: the ADMM kernel (du: its position-controlled form) on a filled BoxArgs, where the plan puts it.  ws may be
 // null; `policy` says what a workspace that is given is for.  fn: the entry a "model has no such form" error names.
 // The caller has checked the ADMM settings (irs_admm_settings_ok), as every entry does before anything else.
 // adapt: null = fixed rho; else the adaptive form of the kernel (checked by the caller: irs_admm_adapt_ok).
+// lazy: null = every finite bound enforced; else the lazy form (adapt must be given: max_refactor = 0 for a fixed rho).
 int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, BoxWs policy,
-                        hipStream_t st, const BoxAdapt* adapt = nullptr);
+                        hipStream_t st, const BoxAdapt* adapt = nullptr, const BoxLazy* lazy = nullptr);
 
 // ctrlbox.hip: active-set solver for the quasistatic descent with ONE control box.
 // kind 0: bounds on u_t (a.ulo/a.uhi), kind 1: bounds on u_t - u_{t-1} (a.dlo/a.dhi); a bound pair

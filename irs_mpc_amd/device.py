@@ -271,20 +271,51 @@ class DeviceModel:
             need = self.lib.irs_tvlqr_box_workspace_bytes(self.model_id, int(T), 1 if du else 0)
         return self._cached_workspace("box", need, device)
 
+    @staticmethod
+    def _lazy_outputs(o, enforced, count, device):
+        """The two outputs of a lazy launch in `o`: enforced (count,) int32, in/out -- a copy of `enforced` (None: all
+        zero, the set starts empty) -- and lazy (3,) f64."""
+        if enforced is None:
+            o["enforced"] = torch.zeros((count,), dtype=torch.int32, device=device)
+        else:
+            o["enforced"] = torch.as_tensor(enforced).to(device=device, dtype=torch.int32, copy=True).contiguous()
+            if tuple(o["enforced"].shape) != (count,):
+                raise ValueError("enforced must have %d entries, not %s" % (count, tuple(o["enforced"].shape)))
+        o["lazy"] = torch.empty((3,), dtype=F64, device=device)
+
     def tvlqr_box_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, xlo, xhi, ulo, uhi, alpha_R=0.5,
-                          rho=10.0, relax=1.6, max_iter=5000, eps=1e-8, records_in_hbm=False, adaptive_rho=False):
+                          rho=10.0, relax=1.6, max_iter=5000, eps=1e-8, records_in_hbm=False, adaptive_rho=False,
+                          lazy_bounds=False, enforced=None):
         """local_descent with active abs bounds (T warm-started tail QPs by ADMM around one
         Riccati factorisation).  Beyond the LDS horizon the factor records go to a cached workspace in HBM;
         records_in_hbm=True puts them there at any horizon (same result, bit for bit).  Returns
         dict(x_new, u_new, info[3]).  adaptive_rho: the penalty follows the residuals from `rho` on, the kernel
         refactorising as it moves (irs_admm_settings); the result then also holds adapt[3] = (factorisations of the
-        launch, final rho, ADMM iterations of all tails)."""
+        launch, final rho, ADMM iterations of all tails).  lazy_bounds: the bounds are enforced lazily
+        (irs_tvlqr_box_descent_lazy) -- only components whose bound a converged tail plan would break carry the
+        penalty term, so "no bound" written as a large finite number costs nothing; `enforced` (n + m, nonzero = in
+        the set from the start, e.g. the previous descent's result) seeds the set.  The result then also holds
+        enforced[n + m] (int32: the final set), lazy[3] = (activations, last tail that activated, ADMM iterations)
+        and adapt[3]."""
         T = At.shape[0]
         dev = At.device
         o = dict(x_new=torch.empty((T + 1, self.n), dtype=F64, device=dev),
                  u_new=torch.empty((T, self.m), dtype=F64, device=dev),
                  info=torch.empty((3,), dtype=torch.int32, device=dev))
         ws = self._box_workspace(T, False, dev, force=records_in_hbm)
+        if lazy_bounds:
+            o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
+            self._lazy_outputs(o, enforced, self.n + self.m, dev)
+            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=bool(adaptive_rho))
+            check(self.lib.irs_tvlqr_box_descent_lazy(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
+                                                      _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
+                                                      float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(xlo, F64),
+                                                      _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64), ctypes.byref(st),
+                                                      _ptr(o["x_new"], F64), _ptr(o["u_new"], F64), o["info"].data_ptr(),
+                                                      _ptr(o["adapt"], F64), *_ws_args(ws), o["enforced"].data_ptr(),
+                                                      _ptr(o["lazy"], F64), _stream()),
+                  "irs_tvlqr_box_descent_lazy")
+            return o
         if adaptive_rho:
             o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
             st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=True)
@@ -307,17 +338,33 @@ class DeviceModel:
 
     def tvlqr_box_solve(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo=None, x_hi=None, u_lo=None, u_hi=None,
                         du_lo=None, du_hi=None, position_controlled=False, alpha_R=0.5, rho=10.0, relax=1.6,
-                        max_iter=5000, eps=1e-8, adaptive_rho=False, records_in_hbm=False):
+                        max_iter=5000, eps=1e-8, adaptive_rho=False, records_in_hbm=False, lazy_bounds=False,
+                        enforced=None):
         """solve_tvlqr stand-alone: ONE bounded QP by ADMM, its plan returned.  Bounds are per-time rows or None;
         du bounds need the position-controlled form.  Beyond the LDS horizon the factor records go to a cached
         workspace in HBM (records_in_hbm=True: at any horizon).  Returns dict(x_star, u_star, info[3]); adaptive_rho
-        as in tvlqr_box_descent (adds adapt[3])."""
+        as in tvlqr_box_descent (adds adapt[3]); lazy_bounds / enforced likewise (adds enforced, lazy and adapt; the
+        components are [x | u], position controlled [x | u abs | du])."""
         T = At.shape[0]
         dev = At.device
         o = dict(x_star=torch.zeros((T + 1, At.shape[1]), dtype=F64, device=dev),
                  u_star=torch.zeros((T, Bt.shape[2]), dtype=F64, device=dev),
                  info=torch.full((3,), -1, dtype=torch.int32, device=dev))
         ws = self._box_workspace(T, position_controlled, dev, force=records_in_hbm)   # None while they fit on chip
+        if lazy_bounds:
+            o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
+            self._lazy_outputs(o, enforced, At.shape[1] + (2 if position_controlled else 1) * Bt.shape[2], dev)
+            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=bool(adaptive_rho))
+            check(self.lib.irs_tvlqr_box_solve_lazy(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
+                                                    _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
+                                                    float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64),
+                                                    1 if position_controlled else 0, _ptr(x_lo, F64), _ptr(x_hi, F64),
+                                                    _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64),
+                                                    ctypes.byref(st), _ptr(o["x_star"], F64), _ptr(o["u_star"], F64),
+                                                    o["info"].data_ptr(), _ptr(o["adapt"], F64), *_ws_args(ws),
+                                                    o["enforced"].data_ptr(), _ptr(o["lazy"], F64), _stream()),
+                  "irs_tvlqr_box_solve_lazy")
+            return o
         if adaptive_rho:
             o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
             st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=True)
@@ -355,14 +402,15 @@ class DeviceModel:
 
     def quasistatic_box_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo=None, x_hi=None, u_lo=None,
                                 u_hi=None, du_lo=None, du_hi=None, solver=0, rho=10.0, relax=1.6,
-                                max_iter=5000, eps=1e-8, out=None, act=None, adaptive_rho=False):
+                                max_iter=5000, eps=1e-8, out=None, act=None, adaptive_rho=False, lazy_bounds=False,
+                                enforced=None):
         """IrsLqrQuasistatic.local_descent after get_TV_matrices (irs_lqr_quasistatic.py:286-345) +
         eval_cost.  Bounds are absolute per-time rows ((T+1,n) / (T,m)) or None.  solver: 0 auto,
         1 ADMM (beyond the LDS horizon with its records in HBM), 2 active set (one control box, no x bounds; lanes,
         LDS-resident), 3 the same on matrix-core tiles (any horizon).  `act` (T,m) f64 in {-1,0,+1}, in/out: the active set the first tail starts
         from / converged to (hand it from one iteration's descent to the next; zeros = cold start).
         Returns dict(x_new, u_new, cost, info[3]).  adaptive_rho (solver 1 only) as in tvlqr_box_descent (adds
-        adapt[3])."""
+        adapt[3]); lazy_bounds / enforced (solver 1 only) likewise, the components [x (n) | u abs (m) | du (m)]."""
         T = At.shape[0]
         dev = At.device
         o = out
@@ -376,6 +424,21 @@ class DeviceModel:
             assert b is None or tuple(b.shape) == shape, (tuple(b.shape), shape)
         assert act is None or tuple(act.shape) == (T, self.m)
         ws = self._descent_workspace(T, solver, dev) if int(solver) in (0, 1, 3) else None
+        if lazy_bounds:
+            if int(solver) != 1:
+                raise ValueError("lazy_bounds belongs to the ADMM kernel: solver must be 1, not %d" % int(solver))
+            if "adapt" not in o:
+                o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
+            self._lazy_outputs(o, enforced, self.n + 2 * self.m, dev)
+            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=bool(adaptive_rho))
+            check(self.lib.irs_quasistatic_box_descent_lazy(
+                self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64), _ptr(ct, F64), _ptr(Q, F64),
+                _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(x_lo, F64), _ptr(x_hi, F64),
+                _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64), 1, ctypes.byref(st),
+                _ptr(o["x_new"], F64), _ptr(o["u_new"], F64), _ptr(o["cost"], F64), o["info"].data_ptr(),
+                _ptr(o["adapt"], F64), *_ws_args(ws), o["enforced"].data_ptr(), _ptr(o["lazy"], F64), _stream()),
+                "irs_quasistatic_box_descent_lazy")
+            return o
         if adaptive_rho:
             if int(solver) != 1:
                 raise ValueError("adaptive_rho belongs to the ADMM kernel: solver must be 1, not %d" % int(solver))

@@ -49,6 +49,10 @@ class IrsLqrParameters:
         # extension (absent in the reference): the bounded QPs' ADMM adapts its penalty from qp_rho on, as OSQP does
         # by itself (irs_admm_settings); the loop then runs descent by descent, not through irs_iterate
         self.qp_adaptive_rho = False
+        # extension: the bounded QPs enforce their bounds lazily (irs_tvlqr_box_descent_lazy) -- only the components a
+        # converged plan would push out of the box carry the ADMM's penalty term; each descent hands its final set to
+        # the next.  Like qp_adaptive_rho it runs descent by descent
+        self.qp_lazy_bounds = False
 
 
 class IrsLqr:
@@ -158,15 +162,26 @@ class IrsLqr:
                                         rho=getattr(self.params, "qp_rho", 10.0),
                                         max_iter=getattr(self.params, "qp_max_iter", 5000),
                                         eps=getattr(self.params, "qp_eps", 1e-8),
-                                        adaptive_rho=self._adaptive_rho())
+                                        adaptive_rho=self._adaptive_rho(), **self._lazy_kw())
+        self._enforced = ob.get("enforced")             # lazy bounds: the set the next descent starts from
         cost = dev.evaluate_cost(ob["x_new"], ob["u_new"], self._Q, self._R, self._xd)
         self._last = dict(At=At, Bt=Bt, ct=ct, K=None, k=None, info=ob["info"][:1], box_info=ob["info"],
-                          box_adapt=ob.get("adapt"))
+                          box_adapt=ob.get("adapt"), box_enforced=ob.get("enforced"), box_lazy=ob.get("lazy"))
         self._box_used = True
         return ob["x_new"], ob["u_new"], cost
 
     def _adaptive_rho(self):
         return bool(getattr(self.params, "qp_adaptive_rho", False))
+
+    def _lazy_bounds(self):
+        return bool(getattr(self.params, "qp_lazy_bounds", False))
+
+    def _lazy_kw(self):
+        """The lazy keywords of the bounded descent: none unless params.qp_lazy_bounds, else the flag and the set the
+        previous bounded descent ended with (None before the first)."""
+        if not self._lazy_bounds():
+            return {}
+        return dict(lazy_bounds=True, enforced=getattr(self, "_enforced", None))
 
     def _box_bounds(self):
         """(xlo, xhi, ulo, uhi) device vectors (+-inf where a component is unbounded), or None when
@@ -308,7 +323,8 @@ class IrsLqr:
         (`_iterate_fused`); otherwise, per iteration: 2 kernel launches (3 with host-drawn samples' upload)
         and one read-back of (x_new, u_new, cost) for the history lists.  `timing` (a dict, fused path only):
         filled with the library's per-phase device times (irs_timing)."""
-        spec = None if self._adaptive_rho() else self._fused_spec()     # irs_iterate's descent has a fixed penalty
+        # irs_iterate's descent has a fixed penalty and enforces every finite bound
+        spec = None if self._adaptive_rho() or self._lazy_bounds() else self._fused_spec()
         if spec is not None and not self.verbose:
             return self._iterate_fused(max_iterations, spec, timing)
         x_dev = dev.to_dev(np.asarray(self.x_trj, float))

@@ -104,6 +104,9 @@ class IrsLqrQuasistaticParameters:
         self.qp_solver, self.qp_rho, self.qp_max_iter, self.qp_eps = QP_DEFAULTS
         # the ADMM (solver 1) adapts its penalty from qp_rho on (irs_admm_settings); the active-set solvers have none
         self.qp_adaptive_rho = False
+        # the ADMM (solver 1) enforces its bounds lazily (irs_quasistatic_box_descent_lazy): only the components a
+        # converged plan would push out of the box carry the penalty term; a descent hands its final set to the next
+        self.qp_lazy_bounds = False
 
 
 def decouple_AB_dev(At, Bt, ct, x_trj, u_trj, idx, dim_x, dim_u):
@@ -282,9 +285,19 @@ class IrsLqrQuasistatic(QuasistaticOptimizerBase):
                                              solver=self._solver, rho=rho, max_iter=max_iter, eps=eps,
                                              act=self._act if self._solver in (2, 3) else None,
                                              adaptive_rho=self._solver == 1 and
-                                             bool(getattr(self.params, "qp_adaptive_rho", False)))
-        self._last = dict(At=At, Bt=Bt, ct=ct, info=o["info"], adapt=o.get("adapt"))
+                                             bool(getattr(self.params, "qp_adaptive_rho", False)),
+                                             **self._lazy_kw())
+        self._enforced = o.get("enforced")
+        self._last = dict(At=At, Bt=Bt, ct=ct, info=o["info"], adapt=o.get("adapt"), enforced=o.get("enforced"),
+                          lazy=o.get("lazy"))
         return o["x_new"], o["u_new"], o["cost"]
+
+    def _lazy_kw(self):
+        """The lazy keywords of the descent: only for solver 1 with params.qp_lazy_bounds -- the flag and the set the
+        previous descent ended with (None before the first)."""
+        if self._solver != 1 or not getattr(self.params, "qp_lazy_bounds", False):
+            return {}
+        return dict(lazy_bounds=True, enforced=getattr(self, "_enforced", None))
 
     def local_descent(self, x_trj, u_trj):
         x_new, u_new, _ = self._local_descent_dev(dev.to_dev(np.asarray(x_trj, float)),

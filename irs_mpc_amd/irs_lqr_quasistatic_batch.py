@@ -96,6 +96,9 @@ class IrsLqrQuasistaticBatch:
         if any(getattr(p, "qp_adaptive_rho", False) for p in ps):
             raise NotImplementedError("qp_adaptive_rho belongs to the ADMM (solver 1); the batched descent is solver "
                                       "3's method")
+        if any(getattr(p, "qp_lazy_bounds", False) for p in ps):
+            raise NotImplementedError("qp_lazy_bounds belongs to the ADMM (solver 1); the batched descent is solver "
+                                      "3's method")
         dm = q_dynamics.dm()
         if not dm.quasistatic_descent_supported(p0.T, 3):
             raise NotImplementedError("the model does not fit the matrix-core tile of the batched descent")

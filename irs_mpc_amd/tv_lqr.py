@@ -83,10 +83,13 @@ def _rows(b, T_rows, width):
 
 def solve_tvlqr(At, Bt, ct, Q, Qd, R, x0, x_trj_d, solver=None, indices_u_into_x=None,
                 x_bound_abs=None, u_bound_abs=None, x_bound_rel=None, u_bound_rel=None,
-                xinit=None, uinit=None, rho=10.0, max_iter=20000, eps=1e-8, *, adaptive_rho=False):
+                xinit=None, uinit=None, rho=10.0, max_iter=20000, eps=1e-8, *, adaptive_rho=False,
+                lazy_bounds=False):
     """Same signature and return value (xt_star (T+1,n), ut_star (T,m)) as tv_lqr.py:30; raises
     ValueError("TV_LQR failed...") like :139-140 when the solve does not converge.  `rho`, `max_iter`, `eps`
-    (extensions) tune the bounded solve; `adaptive_rho` lets its ADMM move the penalty from `rho` on, as OSQP does."""
+    (extensions) tune the bounded solve; `adaptive_rho` lets its ADMM move the penalty from `rho` on, as OSQP does;
+    `lazy_bounds` enforces the bounds lazily (only those a converged plan would break carry the penalty term: same
+    solution, far fewer iterations where "no bound" is written as a large finite number)."""
     At = np.asarray(At, float)
     T, n, m = At.shape[0], At.shape[1], np.asarray(Bt).shape[2]
     # before anything goes to the device: the kernel reads T + 1 state rows and T control rows
@@ -127,7 +130,7 @@ def solve_tvlqr(At, Bt, ct, Q, Qd, R, x0, x_trj_d, solver=None, indices_u_into_x
                                   % (T, dm.box_horizon_limit(du=position)))
     o = dm.tvlqr_box_solve(At_d, Bt_d, ct_d, Q_d, Qd_d, R_d, xd_d, x0_d, x_lo, x_hi, u_lo, u_hi, du_lo, du_hi,
                            position_controlled=position, alpha_R=1.0 if position else 0.5, rho=rho,
-                           max_iter=max_iter, eps=eps, adaptive_rho=adaptive_rho)
+                           max_iter=max_iter, eps=eps, adaptive_rho=adaptive_rho, lazy_bounds=lazy_bounds)
     i = o["info"].cpu().numpy()
     if i[0] != 0 or i[2] != 0:
         raise ValueError("TV_LQR failed. Optimization problem is not solved.")
