@@ -12,18 +12,20 @@
 //   * everything uniform lives in LDS (C, J D^-1, the table) or in ONE set of registers per lane (W, r0: 52);
 //   * the workgroup tabulates, once, for ALL 2^8 candidate active sets A the map  r -> [lam_A ; slacks off A]
 //     (G_A: rows of -W_AA^-1 on A -- masked LDL' in row order with the same pivot rule as
-//     irs_contact_qp_dual_exact, a dependent row drops out -- and of I + W M off A): 256 x 64 floats in LDS;
+//     irs_contact_qp_dual_exact, a dependent row drops out -- and of I + W M off A), not as G_A itself but as what
+//     the sample loop applies it to: G_A r = h_A + H_A du in the QP's four parameters (h_A = G_A r0, H_A = G_A C':
+//     8 + 32 floats) and, for the dual steps, U_A = G_A W (64 floats): 256 x 116 floats in LDS;
 //   * a sample is solved by a few projected sweeps (a guess of A), then primal-dual active-set iterations that
-//     cost ONE table row and ONE 8x8 product each: A <- (A minus rows with lam_i <= 0) + rows with slack < 0,
+//     cost ONE affine table row (12 reads, 40 FMA) each: A <- (A minus rows with lam_i <= 0) + rows with slack < 0,
 //     until the KKT conditions hold -- the exact optimum of the QP, certified per sample;
 //   * samples that do not settle within the iteration cap are parked in the wave's LDS ring (as in smooth.hip)
 //     and finished 64 at a time by the Goldfarb-Idnani dual active-set method (finite, no cycling), whose step
-//     also costs one table row + one product;
+//     reads its direction as one column of U_A (first-order pass: one row of W and a product with G_A);
 //   * zero-order statistics: sum z z', sum z lam', sum z -- the primal step is a UNIFORM linear map of lam, so
 //     it is applied once per workgroup to the sums (sum z df' = (sum z lam') (J D^-1) - ...), not per sample;
 //   * first-order statistics: the derivative of the step through its active set depends on the active set
 //     ALONE (geometry fixed), so the sample pass only counts active sets (integer LDS atomics: order-free,
-//     deterministic) and B(I) is evaluated once per occupied set from the same table.
+//     deterministic) and B(I) is evaluated once per occupied set from the same table (whose X block is then G_A).
 // Per-lane state: r, lam, a mask and the accumulators -- the kernel fits two (or more) waves per SIMD.
 // The f64 nominal step f(x_t, u_t) is evaluated by the last wave of workgroup 0 of every timestep, cooperatively
 // (lane c owns contact row c; an 8x8 masked LDL' spread over the 64 lanes), from the f32 pipeline's active set,
@@ -44,8 +46,17 @@ namespace {
 constexpr int kUgBlock = IRS_UG_BLOCK;
 constexpr int kUgSweeps = IRS_UG_SWEEPS;      // projected sweeps that guess the active set
 constexpr int kUgPdas = IRS_UG_PDAS;          // primal-dual active-set iterations of the first attempt
-constexpr int kUgTabStride = 76;              // floats per table entry: 64 (G', column-major) + 8 (tau: 1 off the reduced
-                                              // set, 0 on it) + the reduced set + pad; 304 B: 16-byte aligned rows
+#ifndef IRS_UG_STEP_COLUMNS
+#define IRS_UG_STEP_COLUMNS 1
+#endif
+constexpr bool kUgStepColumns = IRS_UG_STEP_COLUMNS != 0;   // zero-order pass: dual steps read a column of G W (0: G and a product)
+// One table entry, in floats (every piece 16-byte aligned, 464 B per entry):
+//   [ h = G r0 (8) | H = G C' (4 columns of 8, one per command) | tau (8: 1 off the reduced set, 0 on it) |
+//     the reduced set + pad (4) | X (8 x 8, column-major) ]
+// X = G W for the zero-order pass (a dual step reads its direction u = G W[:,p] as column p), X = G for the first-order
+// pass (its epilogue reads M on the set from it).
+constexpr int kUgTabH = 8, kUgTabTau = 40, kUgTabSet = 48, kUgTabX = 52;
+constexpr int kUgTabStride = 116;
 #ifndef IRS_UG_NOM_ROUNDS
 #define IRS_UG_NOM_ROUNDS 2
 #endif
@@ -85,33 +96,71 @@ struct UgUni {
     }
 };
 
-// v = G_a x + tol tau_a (table entry a, G stored column-major: row c of the entry = column c of G_a; tau_i = 1 for a
-// row off the reduced set -- whose v_i is a slack, optimal when >= -tol -- and 0 on it -- v_i a multiplier, optimal
-// when > 0: with the tolerance folded in, "row i is optimal" is v_i > 0 for both kinds).  All 18 reads are issued
-// before the first use: a wave has one partner on its SIMD to hide the LDS latency behind.
+// v = G_a r + tol tau_a for r = r0 + C du, read as h_a + H_a du (table entry a; tau_i = 1 for a row off the reduced
+// set -- whose v_i is a slack, optimal when >= -tol -- and 0 on it -- v_i a multiplier, optimal when > 0: with the
+// tolerance folded in, "row i is optimal" is v_i > 0 for both kinds).  The step QP has four parameters, so the row is
+// 8 + 4 x 8 numbers, not 8 x 8.  All 12 reads are issued before the first use: a wave has one partner on its SIMD to
+// hide the LDS latency behind.  Returns the reduced set.
 template <class Model>
-__device__ __forceinline__ unsigned ug_lookup(const UgLds<Model>& S, unsigned a, const float* x, float tol, float* v,
-                                              float* tau) {
-    constexpr int NC = Model::NC;
-    static_assert(NC == 8, "table entries are 8 x 8");
+__device__ __forceinline__ unsigned ug_lookup_affine(const UgLds<Model>& S, unsigned a, const float* du, float tol,
+                                                     float* v, float* tau) {
+    constexpr int NC = Model::NC, m = Model::NU;
+    static_assert(NC == 8 && m == 4, "table entries are 8 rows by 4 commands");
     const float4* e = reinterpret_cast<const float4*>(&S.tab[a][0]);
-    float4 g4[2 * NC + 2];
+    float4 g4[kUgTabSet / 4];
 #pragma unroll
-    for (int c = 0; c < 2 * NC + 2; ++c) g4[c] = e[c];
-    const unsigned ap = __float_as_uint(S.tab[a][72]);
-    tau[0] = g4[16].x; tau[1] = g4[16].y; tau[2] = g4[16].z; tau[3] = g4[16].w;
-    tau[4] = g4[17].x; tau[5] = g4[17].y; tau[6] = g4[17].z; tau[7] = g4[17].w;
+    for (int c = 0; c < kUgTabSet / 4; ++c) g4[c] = e[c];
+    const unsigned ap = __float_as_uint(S.tab[a][kUgTabSet]);
+    tau[0] = g4[kUgTabTau / 4].x; tau[1] = g4[kUgTabTau / 4].y; tau[2] = g4[kUgTabTau / 4].z; tau[3] = g4[kUgTabTau / 4].w;
+    tau[4] = g4[kUgTabTau / 4 + 1].x; tau[5] = g4[kUgTabTau / 4 + 1].y; tau[6] = g4[kUgTabTau / 4 + 1].z; tau[7] = g4[kUgTabTau / 4 + 1].w;
+    v[0] = fmaf(tau[0], tol, g4[0].x); v[1] = fmaf(tau[1], tol, g4[0].y);
+    v[2] = fmaf(tau[2], tol, g4[0].z); v[3] = fmaf(tau[3], tol, g4[0].w);
+    v[4] = fmaf(tau[4], tol, g4[1].x); v[5] = fmaf(tau[5], tol, g4[1].y);
+    v[6] = fmaf(tau[6], tol, g4[1].z); v[7] = fmaf(tau[7], tol, g4[1].w);
 #pragma unroll
-    for (int i = 0; i < NC; ++i) v[i] = tau[i] * tol;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const float4 lo = g4[2 * c], hi = g4[2 * c + 1];
-        v[0] = fmaf(lo.x, x[c], v[0]); v[1] = fmaf(lo.y, x[c], v[1]);
-        v[2] = fmaf(lo.z, x[c], v[2]); v[3] = fmaf(lo.w, x[c], v[3]);
-        v[4] = fmaf(hi.x, x[c], v[4]); v[5] = fmaf(hi.y, x[c], v[5]);
-        v[6] = fmaf(hi.z, x[c], v[6]); v[7] = fmaf(hi.w, x[c], v[7]);
+    for (int j = 0; j < m; ++j) {
+        const float4 lo = g4[kUgTabH / 4 + 2 * j], hi = g4[kUgTabH / 4 + 2 * j + 1];
+        v[0] = fmaf(lo.x, du[j], v[0]); v[1] = fmaf(lo.y, du[j], v[1]);
+        v[2] = fmaf(lo.z, du[j], v[2]); v[3] = fmaf(lo.w, du[j], v[3]);
+        v[4] = fmaf(hi.x, du[j], v[4]); v[5] = fmaf(hi.y, du[j], v[5]);
+        v[6] = fmaf(hi.z, du[j], v[6]); v[7] = fmaf(hi.w, du[j], v[7]);
     }
     return ap;
+}
+
+// The direction of a dual step towards row p (off the set a): u = G_a W[:,p], with tau_a.  UCOL (the zero-order pass):
+// column p of the entry's X = G_a W, 4 reads and no arithmetic; else (X = G_a): the row W[p][:] and the 8 x 8 product.
+template <class Model, bool UCOL>
+__device__ __forceinline__ void ug_step_direction(const UgLds<Model>& S, unsigned a, int p, float* u, float* tau) {
+    constexpr int NC = Model::NC;
+    const float* e = &S.tab[a][0];
+    const float4 t0 = *reinterpret_cast<const float4*>(e + kUgTabTau), t1 = *reinterpret_cast<const float4*>(e + kUgTabTau + 4);
+    if constexpr (UCOL) {
+        const float4 lo = *reinterpret_cast<const float4*>(e + kUgTabX + NC * p);
+        const float4 hi = *reinterpret_cast<const float4*>(e + kUgTabX + NC * p + 4);
+        u[0] = lo.x; u[1] = lo.y; u[2] = lo.z; u[3] = lo.w;
+        u[4] = hi.x; u[5] = hi.y; u[6] = hi.z; u[7] = hi.w;
+    } else {
+        const float4 wlo = *reinterpret_cast<const float4*>(&S.W[p][0]);
+        const float4 whi = *reinterpret_cast<const float4*>(&S.W[p][4]);
+        const float4* x4 = reinterpret_cast<const float4*>(e + kUgTabX);
+        float4 g4[2 * NC];
+#pragma unroll
+        for (int c = 0; c < 2 * NC; ++c) g4[c] = x4[c];
+        const float wp[NC] = {wlo.x, wlo.y, wlo.z, wlo.w, whi.x, whi.y, whi.z, whi.w};
+#pragma unroll
+        for (int i = 0; i < NC; ++i) u[i] = 0.f;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            const float4 lo = g4[2 * c], hi = g4[2 * c + 1];
+            u[0] = fmaf(lo.x, wp[c], u[0]); u[1] = fmaf(lo.y, wp[c], u[1]);
+            u[2] = fmaf(lo.z, wp[c], u[2]); u[3] = fmaf(lo.w, wp[c], u[3]);
+            u[4] = fmaf(hi.x, wp[c], u[4]); u[5] = fmaf(hi.y, wp[c], u[5]);
+            u[6] = fmaf(hi.z, wp[c], u[6]); u[7] = fmaf(hi.w, wp[c], u[7]);
+        }
+    }
+    tau[0] = t0.x; tau[1] = t0.y; tau[2] = t0.z; tau[3] = t0.w;
+    tau[4] = t1.x; tau[5] = t1.y; tau[6] = t1.z; tau[7] = t1.w;
 }
 
 // r = r0 + C du and the tolerance of the optimality tests (that of irs_contact_qp_dual_exact)
@@ -138,8 +187,8 @@ __device__ __forceinline__ float ug_rhs(const UgUni<Model::NC>& U, const UgLds<M
 // FIRST ATTEMPT: sweeps guess the active set, primal-dual active-set iterations settle it.  true: lam is the exact
 // optimum (KKT certified); false: `a` is the set the iteration stopped on (a warm start for ug_full).
 template <class Model>
-__device__ __forceinline__ bool ug_try(const UgUni<Model::NC>& U, const UgLds<Model>& S, const float* r, float tolv,
-                                       float* lam, unsigned& a_out, int diag = 0) {
+__device__ __forceinline__ bool ug_try(const UgUni<Model::NC>& U, const UgLds<Model>& S, const float* r, const float* du,
+                                       float tolv, float* lam, unsigned& a_out, int diag = 0) {
     constexpr int NC = Model::NC;
     float g[NC];
 #pragma unroll
@@ -161,7 +210,7 @@ __device__ __forceinline__ bool ug_try(const UgUni<Model::NC>& U, const UgLds<Mo
     bool done = (diag & 32) != 0;
     for (int it = 0; it < kUgPdas; ++it) {
         float v[NC], tau[NC];
-        const unsigned ap = ug_lookup<Model>(S, a, r, tolv, v, tau);
+        const unsigned ap = ug_lookup_affine<Model>(S, a, du, tolv, v, tau);
         // rows that are not optimal flip: a multiplier <= 0 leaves the set, a slack < -tol joins it
         // (the sign bits, shifted in one v_alignbit each: row 0 ends in bit 0.  A multiplier of exactly +0 stays: it
         // satisfies the KKT conditions as it is)
@@ -185,11 +234,12 @@ __device__ __forceinline__ bool ug_try(const UgUni<Model::NC>& U, const UgLds<Mo
 // FULL METHOD from a warm set: the Goldfarb-Idnani dual active-set method in the dual variables, restated from
 // irs_contact_qp_dual_exact (contact_models.hpp) with every factorisation replaced by a table row:
 //   repair rounds: lam_A = -W_AA^-1 r_A; rows with lam_i <= 0 leave (<= 3 rounds; else start from lam = 0);
-//   loop: p = most violated row off A; u = G_A W[:,p] gives rho = -u on A and the slack rates s = u off A in one
-//   product; step to the first of { slack_p = 0 (p joins), some lam_i = 0 (i leaves) }.  Finite, no cycling.
-template <class Model>
-__device__ __forceinline__ void ug_full(const UgLds<Model>& S, const float* r, float tolv, unsigned a, float* lam,
-                                        int cap = 4 * Model::NC) {
+//   loop: p = most violated row off A; u = G_A W[:,p] (ug_step_direction) gives rho = -u on A and the slack rates
+//   s = u off A; step to the first of { slack_p = 0 (p joins), some lam_i = 0 (i leaves) }.  Finite, no cycling.
+// r (= r0 + C du) serves the cold start only; the repair rounds read the affine rows at du.
+template <class Model, bool UCOL>
+__device__ __forceinline__ void ug_full(const UgLds<Model>& S, const float* r, const float* du, float tolv, unsigned a,
+                                        float* lam, int cap = 4 * Model::NC) {
     constexpr int NC = Model::NC;
     constexpr float kBig = 3.0e38f, piv_rel = 1e-5f;
     float g[NC];
@@ -197,7 +247,7 @@ __device__ __forceinline__ void ug_full(const UgLds<Model>& S, const float* r, f
     for (int round = 0; round < 3; ++round) {
         if (__all(valid)) break;
         float v[NC], tau[NC];
-        const unsigned ap = ug_lookup<Model>(S, a, r, 0.f, v, tau);
+        const unsigned ap = ug_lookup_affine<Model>(S, a, du, 0.f, v, tau);
         if (!valid) {
             unsigned negb = 0u;
 #pragma unroll
@@ -232,14 +282,8 @@ __device__ __forceinline__ void ug_full(const UgLds<Model>& S, const float* r, f
         }
         if (__all(done)) break;
         const int pp = (done || p < 0) ? 0 : p;
-        float wp[NC], u[NC], tau[NC];
-        {
-            const float4 lo = *reinterpret_cast<const float4*>(&S.W[pp][0]);
-            const float4 hi = *reinterpret_cast<const float4*>(&S.W[pp][4]);
-            wp[0] = lo.x; wp[1] = lo.y; wp[2] = lo.z; wp[3] = lo.w;
-            wp[4] = hi.x; wp[5] = hi.y; wp[6] = hi.z; wp[7] = hi.w;
-        }
-        ug_lookup<Model>(S, a, wp, 0.f, u, tau);
+        float u[NC], tau[NC];
+        ug_step_direction<Model, UCOL>(S, a, pp, u, tau);
         // in arithmetic rather than selects (tau_i = 1 off the reduced set, 0 on it): rho = -(1 - tau) u on the set,
         // the slack rates s = tau u off it -- a third of the instructions of the select form (400 -> ~270 per step)
         const float wpp = S.Wd[pp];
@@ -285,9 +329,12 @@ __device__ __forceinline__ void ug_full(const UgLds<Model>& S, const float* r, f
     }
 }
 
-// One table entry: G_a for the candidate set `a`, by the masked LDL' in row order of irs_contact_qp_dual_exact_try
-// (pivot rule included: a dependent row leaves the set).  `half` (0/1): the four columns this lane writes.
-template <class Model>
+// One table entry for the candidate set `a`, by the masked LDL' in row order of irs_contact_qp_dual_exact_try (pivot
+// rule included: a dependent row leaves the set).  G_a is never formed: it is APPLIED (a solve on the set with the
+// right-hand side -x_A; x_i + sum_j W_ij y_j on the rows off it) to the 13 vectors the sample loop needs it on --
+// r0 (h), the four C[j][:] (H) and the eight W[:,p] (X = G W; UCOL) or unit vectors (X = G).  `half` (0/1): this lane's
+// share, 7 and 6 of them.
+template <class Model, bool UCOL>
 __device__ __forceinline__ void ug_build_entry(UgLds<Model>& S, unsigned a, int half) {
     constexpr int NC = Model::NC;
     constexpr float piv_rel = 1e-5f;
@@ -317,13 +364,26 @@ __device__ __forceinline__ void ug_build_entry(UgLds<Model>& S, unsigned a, int 
             for (int k = j + 1; k <= i; ++k) M_[i][k] = M_[i][k] - M_[j][i] * M_[k][j];
     }
     float* e = &S.tab[a][0];
-    for (int cc = 0; cc < NC / 2; ++cc) {
-        const int c = half * (NC / 2) + cc;
-        // y = -W_AA^-1 e_c on the set (zero off it)
+    constexpr int NAPP = 1 + Model::NU + NC, SHARE = (NAPP + 1) / 2;
+    for (int qq = 0; qq < SHARE; ++qq) {
+        const int q = half * SHARE + qq;
+        if (q >= NAPP) break;
+        const int c = q - (1 + Model::NU);                 // the column of X, if any
+        float x[NC];
+        if (UCOL || c < 0) {
+            const float* src = q == 0 ? &S.r0[0] : (c < 0 ? &S.C[q - 1][0] : &S.W[c][0]);     // W is symmetric to the bit
+            const float4 lo = *reinterpret_cast<const float4*>(src), hi = *reinterpret_cast<const float4*>(src + 4);
+            x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w;
+            x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;
+        } else {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) x[i] = (i == c) ? 1.f : 0.f;
+        }
+        // y = -W_AA^-1 x_A on the set (zero off it)
         float y[NC];
 #pragma unroll
         for (int j = 0; j < NC; ++j) {
-            float v = (act[j] && j == c) ? -1.f : 0.f;
+            float v = act[j] ? -x[j] : 0.f;
 #pragma unroll
             for (int k = 0; k < j; ++k) v = v - M_[k][j] * y[k];
             y[j] = v;
@@ -338,18 +398,19 @@ __device__ __forceinline__ void ug_build_entry(UgLds<Model>& S, unsigned a, int 
         float col[NC];
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
-            float s = (i == c) ? 1.f : 0.f;
+            float s = x[i];
 #pragma unroll
             for (int j = 0; j < NC; ++j) s = fmaf(W[i][j], y[j], s);
             col[i] = act[i] ? y[i] : s;
         }
-        *reinterpret_cast<float4*>(e + 8 * c) = make_float4(col[0], col[1], col[2], col[3]);
-        *reinterpret_cast<float4*>(e + 8 * c + 4) = make_float4(col[4], col[5], col[6], col[7]);
+        float* dst = e + (c < 0 ? NC * q : kUgTabX + NC * c);
+        *reinterpret_cast<float4*>(dst) = make_float4(col[0], col[1], col[2], col[3]);
+        *reinterpret_cast<float4*>(dst + 4) = make_float4(col[4], col[5], col[6], col[7]);
     }
-    if (half == 0) {
-        *reinterpret_cast<float4*>(e + 64) = make_float4(act[0] ? 0.f : 1.f, act[1] ? 0.f : 1.f, act[2] ? 0.f : 1.f, act[3] ? 0.f : 1.f);
-        *reinterpret_cast<float4*>(e + 68) = make_float4(act[4] ? 0.f : 1.f, act[5] ? 0.f : 1.f, act[6] ? 0.f : 1.f, act[7] ? 0.f : 1.f);
-        e[72] = __uint_as_float(ap);
+    if (half == 1) {
+        *reinterpret_cast<float4*>(e + kUgTabTau) = make_float4(act[0] ? 0.f : 1.f, act[1] ? 0.f : 1.f, act[2] ? 0.f : 1.f, act[3] ? 0.f : 1.f);
+        *reinterpret_cast<float4*>(e + kUgTabTau + 4) = make_float4(act[4] ? 0.f : 1.f, act[5] ? 0.f : 1.f, act[6] ? 0.f : 1.f, act[7] ? 0.f : 1.f);
+        e[kUgTabSet] = __uint_as_float(ap);
     }
 }
 
@@ -398,7 +459,7 @@ __device__ __forceinline__ double ug_nominal_geometry(const Args& a, UgNomLds& L
 }
 
 // (b) after the table exists: the f32 pipeline's active set at du = 0, then the cooperative f64 solve and its check
-template <class Model, class Args>
+template <class Model, bool UCOL, class Args>
 __device__ __forceinline__ void ug_nominal(const Args& a, const UgUni<Model::NC>& U, const UgLds<Model>& S,
                                            UgNomLds& L, double rr, int t, int lane) {
     constexpr int NC = Model::NC, n = Model::NX, m = Model::NU;
@@ -409,7 +470,7 @@ __device__ __forceinline__ void ug_nominal(const Args& a, const UgUni<Model::NC>
     for (int j = 0; j < m; ++j) du0[j] = 0.f;
     const float tolv = ug_rhs<Model>(U, S, du0, r32);
     unsigned am = 0u;
-    if (!ug_try<Model>(U, S, r32, tolv, lam32, am)) ug_full<Model>(S, r32, tolv, am, lam32);
+    if (!ug_try<Model>(U, S, r32, du0, tolv, lam32, am)) ug_full<Model, UCOL>(S, r32, du0, tolv, am, lam32);
     unsigned set = 0u;
 #pragma unroll
     for (int i = 0; i < NC; ++i) set |= (lam32[i] > 0.f) ? (1u << i) : 0u;
@@ -521,6 +582,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
     constexpr int PI = TR::FIRST_B ? 1 : NG + m * NC + m;
     constexpr int PPI = irs_reduce_pad(TR::FIRST_B ? n * m : PI);
     constexpr int QE = m + 1;
+    constexpr bool UCOL = !TR::FIRST_B && kUgStepColumns;      // the table's X: G W (dual steps read a column) / G (the first-order epilogue reads M)
     __shared__ UgLds<Model> S;
     __shared__ UgNomLds nomL;
     __shared__ float ring_all[NW * kUgRing * QE];
@@ -595,7 +657,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
     __syncthreads();
     UG_STAMP(1);
     if (!(a.diag & 4))
-        for (int e = tid; e < 2 * (1 << NC); e += BLOCK) ug_build_entry<Model>(S, (unsigned)(e >> 1), e & 1);
+        for (int e = tid; e < 2 * (1 << NC); e += BLOCK) ug_build_entry<Model, UCOL>(S, (unsigned)(e >> 1), e & 1);
     __syncthreads();
 
     UG_STAMP(2);
@@ -618,7 +680,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
 #pragma unroll
     for (int i = 0; i < PPI; ++i) acc[i] = 0.f;
 
-    if (nominal_wave && !(a.diag & 2)) ug_nominal<Model>(a, U, S, nomL, nom_r, t, lane);
+    if (nominal_wave && !(a.diag & 2)) ug_nominal<Model, UCOL>(a, U, S, nomL, nom_r, t, lane);
     if (nominal_wave) UG_STAMP(8);
     if (!(a.diag & 8)) {
         // 64-sample blocks are dealt round robin to the waves of the timestep: rounds 0 .. kUgNomRounds - 1 to all but
@@ -665,7 +727,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
                 for (int j = 0; j < m; ++j) du[j] = ring[slot * QE + j];
                 const unsigned wm = __float_as_uint(ring[slot * QE + m]);
                 const float tolv = ug_rhs<Model>(U, S, du, r);
-                ug_full<Model>(S, r, tolv, wm, lam, (a.diag & 128) ? 8 : ((a.diag & 256) ? 12 : 4 * NC));
+                ug_full<Model, UCOL>(S, r, du, tolv, wm, lam, (a.diag & 128) ? 8 : ((a.diag & 256) ? 12 : 4 * NC));
                 qhead += take;
             } else {
                 const int sidx = bk * 64 + lane;
@@ -689,7 +751,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
                 }
                 const float tolv = ug_rhs<Model>(U, S, du, r);
                 unsigned mask = 0u;
-                fin_ = ug_try<Model>(U, S, r, tolv, lam, mask, a.diag);
+                fin_ = ug_try<Model>(U, S, r, du, tolv, lam, mask, a.diag);
                 if (a.diag & 16) fin_ = true;
                 const bool hard = on && !fin_;
                 const unsigned long long bal = __ballot(hard);
@@ -749,7 +811,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
             const unsigned cnt = hist[I];
             if (cnt == 0u) continue;
             const float* e = &S.tab[I][0];
-            const unsigned ap = __float_as_uint(e[72]);
+            const unsigned ap = __float_as_uint(e[kUgTabSet]);
             float Y[NC][m];
 #pragma unroll
             for (int i = 0; i < NC; ++i) {
@@ -758,7 +820,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
                 for (int c = 0; c < m; ++c) {
                     float s = 0.f;
 #pragma unroll
-                    for (int j = 0; j < NC; ++j) s = fmaf(e[8 * j + i], S.Jc[j][Model::act(c)], s);    // G[i][j] = M[i][j] on the set
+                    for (int j = 0; j < NC; ++j) s = fmaf(e[kUgTabX + 8 * j + i], S.Jc[j][Model::act(c)], s);    // G[i][j] = M[i][j] on the set
                     Y[i][c] = in ? -s : 0.f;
                 }
             }
@@ -850,7 +912,7 @@ bool irs_smooth_ug_supported(int model, int mode) {
     return model == IRS_MODEL_PLANAR_HAND_EXACT && (mode == IRS_SMOOTH_ZERO_ORDER_B || mode == IRS_SMOOTH_FIRST_ORDER);
 }
 
-// workgroups per timestep: one 512-thread workgroup per CU holds the 70 KB table, so the grid is about the CU count
+// workgroups per timestep: one 512-thread workgroup per CU holds the 116 KB table, so the grid is about the CU count
 // and every wave loops over its share of the 64-sample blocks; never more workgroups than blocks / 8
 int irs_smooth_ug_nblk(int T, int N) {
     static int cus = 0;
