@@ -586,6 +586,51 @@ int irs_quasistatic_box_descent_lazy(int model, const double *params, int n_para
  * rank-deficient design), or n+m+1 for non-finite data.  n <= 32, m <= 16.                                   */
 int irs_least_squares(int n, int m, int N, const double *dxdu, const double *deltaf, double *A, double *B,
                       int *info, void *stream);
+
+/* ---- The values pass: the zero-order sample pass of a system WITHOUT a device functor ------------------------
+ * The caller evaluated its own dynamics; these entries evaluate no model.  All T timesteps at once:
+ *   dx (T,N,n), du (T,N,m), fz (T,N,n) DEV f32, 16-byte aligned: the samples and fz = f(x_t + dx, u_t + du);
+ *   f0 (T,n) DEV f32: f(x_t, u_t) from the same code in the same precision (dF = fz - f0 is formed in f32);
+ *   fnom (T,n) DEV f64: the nominal step c_t is measured from; x_trj (>= T rows of n), u_trj (T,m) DEV f64.
+ * 1 <= n <= 32, 1 <= m <= 16 (the generic Riccati kernel's limits), 1 <= T <= 1024, N >= 1.
+ * sums (T,P) DEV f64, P = irs_values_sums_len(n, m) = d(d+1)/2 + d n, d = n + m: the IRS_SMOOTH_ZERO_ORDER_AB
+ * layout of irs_sums_len -- upper triangle of Z'Z row-major, then Z'dF (d,n).  Sums of sample shards add
+ * (all-reduce them, then finalize with N_total).  The Gram products run on the matrix cores in f32, moved to f64
+ * every 1024 samples per wave; every summation order is a function of (T, N) alone, so a call is bit-reproducible.
+ * The solve is irs_least_squares' (Jacobi-scaled Cholesky of the normal equations, f64): At (T,n,n), Bt (T,n,m),
+ * ct (T,n) = fnom_t - A_t x_t - B_t u_t, info (T): 0, the failed pivot (1-based), or n+m+1 where a statistic of
+ * that timestep is not finite; a bad timestep leaves the others alone.  N_total < n+m samples cannot span the
+ * design (rank Z'Z <= N_total): pivot N_total + 1 is reported failed whatever rounding left on it.
+ * workspace: DEV, 256-byte aligned, >= irs_smooth_values_workspace_bytes(n, m, T, N), uninitialised scratch (the
+ * workgroups' partial sums; no counters, nothing to zero).  One call in flight per workspace at a time.  No
+ * allocation, no host synchronisation: accumulate and irs_smooth_values enqueue two launches, finalize one.
+ * Every argument error is decided before the first HIP call:
+ *   IRS_ERR_INVALID_ARG  a size out of range, a null pointer, dx / du / fz not 16-byte aligned
+ *   IRS_ERR_WORKSPACE    workspace null, too small or not 256-byte aligned                                      */
+int irs_values_sums_len(int n, int m);
+/* No GPU is touched; 0 for invalid sizes.  Non-decreasing in n, m, T and N (an upper bound of the partials, not their
+ * exact size): a workspace sized for a caller's largest (n, m, T, N) -- the largest shard, say -- serves every
+ * smaller call.                                                                                                 */
+size_t irs_smooth_values_workspace_bytes(int n, int m, int T, int N);
+/* the launch geometry for (T, N) -- it does not depend on (n, m): out = {threads per workgroup, workgroups per
+ * timestep (nblk), samples per workgroup (a multiple of 256; the last one of a timestep may be ragged), trips
+ * between f64 flushes}                                                                                          */
+int irs_smooth_values_geometry(int T, int N, long long out[4]);
+/* irs_rng_samples for ANY 1 <= n <= 32, 1 <= m <= 16 (that entry serves the compiled models' sizes): the same
+ * Philox stream -- counter (sample_offset + i, t, block, iter), key seed; oracle/irs_oracle.py:device_gaussian_samples --
+ * written as dx (T,N,n), du (T,N,m) DEV f32.  std_x (n), std_u (m) HOST.                                        */
+int irs_values_rng_samples(int n, int m, int T, int N, const double *std_x, const double *std_u, uint64_t seed,
+                           uint32_t iter, uint64_t sample_offset, float *dx, float *du, void *stream);
+int irs_smooth_values_accumulate(int n, int m, int T, int N, const float *dx, const float *du, const float *fz,
+                                 const float *f0, double *sums, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+int irs_smooth_values_finalize(int n, int m, int T, long long N_total, const double *x_trj, const double *u_trj,
+                               const double *fnom, const double *sums, double *At, double *Bt, double *ct,
+                               int *info, void *stream);
+int irs_smooth_values(int n, int m, int T, int N, const double *x_trj, const double *u_trj, const float *dx,
+                      const float *du, const float *fz, const float *f0, const double *fnom, double *sums,
+                      double *At, double *Bt, double *ct, int *info, void *workspace, size_t workspace_bytes,
+                      void *stream);
 /* The same with a device workspace for horizons whose per-step records do not fit the 160 KB of LDS
  * (solver 3 / 0, and solver 1: the ADMM's factor records, up to irs_tvlqr_box_hbm_lds_bytes(model, T, 1)
  * <= ~160 KB): `workspace` DEV, 256-byte aligned, at least irs_quasistatic_descent_workspace_bytes(model, T,

@@ -15,4 +15,5 @@ from .systems import (BicycleDynamics, BoxOnBoxDynamics,             # noqa: F40
                       PendulumDynamics, PlanarHandDynamics,
                       QuadrotorDynamics, QuasistaticDeviceDynamics,
                       ThreeCartDynamics)
+from .torch_system import TorchDynamicalSystem                      # noqa: F401
 from .tv_lqr import get_solver, solve_tvlqr                         # noqa: F401

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IRS_HIP_LIB") or os.path.join(_HERE, "csrc", "libirs_hip.so")
 
 IRS_OK = 0
+IRS_ERR_UNSUPPORTED = -3
 MODEL_PENDULUM = 0
 MODEL_QUADROTOR = 1
 MODEL_BICYCLE = 2
@@ -226,6 +227,18 @@ for _name in ("irs_tvlqr_box_descent", "irs_tvlqr_box_solve", "irs_quasistatic_b
     _res, _args = SIGNATURES[_name + "_set"]
     SIGNATURES[_name + "_lazy"] = (_res, _args[:-1] + [_dp, _dp] + _args[-1:])
 SIGNATURES["irs_least_squares"] = (c_int, [c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, c_void_p])
+# the values pass (csrc/smooth_values.hip): sizes (n, m, T, N) instead of a model
+SIGNATURES["irs_values_sums_len"] = (c_int, [c_int, c_int])
+SIGNATURES["irs_smooth_values_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int, c_int])
+SIGNATURES["irs_smooth_values_geometry"] = (c_int, [c_int, c_int, POINTER(c_longlong)])
+SIGNATURES["irs_values_rng_samples"] = (c_int, [c_int, c_int, c_int, c_int, POINTER(c_double), POINTER(c_double), c_uint64,
+                                                c_uint32, c_uint64, _dp, _dp, c_void_p])
+SIGNATURES["irs_smooth_values_accumulate"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_size_t,
+                                                      c_void_p])
+SIGNATURES["irs_smooth_values_finalize"] = (c_int, [c_int, c_int, c_int, c_longlong, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                    _dp, c_void_p])
+SIGNATURES["irs_smooth_values"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                           _dp, _dp, _dp, c_size_t, c_void_p])
 SIGNATURES["irs_smooth_run"] = (c_int, [POINTER(SmoothCall), c_void_p])
 SIGNATURES["irs_descent_run"] = (c_int, [POINTER(DescentCall), c_void_p])
 SIGNATURES["irs_comm_available"] = (c_int, [])

@@ -825,3 +825,86 @@ def tvlqr_linear_rollout(At, Bt, ct, K, k, x0):
                                        _ptr(k, F64), _ptr(x0, F64), _ptr(xs, F64), _ptr(us, F64), _stream()),
           "irs_tvlqr_linear_rollout")
     return xs, us
+
+
+# ---- the values pass: the zero-order sample pass on function values the caller evaluated (csrc/smooth_values.hip) ----
+def values_sums_len(n, m):
+    return _lib.load().irs_values_sums_len(int(n), int(m))
+
+
+def smooth_values_geometry(T, N):
+    """The launch geometry of the values pass for (T, N) (irs_smooth_values_geometry): no launch, no device.
+    dict(block, nblk, chunk, flush_trips)."""
+    out = (ctypes.c_longlong * 4)()
+    check(_lib.load().irs_smooth_values_geometry(int(T), int(N), out), "irs_smooth_values_geometry")
+    return dict(block=out[0], nblk=out[1], chunk=out[2], flush_trips=out[3])
+
+
+_values_ws = {}
+
+
+def _values_workspace(n, m, T, N, device):
+    """The cached scratch of the values pass for (`device`, the current stream), grown on demand (uninitialised: the
+    pass zeroes nothing).  One per stream: a workspace takes one call in flight at a time, and calls on one stream run
+    in order.  (An outgrown buffer goes back to torch's caching allocator, which orders its reuse behind the work
+    queued on the stream it was allocated on: this one.)"""
+    need = _lib.load().irs_smooth_values_workspace_bytes(n, m, T, N)
+    key = (device, _stream())
+    ws = _values_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _values_ws[key] = torch.empty((max(need, 256),), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _values_shapes(dx, du, fz, f0):
+    T, N, n = dx.shape
+    m = du.shape[2]
+    assert tuple(du.shape) == (T, N, m) and tuple(fz.shape) == (T, N, n) and tuple(f0.shape) == (T, n), \
+        (tuple(dx.shape), tuple(du.shape), tuple(fz.shape), tuple(f0.shape))
+    return T, N, n, m
+
+
+def smooth_values_accumulate(dx, du, fz, f0, sums=None, workspace=None):
+    """Statistics of the values pass: dx (T,N,n), du (T,N,m), fz (T,N,n), f0 (T,n) f32 -> sums (T,P) f64."""
+    T, N, n, m = _values_shapes(dx, du, fz, f0)
+    if sums is None:
+        sums = torch.empty((T, values_sums_len(n, m)), dtype=F64, device=dx.device)
+    ws = workspace if workspace is not None else _values_workspace(n, m, T, N, dx.device)
+    check(_lib.load().irs_smooth_values_accumulate(n, m, T, N, _ptr(dx, F32), _ptr(du, F32), _ptr(fz, F32), _ptr(f0, F32),
+                                                   _ptr(sums, F64), ws.data_ptr(), ws.numel(), _stream()),
+          "irs_smooth_values_accumulate")
+    return sums
+
+
+def _values_outputs(T, n, m, device):
+    return dict(sums=None,
+                At=torch.empty((T, n, n), dtype=F64, device=device),
+                Bt=torch.empty((T, n, m), dtype=F64, device=device),
+                ct=torch.empty((T, n), dtype=F64, device=device),
+                info=torch.empty((T,), dtype=torch.int32, device=device))
+
+
+def smooth_values_finalize(N_total, x_trj, u_trj, fnom, sums, m=None, out=None):
+    """Solve from (all-reduced) sums of the values pass -> (At, Bt, ct, info); fnom (T,n) f64 = f(x_t, u_t)."""
+    T, n = fnom.shape
+    m = u_trj.shape[1] if m is None else m
+    o = out if out is not None else _values_outputs(T, n, m, fnom.device)
+    check(_lib.load().irs_smooth_values_finalize(n, m, T, int(N_total), _ptr(x_trj, F64), _ptr(u_trj, F64),
+                                                 _ptr(fnom, F64), _ptr(sums, F64), _ptr(o["At"], F64), _ptr(o["Bt"], F64),
+                                                 _ptr(o["ct"], F64), o["info"].data_ptr(), _stream()),
+          "irs_smooth_values_finalize")
+    return o["At"], o["Bt"], o["ct"], o["info"]
+
+
+def smooth_values(x_trj, u_trj, dx, du, fz, f0, fnom, out=None, workspace=None):
+    """The values pass and its solve behind one call -> dict(sums, At, Bt, ct, info); `out` = a previous result."""
+    T, N, n, m = _values_shapes(dx, du, fz, f0)
+    o = out if out is not None else _values_outputs(T, n, m, dx.device)
+    if o["sums"] is None:
+        o["sums"] = torch.empty((T, values_sums_len(n, m)), dtype=F64, device=dx.device)
+    ws = workspace if workspace is not None else _values_workspace(n, m, T, N, dx.device)
+    check(_lib.load().irs_smooth_values(n, m, T, N, _ptr(x_trj, F64), _ptr(u_trj, F64), _ptr(dx, F32), _ptr(du, F32),
+                                        _ptr(fz, F32), _ptr(f0, F32), _ptr(fnom, F64), _ptr(o["sums"], F64),
+                                        _ptr(o["At"], F64), _ptr(o["Bt"], F64), _ptr(o["ct"], F64), o["info"].data_ptr(),
+                                        ws.data_ptr(), ws.numel(), _stream()), "irs_smooth_values")
+    return o

@@ -28,7 +28,9 @@ class DynamicalSystem:
         if self.device_model is None:
             raise NotImplementedError(
                 "%s has no device model: the HIP path needs a functor registered in "
-                "irs_mpc_amd/csrc/models.hpp (there is no CPU fallback)." % type(self).__name__)
+                "irs_mpc_amd/csrc/models.hpp, or dynamics written as a torch callable -- subclass "
+                "irs_mpc_amd.TorchDynamicalSystem and implement dynamics_batch_torch (there is no CPU "
+                "fallback)." % type(self).__name__)
         if getattr(self, "_dm", None) is None:
             self._dm = dev.DeviceModel(self.device_model, self.device_params())
         return self._dm

@@ -152,6 +152,10 @@ class IrsLqr:
         box = self._box_bounds()
         if box is None or self._tail_plans_within_bounds(At, Bt, ct, o["K"], o["k"], o["x_new"]):
             return o["x_new"], o["u_new"], o["cost"]
+        if not self._compiled():
+            raise NotImplementedError(
+                "a box bound is active: bounded descents need a compiled device model (a functor in "
+                "irs_mpc_amd/csrc/models.hpp); a TorchDynamicalSystem runs while no bound binds")
         if not self._dm.box_descent_supported(self.T):
             raise NotImplementedError(
                 "a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
@@ -169,6 +173,11 @@ class IrsLqr:
                           box_adapt=ob.get("adapt"), box_enforced=ob.get("enforced"), box_lazy=ob.get("lazy"))
         self._box_used = True
         return ob["x_new"], ob["u_new"], cost
+
+    def _compiled(self):
+        """Whether the system runs on a device functor (DeviceModel); False for a TorchDynamicalSystem, whose model
+        only torch can evaluate: no fused irs_iterate loop, no bounded descent."""
+        return getattr(self._dm, "compiled", True)
 
     def _adaptive_rho(self):
         return bool(getattr(self.params, "qp_adaptive_rho", False))
@@ -381,7 +390,7 @@ class _IrsLqrSampled(IrsLqr):
 
     def _fused_spec(self):
         on_device = isinstance(self.sampling, GaussianSmoothing) and getattr(self.sampling, "on_device", True)
-        if not on_device or dist_util.rank_world()[1] != 1:
+        if not on_device or dist_util.rank_world()[1] != 1 or not self._compiled():
             return None
         return self.MODE, self.sampling.num_samples, self.sampling
 
@@ -451,6 +460,8 @@ class IrsLqrExact(IrsLqr):
 
     def _fused_spec(self):
         from ._lib import ITERATE_EXACT
+        if not self._compiled():
+            return None
         return ITERATE_EXACT, 0, None
 
     def _get_TV_matrices_dev(self, x_trj, u_trj):
