@@ -4,6 +4,7 @@ no compiled functor -- the values pass and the generic Riccati kernel run) throu
 
     python examples/run_torch.py                       # zero_order, first_order and exact, one after the other
     python examples/run_torch.py zero_order --iters 20 --N 2000
+    python examples/run_torch.py exact --ubound 4      # |force| <= 4: bounded descents through the any-size box-QP kernel
 
 The task is a crane's: the load starts swinging 0.5 rad off the vertical; move the cart one metre and bring the load to
 rest under it (T = 100 steps of 0.02 s).  Samples are drawn on the GPU (GaussianSmoothing, Philox).
@@ -40,9 +41,15 @@ def main():
     ap.add_argument("--h", type=float, default=0.02)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--quiet", action="store_true")
+    ap.add_argument("--ubound", type=float, default=None, metavar="V",
+                    help="bound the force on the cart, |u| <= V: where it binds, the stepped bounded descent runs "
+                         "(IrsLqrParameters.qp_model_free)")
     a = ap.parse_args()
     for method in (["zero_order", "first_order", "exact"] if a.method == "all" else [a.method]):
         system, params = TorchCartPole(a.h), cartpole_problem(a.T)
+        if a.ubound is not None:
+            params.ubound = np.array([[-a.ubound], [a.ubound]])
+            params.qp_model_free = True
         if method == "exact":
             solver = amd.IrsLqrExact(system, params)
         else:

@@ -631,6 +631,57 @@ int irs_smooth_values(int n, int m, int T, int N, const double *x_trj, const dou
                       const float *du, const float *fz, const float *f0, const double *fnom, double *sums,
                       double *At, double *Bt, double *ct, int *info, void *workspace, size_t workspace_bytes,
                       void *stream);
+
+/* ---- Bounded TV-LQR of ANY size, resumable from tail to tail (csrc/boxqp_values.hip) --------------------------
+ * irs_tvlqr_box_descent is compiled per model and keeps the plant step inside its launch.  These entries evaluate no
+ * model: the same ADMM (one Riccati factorisation, w <- clip(a z + (1-a) w + y), a rho term only on components with
+ * a finite bound at any time, stop at max(primal, dual residual) < eps; fixed penalty only) for runtime
+ * 1 <= n <= 32, 1 <= m <= 16, split at the plant.  `begin` factorises the whole horizon once per descent; `tail`
+ * solves the tail QP t..T from a given state, warm started from the previous tail; the caller's plant runs between
+ * the launches on the same stream.  Each entry is ONE launch of one wave; nothing waits on the host.
+ *   At (T,n,n), Bt (T,n,m), ct (T,n), Q, Qd (n,n), R (m,m), xd_trj (T+1,n) DEV f64; alpha_R as irs_tvlqr_riccati.
+ *   x_lo, x_hi: DEV, x_rows = 1 (one row of n, every step) or T + 1 (row t bounds x_t; row 0 is not enforced: x_t of
+ *   a tail is data); u_lo, u_hi: DEV, u_rows = 1 or T.  NULL = absent; +-inf allowed.
+ *   workspace: DEV, 256-byte aligned, >= irs_box_values_workspace_bytes(n, m, T).  It holds the state of a descent --
+ *   a header, the masks, the T factor records, the warm start (w, y) -- from `begin` to the last `tail`; one descent
+ *   at a time per workspace.  It need not be initialised: `begin` writes all of it, the header last.
+ *   info (3) DEV: begin writes [t+1 of a non-PD Hessian or 0, 0, 0]; each tail updates [1] = most ADMM iterations of
+ *   any tail so far, [2] += 1 if it stopped at max_iter.  A tail whose workspace header does not match (n, m, T,
+ *   begun) writes info[0] = -1 and nothing else.
+ * Every argument error is decided before the first HIP call:
+ *   IRS_ERR_INVALID_ARG  n, m, T or t out of range; a null pointer; x_rows / u_rows not as above; rho <= 0; relax
+ *                        outside (0, 2); max_iter <= 0; eps <= 0
+ *   IRS_ERR_UNSUPPORTED  T > irs_box_values_horizon_limit(n, m)
+ *   IRS_ERR_WORKSPACE    workspace null, too small or not 256-byte aligned                                      */
+typedef struct irs_box_values_call {
+    int n, m, T;
+    const double *At, *Bt, *ct, *Q, *Qd, *R;
+    double alpha_R;
+    const double *xd_trj;
+    const double *x_lo, *x_hi;
+    int x_rows;
+    const double *u_lo, *u_hi;
+    int u_rows;
+    double rho, relax;
+    void *workspace;
+    size_t workspace_bytes;
+    int *info;
+} irs_box_values_call;
+/* No GPU is touched; 0 for invalid sizes.  Non-decreasing in n, m and T: a buffer sized for the largest call serves
+ * every smaller one.                                                                                            */
+size_t irs_box_values_workspace_bytes(int n, int m, int T);
+/* The longest horizon a tail launch serves: its ADMM vectors -- wx, yx, zx (T+1,n), wu, yu, zu, k (T,m) -- stay in
+ * LDS beside the 3-slot record ring.  0 for invalid sizes.  Decided by the planner the launch reads.           */
+int irs_box_values_horizon_limit(int n, int m);
+/* dynamic LDS bytes of a tail launch at horizon T (0 for invalid sizes); <= ~160 KB up to the horizon limit      */
+size_t irs_box_values_lds_bytes(int n, int m, int T);
+int irs_box_values_begin(const irs_box_values_call *call, void *stream);
+/* x_t (n) DEV: the realised state.  u_t (m) DEV: the tail's first control, clipped to its bounds.  x_plan
+ * (T+1-t, n), u_plan (T-t, m) DEV or NULL: the tail's plan (the linear-model rollout of the final iterate); with
+ * t = 0 that is solve_tvlqr's result.  `call` is checked as in `begin`; the launch reads its bounds, sizes, workspace
+ * and info -- the matrices are in the records, and rho and relax are those `begin` wrote to the header.         */
+int irs_box_values_tail(const irs_box_values_call *call, int t, const double *x_t, int max_iter, double eps,
+                        double *u_t, double *x_plan, double *u_plan, void *stream);
 /* The same with a device workspace for horizons whose per-step records do not fit the 160 KB of LDS
  * (solver 3 / 0, and solver 1: the ADMM's factor records, up to irs_tvlqr_box_hbm_lds_bytes(model, T, 1)
  * <= ~160 KB): `workspace` DEV, 256-byte aligned, at least irs_quasistatic_descent_workspace_bytes(model, T,

@@ -13,7 +13,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IRS_HIP_LIB") or os.path.join(_HERE, "csrc", "libirs_hip.so")
 
 IRS_OK = 0
+IRS_ERR_INVALID_ARG = -1
 IRS_ERR_UNSUPPORTED = -3
+IRS_ERR_WORKSPACE = -4
 MODEL_PENDULUM = 0
 MODEL_QUADROTOR = 1
 MODEL_BICYCLE = 2
@@ -239,6 +241,25 @@ SIGNATURES["irs_smooth_values_finalize"] = (c_int, [c_int, c_int, c_int, c_longl
                                                     _dp, c_void_p])
 SIGNATURES["irs_smooth_values"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                            _dp, _dp, _dp, c_size_t, c_void_p])
+
+
+class BoxValuesCall(ctypes.Structure):
+    """irs_box_values_call (include/irs_hip.h)."""
+    _fields_ = [("n", c_int), ("m", c_int), ("T", c_int),
+                ("At", c_void_p), ("Bt", c_void_p), ("ct", c_void_p), ("Q", c_void_p), ("Qd", c_void_p),
+                ("R", c_void_p), ("alpha_R", c_double), ("xd_trj", c_void_p),
+                ("x_lo", c_void_p), ("x_hi", c_void_p), ("x_rows", c_int),
+                ("u_lo", c_void_p), ("u_hi", c_void_p), ("u_rows", c_int),
+                ("rho", c_double), ("relax", c_double),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("info", c_void_p)]
+
+
+# the any-size bounded TV-LQR (csrc/boxqp_values.hip): sizes (n, m, T) instead of a model
+SIGNATURES["irs_box_values_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int])
+SIGNATURES["irs_box_values_horizon_limit"] = (c_int, [c_int, c_int])
+SIGNATURES["irs_box_values_lds_bytes"] = (c_size_t, [c_int, c_int, c_int])
+SIGNATURES["irs_box_values_begin"] = (c_int, [POINTER(BoxValuesCall), c_void_p])
+SIGNATURES["irs_box_values_tail"] = (c_int, [POINTER(BoxValuesCall), c_int, _dp, c_int, c_double, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_smooth_run"] = (c_int, [POINTER(SmoothCall), c_void_p])
 SIGNATURES["irs_descent_run"] = (c_int, [POINTER(DescentCall), c_void_p])
 SIGNATURES["irs_comm_available"] = (c_int, [])

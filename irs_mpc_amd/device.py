@@ -908,3 +908,88 @@ def smooth_values(x_trj, u_trj, dx, du, fz, f0, fnom, out=None, workspace=None):
                                         _ptr(o["At"], F64), _ptr(o["Bt"], F64), _ptr(o["ct"], F64), o["info"].data_ptr(),
                                         ws.data_ptr(), ws.numel(), _stream()), "irs_smooth_values")
     return o
+
+
+# ---- bounded TV-LQR of any size, resumable from tail to tail (csrc/boxqp_values.hip) ----
+def box_values_horizon_limit(n, m):
+    """The longest horizon the any-size bounded kernel serves at (n, m) (irs_box_values_horizon_limit); 0 for sizes
+    out of range.  No launch, no device."""
+    return _lib.load().irs_box_values_horizon_limit(int(n), int(m))
+
+
+_box_values_ws = {}
+
+
+def _box_values_workspace(n, m, T, device):
+    """The cached workspace of the any-size bounded kernel for (`device`, the current stream), grown on demand.  It
+    holds one descent's state from `begin` to its last `tail`; one per stream, like the values pass's scratch."""
+    need = _lib.load().irs_box_values_workspace_bytes(n, m, T)
+    key = (device, _stream())
+    ws = _box_values_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _box_values_ws[key] = torch.empty((max(need, 256),), dtype=torch.uint8, device=device)
+    return ws
+
+
+def _bound_rows(b, width):
+    """(tensor, rows) of a bound given as (width,) or (rows, width); (None, 1) for None."""
+    if b is None:
+        return None, 1
+    assert b.shape[-1] == width and b.dim() in (1, 2), tuple(b.shape)
+    return b, (1 if b.dim() == 1 else b.shape[0])
+
+
+def box_values_handle(At, Bt, ct, Q, Qd, R, xd_trj, x_lo=None, x_hi=None, u_lo=None, u_hi=None, alpha_R=0.5, rho=10.0,
+                      relax=1.6, workspace=None, info=None):
+    """The description of one bounded descent (irs_box_values_call) without a launch: what box_values_begin starts and
+    box_values_tail resumes.  Bounds: (n,) / (m,) for every step, or (T+1, n) / (T, m) rows; None = absent.  Keeps the
+    tensors it points at alive.  workspace: a uint8 tensor (default: the cached one of this device and stream)."""
+    T, n, m = At.shape[0], At.shape[1], Bt.shape[2]
+    device = At.device
+    ws = workspace if workspace is not None else _box_values_workspace(n, m, T, device)
+    if info is None:
+        info = torch.zeros((3,), dtype=torch.int32, device=device)
+    (x_lo, rx0), (x_hi, rx1) = _bound_rows(x_lo, n), _bound_rows(x_hi, n)
+    (u_lo, ru0), (u_hi, ru1) = _bound_rows(u_lo, m), _bound_rows(u_hi, m)
+    if (x_lo is not None and x_hi is not None and rx0 != rx1) or (u_lo is not None and u_hi is not None and ru0 != ru1):
+        raise ValueError("the two sides of a bound need the same number of rows")
+    c = _lib.BoxValuesCall(n=n, m=m, T=T, At=_ptr(At, F64), Bt=_ptr(Bt, F64), ct=_ptr(ct, F64), Q=_ptr(Q, F64),
+                           Qd=_ptr(Qd, F64), R=_ptr(R, F64), alpha_R=float(alpha_R), xd_trj=_ptr(xd_trj, F64),
+                           x_lo=_ptr(x_lo, F64), x_hi=_ptr(x_hi, F64), x_rows=rx0 if x_lo is not None else rx1,
+                           u_lo=_ptr(u_lo, F64), u_hi=_ptr(u_hi, F64), u_rows=ru0 if u_lo is not None else ru1,
+                           rho=float(rho), relax=float(relax), workspace=ws.data_ptr(), workspace_bytes=ws.numel(),
+                           info=info.data_ptr())
+    return dict(call=c, n=n, m=m, T=T, info=info, workspace=ws, device=device,
+                keep=(At, Bt, ct, Q, Qd, R, xd_trj, x_lo, x_hi, u_lo, u_hi))
+
+
+def box_values_begin(At, Bt, ct, Q, Qd, R, xd_trj, x_lo=None, x_hi=None, u_lo=None, u_hi=None, alpha_R=0.5, rho=10.0,
+                     relax=1.6, workspace=None, info=None):
+    """Start a bounded descent: one launch factorises the whole horizon into the workspace (irs_box_values_begin).
+    Returns the handle box_values_tail takes; handle["info"] (3,) int32 is the descent's info."""
+    h = box_values_handle(At, Bt, ct, Q, Qd, R, xd_trj, x_lo, x_hi, u_lo, u_hi, alpha_R, rho, relax, workspace, info)
+    check(_lib.load().irs_box_values_begin(ctypes.byref(h["call"]), _stream()), "irs_box_values_begin")
+    return h
+
+
+def box_values_tail(h, t, x_t, max_iter=5000, eps=1e-8, u_t=None, x_plan=None, u_plan=None):
+    """Solve the tail QP t..T of a begun descent from the state x_t (n) -- one launch, warm started from the previous
+    tail (irs_box_values_tail).  Returns u_t (m): the tail's first control, clipped; x_plan (T+1-t, n) / u_plan
+    (T-t, m), where given, receive the tail's plan."""
+    if u_t is None:
+        u_t = torch.empty((h["m"],), dtype=F64, device=h["device"])
+    check(_lib.load().irs_box_values_tail(ctypes.byref(h["call"]), int(t), _ptr(x_t, F64), int(max_iter), float(eps),
+                                          _ptr(u_t, F64), _ptr(x_plan, F64), _ptr(u_plan, F64), _stream()),
+          "irs_box_values_tail")
+    return u_t
+
+
+def box_values_solve(At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo=None, x_hi=None, u_lo=None, u_hi=None, alpha_R=0.5, rho=10.0,
+                     relax=1.6, max_iter=5000, eps=1e-8, workspace=None):
+    """solve_tvlqr stand-alone at any size: begin, tail 0, its plan.  Returns dict(x_star, u_star, info[3])."""
+    h = box_values_begin(At, Bt, ct, Q, Qd, R, xd_trj, x_lo, x_hi, u_lo, u_hi, alpha_R, rho, relax, workspace)
+    T, n, m = h["T"], h["n"], h["m"]
+    x_star = torch.zeros((T + 1, n), dtype=F64, device=h["device"])
+    u_star = torch.zeros((T, m), dtype=F64, device=h["device"])
+    box_values_tail(h, 0, x0, max_iter, eps, x_plan=x_star, u_plan=u_star)
+    return dict(x_star=x_star, u_star=u_star, info=h["info"])

@@ -53,6 +53,10 @@ class IrsLqrParameters:
         # converged plan would push out of the box carry the ADMM's penalty term; each descent hands its final set to
         # the next.  Like qp_adaptive_rho it runs descent by descent
         self.qp_lazy_bounds = False
+        # extension: a TorchDynamicalSystem (no device functor) whose box bound binds takes the stepped bounded descent
+        # (csrc/boxqp_values.hip: one factorisation, then per t one tail QP launch and one torch step) instead of
+        # raising; fixed penalty only.  Ignored for compiled systems, whose descent is one launch
+        self.qp_model_free = False
 
 
 class IrsLqr:
@@ -153,9 +157,15 @@ class IrsLqr:
         if box is None or self._tail_plans_within_bounds(At, Bt, ct, o["K"], o["k"], o["x_new"]):
             return o["x_new"], o["u_new"], o["cost"]
         if not self._compiled():
-            raise NotImplementedError(
-                "a box bound is active: bounded descents need a compiled device model (a functor in "
-                "irs_mpc_amd/csrc/models.hpp); a TorchDynamicalSystem runs while no bound binds")
+            if not bool(getattr(self.params, "qp_model_free", False)):
+                raise NotImplementedError(
+                    "a box bound is active: bounded descents need a compiled device model (a functor in "
+                    "irs_mpc_amd/csrc/models.hpp); a TorchDynamicalSystem runs while no bound binds, or with "
+                    "params.qp_model_free = True (the stepped descent: one tail QP launch and one torch step per t)")
+            for flag in ("qp_adaptive_rho", "qp_lazy_bounds"):
+                if bool(getattr(self.params, flag, False)):
+                    raise NotImplementedError("params.%s needs a compiled device model: the stepped bounded descent "
+                                              "(qp_model_free) has the fixed penalty and enforces every bound" % flag)
         if not self._dm.box_descent_supported(self.T):
             raise NotImplementedError(
                 "a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
@@ -176,7 +186,8 @@ class IrsLqr:
 
     def _compiled(self):
         """Whether the system runs on a device functor (DeviceModel); False for a TorchDynamicalSystem, whose model
-        only torch can evaluate: no fused irs_iterate loop, no bounded descent."""
+        only torch can evaluate: no fused irs_iterate loop, and a bounded descent only as the stepped one
+        (params.qp_model_free)."""
         return getattr(self._dm, "compiled", True)
 
     def _adaptive_rho(self):

@@ -25,9 +25,15 @@ their least-squares solves are the values pass (csrc/smooth_values.hip, device.s
 cost and the plan test are the model-free kernels every compiled system uses; the first-order mode is the float64 mean
 of the sampled Jacobians in torch.
 
-Limits: dim_x <= 32, dim_u <= 16; samples are evaluated in float32; a rollout is T torch steps; no bounded descent
-(a box bound that would bind raises NotImplementedError: that needs a compiled model) and no fused `irs_iterate` loop.
-CrossEntropyMethod, the quasistatic classes and `solve_tvlqr` with bounds stay compiled-models-only.
+Bounds: a box bound that binds takes the stepped bounded descent when IrsLqrParameters.qp_model_free is set
+(TorchDeviceModel.tvlqr_box_descent: one factorisation, then per t one tail-QP launch of csrc/boxqp_values.hip and one
+float64 step of the callable, all on the current stream with nothing read on the host); without the flag it raises
+NotImplementedError, as a compiled model is then needed.
+
+Limits: dim_x <= 32, dim_u <= 16; samples are evaluated in float32; a rollout is T torch steps; the bounded descent
+has the fixed penalty only (qp_adaptive_rho and qp_lazy_bounds are compiled-only) and a horizon limit
+(box_horizon_limit); no fused `irs_iterate` loop.  CrossEntropyMethod, the quasistatic classes and the
+position-controlled form of `solve_tvlqr` stay compiled-models-only.
 """
 import numpy as np
 import torch
@@ -68,7 +74,7 @@ class TorchDeviceModel:
     """What `IrsLqr` calls on `system.dm()`, for a TorchDynamicalSystem: the method names, signatures and result keys
     of device.DeviceModel."""
 
-    compiled = False            # no device functor: no fused loop, no bounded descent
+    compiled = False            # no device functor: no fused loop; bounded descents are stepped (tvlqr_box_descent)
     model_id = None
 
     def __init__(self, system):
@@ -234,7 +240,31 @@ class TorchDeviceModel:
         return dict(K=K, k=k, x_new=x_new, u_new=u_new, cost=cost, info=info)
 
     def box_descent_supported(self, T, du=False):
-        return False
+        """Whether the stepped bounded descent runs horizon T (the plain form only: du has no any-size kernel)."""
+        return 0 < int(T) <= self.box_horizon_limit(du)
 
     def box_horizon_limit(self, du=False):
-        return 0
+        """The longest horizon of the any-size bounded kernel at this (n, m) (irs_box_values_horizon_limit)."""
+        return 0 if du else dev.box_values_horizon_limit(self.n, self.m)
+
+    def tvlqr_box_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, xlo, xhi, ulo, uhi, alpha_R=0.5,
+                          rho=10.0, relax=1.6, max_iter=5000, eps=1e-8, records_in_hbm=False, adaptive_rho=False,
+                          lazy_bounds=False, enforced=None):
+        """local_descent with active abs bounds, the signature and result keys of DeviceModel.tvlqr_box_descent:
+        one factorisation (irs_box_values_begin), then for every t one warm-started tail QP (irs_box_values_tail)
+        and one float64 step of the callable from the realised state -- 1 + T launches and T torch steps on the
+        current stream, nothing read on the host.  The factor records are always in HBM.  Returns
+        dict(x_new, u_new, info[3])."""
+        if adaptive_rho or lazy_bounds:
+            raise NotImplementedError("the stepped bounded descent of a TorchDynamicalSystem has the fixed penalty only: "
+                                      "%s needs a compiled device model" % ("qp_adaptive_rho" if adaptive_rho
+                                                                            else "qp_lazy_bounds"))
+        T = At.shape[0]
+        x_new = torch.empty((T + 1, self.n), dtype=dev.F64, device=At.device)
+        u_new = torch.empty((T, self.m), dtype=dev.F64, device=At.device)
+        h = dev.box_values_begin(At, Bt, ct, Q, Qd, R, xd_trj, xlo, xhi, ulo, uhi, alpha_R=alpha_R, rho=rho, relax=relax)
+        x_new[0] = x0
+        for t in range(T):
+            dev.box_values_tail(h, t, x_new[t], max_iter, eps, u_t=u_new[t])
+            x_new[t + 1] = self._step(x_new[t], u_new[t])
+        return dict(x_new=x_new, u_new=u_new, info=h["info"])

@@ -16,7 +16,10 @@ GPU, whatever its options:
 The reference's callers are the MPC loops of `local_descent`; those run as whole-descent kernels
 (irs_tvlqr_descent / irs_tvlqr_box_descent / irs_quasistatic_box_descent_wsx) and do not go through here.
 The bounded kernel is compiled per (dim_x, dim_u) of the registered device models: (2,1), (12,4), (5,2), (6,2),
-(7,4); position-controlled: (7,4) with indices [1,4,2,5], (5,2) with [0,2], (2,1) with [0]; other sizes raise.  `x_bound_rel` ("should be rarely used", irs_lqr_quasistatic.py:315) is not supported in the
+(7,4); position-controlled: (7,4) with indices [1,4,2,5], (5,2) with [0,2], (2,1) with [0].  Every other size of the
+plain form, dim_x <= 32 and dim_u <= 16, goes through the any-size kernels (csrc/boxqp_values.hip: begin + tail 0 + its
+plan; fixed penalty only; T <= irs_box_values_horizon_limit(dim_x, dim_u), e.g. 415 at (9,5), 71 at (32,16)); other
+position-controlled sizes raise.  `x_bound_rel` ("should be rarely used", irs_lqr_quasistatic.py:315) is not supported in the
 position-controlled form; in the plain form the reference bounds free variables with it (dxt / dut are only
 tied to x, u inside the `indices_u_into_x` branch, tv_lqr.py:93-104), i.e. it has no effect, and neither has it here.
 """
@@ -38,6 +41,9 @@ def get_solver(solver_name: str):
     if solver_name in _SOLVERS:
         return RiccatiSolver(solver_name)
     raise ValueError("Do not recognize solver.")
+
+
+_PLAIN_SIZES = ((2, 1), (12, 4), (5, 2), (6, 2), (7, 4))       # the plain sizes _model_for has a compiled kernel for
 
 
 def _model_for(n, m, indices_u_into_x):
@@ -121,9 +127,27 @@ def solve_tvlqr(At, Bt, ct, Q, Qd, R, x0, x_trj_d, solver=None, indices_u_into_x
 
         if inside(xs, x_bound_abs, T + 1, skip=1) and inside(us, u_bound_abs, T):
             return xs, us
-    dm = _model_for(n, m, indices_u_into_x)
     x_lo, x_hi = _rows(x_bound_abs, T + 1, n)
     u_lo, u_hi = _rows(u_bound_abs, T, m)
+    if not position and (n, m) not in _PLAIN_SIZES:
+        # no compiled kernel of this size: the any-size kernel (csrc/boxqp_values.hip), begin + tail 0 + its plan
+        if adaptive_rho or lazy_bounds:
+            raise NotImplementedError("solve_tvlqr with bounds: adaptive_rho / lazy_bounds need a compiled kernel, and "
+                                      "there is none for dim_x=%d, dim_u=%d" % (n, m))
+        limit = dev.box_values_horizon_limit(n, m)
+        if limit == 0:
+            raise NotImplementedError("solve_tvlqr with bounds: no kernel for dim_x=%d, dim_u=%d (dim_x <= 32, "
+                                      "dim_u <= 16)" % (n, m))
+        if T > limit:
+            raise NotImplementedError("solve_tvlqr with bounds: horizon T=%d is beyond the kernel's limit T <= %d"
+                                      % (T, limit))
+        o = dev.box_values_solve(At_d, Bt_d, ct_d, Q_d, Qd_d, R_d, xd_d, x0_d, x_lo, x_hi, u_lo, u_hi, alpha_R=0.5,
+                                 rho=rho, max_iter=max_iter, eps=eps)
+        i = o["info"].cpu().numpy()
+        if i[0] != 0 or i[2] != 0:
+            raise ValueError("TV_LQR failed. Optimization problem is not solved.")
+        return o["x_star"].cpu().numpy(), o["u_star"].cpu().numpy()
+    dm = _model_for(n, m, indices_u_into_x)
     du_lo, du_hi = _rows(u_bound_rel, T, m) if position else (None, None)
     if not dm.box_descent_supported(T, du=position):
         raise NotImplementedError("solve_tvlqr with bounds: horizon T=%d is beyond the kernel's limit T <= %d"
