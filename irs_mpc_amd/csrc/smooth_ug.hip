@@ -11,8 +11,9 @@
 // lane (388 registers: one wave per SIMD) and re-factorises per sample.  Here
 //   * everything uniform lives in LDS (C, J D^-1, the table) or in ONE set of registers per lane (W, r0: 52);
 //   * the workgroup tabulates, once, for ALL 2^8 candidate active sets A the map  r -> [lam_A ; slacks off A]
-//     (G_A: rows of -W_AA^-1 on A -- masked LDL' in row order with the same pivot rule as
-//     irs_contact_qp_dual_exact, a dependent row drops out -- and of I + W M off A), not as G_A itself but as what
+//     (G_A: rows of -W_AA^-1 on A -- row order, with the pivot rule of irs_contact_qp_dual_exact: a dependent row
+//     drops out -- and of I + W M off A; built by principal pivot steps from the empty set, one rank-1 update of an
+//     8 x 13 tableau per row of A, eight lanes per tableau: ug_build_table), not as G_A itself but as what
 //     the sample loop applies it to: G_A r = h_A + H_A du in the QP's four parameters (h_A = G_A r0, H_A = G_A C':
 //     8 + 32 floats) and, for the dual steps, U_A = G_A W (64 floats): 256 x 116 floats in LDS;
 //   * a sample is solved by a few projected sweeps (a guess of A), then primal-dual active-set iterations that
@@ -50,6 +51,10 @@ constexpr int kUgPdas = IRS_UG_PDAS;          // primal-dual active-set iteratio
 #define IRS_UG_STEP_COLUMNS 1
 #endif
 constexpr bool kUgStepColumns = IRS_UG_STEP_COLUMNS != 0;   // zero-order pass: dual steps read a column of G W (0: G and a product)
+#ifndef IRS_UG_TABLE_LDL
+#define IRS_UG_TABLE_LDL 0
+#endif
+constexpr bool kUgTableLdl = IRS_UG_TABLE_LDL != 0;         // the table by one masked LDL' per entry (the build the pivot steps replaced; reference and timing)
 // One table entry, in floats (every piece 16-byte aligned, 464 B per entry):
 //   [ h = G r0 (8) | H = G C' (4 columns of 8, one per command) | tau (8: 1 off the reduced set, 0 on it) |
 //     the reduced set + pad (4) | X (8 x 8, column-major) ]
@@ -329,7 +334,8 @@ __device__ __forceinline__ void ug_full(const UgLds<Model>& S, const float* r, c
     }
 }
 
-// One table entry for the candidate set `a`, by the masked LDL' in row order of irs_contact_qp_dual_exact_try (pivot
+// -DIRS_UG_TABLE_LDL=1 (the build the pivot steps replaced; the reference of tests/test_smooth_ug_table_gpu.py and of
+// same-day timings): one table entry for the candidate set `a`, by the masked LDL' in row order of irs_contact_qp_dual_exact_try (pivot
 // rule included: a dependent row leaves the set).  G_a is never formed: it is APPLIED (a solve on the set with the
 // right-hand side -x_A; x_i + sum_j W_ij y_j on the rows off it) to the 13 vectors the sample loop needs it on --
 // r0 (h), the four C[j][:] (H) and the eight W[:,p] (X = G W; UCOL) or unit vectors (X = G).  `half` (0/1): this lane's
@@ -411,6 +417,133 @@ __device__ __forceinline__ void ug_build_entry(UgLds<Model>& S, unsigned a, int 
         *reinterpret_cast<float4*>(e + kUgTabTau) = make_float4(act[0] ? 0.f : 1.f, act[1] ? 0.f : 1.f, act[2] ? 0.f : 1.f, act[3] ? 0.f : 1.f);
         *reinterpret_cast<float4*>(e + kUgTabTau + 4) = make_float4(act[4] ? 0.f : 1.f, act[5] ? 0.f : 1.f, act[6] ? 0.f : 1.f, act[7] ? 0.f : 1.f);
         e[kUgTabSet] = __uint_as_float(ap);
+    }
+}
+
+// ---- the table by pivot steps ---------------------------------------------------------------------------------
+// Entry A is the tableau of the principal pivot transform of the dual on A: T_A = G_A [r0 | C' | W] (8 x 13), and
+// T_0 = [r0 | C' | W] (G_0 = I).  Its last eight columns G_A W are the pivot columns: for a row p off A with
+// d = (G_A W)[p][p] (the Schur complement of W_pp on A),
+//     rho = -T[p,:] / d,   T[i,:] += (G_A W)[i][p] rho  (i != p),   T[p,:] = rho
+// is T of A + {p}: one reciprocal and 8 x 13 FMAs instead of a factorisation and 13 applications.  Every set is reached
+// from the empty one by pivoting its rows in increasing order -- the order of the masked LDL' above, whose pivot of row
+// p IS d -- with that build's rule: a row with d <= 1e-5 W_pp is not pivoted (the entry is that of the set without it).
+// The first-order pass stores G_A itself: eight more columns that start as the identity ride along.
+//
+// Eight lanes carry one tableau in registers, COLUMNS across the lanes (lane l: columns l, 8 + l [, 16 + l], eight
+// rows each): a step needs the pivot column on every lane -- 8 broadcasts within the eight lanes, against 13 for the
+// pivot row had the rows been dealt out -- and then only values of its own (rho_c = T[p][c] rinv; 7 FMAs; T[p][c] = rho_c
+// with p a compile-time register index, no select by lane); and an entry is stored column by column, which is how it
+// lies in LDS (two ds_write_b128 per column).
+//   column:  0 h | 1..4 H | 5..12 G W | 13..15 unused | 16..23 G (first-order pass)
+template <int NS>
+struct UgTableau {
+    float c[NS][8];    // this lane's columns 8 s + l
+    unsigned set;      // the reduced set (the same on the eight lanes)
+};
+
+// lane P of every group of eight lanes (ds_swizzle, bit-mask mode: lane' = (lane & 0x18) | P within each 32)
+template <int P>
+__device__ __forceinline__ float ug_bcast8(float v) {
+    return __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(v), 0x18 | (P << 5)));
+}
+
+// the pivot on row P where `want` (the same on the eight lanes of a tableau) and the pivot rule allow it
+template <int P, int NS>
+__device__ __forceinline__ void ug_pivot(UgTableau<NS>& R, bool want, float wpp) {
+    constexpr float piv_rel = 1e-5f;
+    constexpr int PS = (5 + P) >> 3, PL = (5 + P) & 7;     // where column P of G W lives
+    float x[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) x[i] = ug_bcast8<PL>(R.c[PS][i]);
+    const float d = x[P];
+    const bool ok = want && d > piv_rel * wpp;
+    const float rinv = ok ? -irs_rcp_fast(d) : 0.f;        // not taken: rho = 0 and every row stays what it is
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const float rho = R.c[s][P] * rinv;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (i != P) R.c[s][i] = fmaf(x[i], rho, R.c[s][i]);
+        R.c[s][P] = ok ? rho : R.c[s][P];
+    }
+    R.set |= ok ? (1u << P) : 0u;
+}
+
+// lane l of the eight stores its columns of entry `a`.  Three of the eight have no second column (zero-order pass) or
+// no h / H column (first-order pass): they store tau (lanes 5, 6) and the set with its pad (lane 7) in the same
+// ds_write_b128 as the others' half columns, so an entry is four stores.  (Columns four apart share their banks, a
+// 2-way conflict; letting some lanes store their upper half first removes most of it and was measured SLOWER, by 550
+// ticks per workgroup: the selects cost more than the conflicts.)
+template <class Model, bool UCOL, int NS>
+__device__ __forceinline__ void ug_emit_entry(UgLds<Model>& S, unsigned a, const UgTableau<NS>& R, int l) {
+    float* e = &S.tab[a][0];
+    auto put = [&](int off, const float* v) {
+        *reinterpret_cast<float4*>(e + off) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4*>(e + off + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    };
+    // the full columns: h, H, G W columns 0..2 (zero-order pass) / G (first-order pass)
+    if constexpr (UCOL) put(l < 5 ? 8 * l : kUgTabX + 8 * (l - 5), R.c[0]);
+    else put(kUgTabX + 8 * l, R.c[2]);
+    // lanes 0..4: G W columns 3..7 / h, H; lanes 5..7: tau and the set
+    const float* v = UCOL ? R.c[1] : R.c[0];
+    const int half = l == 6 ? 4 : 0;
+    float4 q;
+    q.x = l < 5 ? v[0] : (l == 7 ? __uint_as_float(R.set) : (((R.set >> (half + 0)) & 1u) ? 0.f : 1.f));
+    q.y = l < 5 ? v[1] : (l == 7 ? 0.f : (((R.set >> (half + 1)) & 1u) ? 0.f : 1.f));
+    q.z = l < 5 ? v[2] : (l == 7 ? 0.f : (((R.set >> (half + 2)) & 1u) ? 0.f : 1.f));
+    q.w = l < 5 ? v[3] : (l == 7 ? 0.f : (((R.set >> (half + 3)) & 1u) ? 0.f : 1.f));
+    const int off = l < 5 ? (UCOL ? kUgTabX + 8 * (l + 3) : 8 * l) : (l == 7 ? kUgTabSet : kUgTabTau + half);
+    *reinterpret_cast<float4*>(e + off) = q;
+    if (l < 5) *reinterpret_cast<float4*>(e + off + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+
+// All 256 entries: 64 tableaux of eight lanes.  Tableau g (6 bits) pivots the rows 0..5 that g has, emits entry g, and
+// reaches g|64, g|128 and g|192 by pivots on rows 6 and 7 (row 7 once on a copy of g's tableau, once after row 6).
+// The eight tableaux of a wave differ in the bits 0..2 -- those steps run for everyone, `want` decides -- and share the
+// bits 3..5, whose steps the wave skips when it does not have them; the two waves of a SIMD (w and w + 4) are given
+// complementary shared bits, so every SIMD runs 15 steps.
+template <class Model, bool UCOL>
+__device__ __forceinline__ void ug_build_table(UgLds<Model>& S, int tid) {
+    constexpr int NC = Model::NC, NS = UCOL ? 2 : 3, NW = kUgBlock / 64;
+    static_assert(NC == 8 && Model::NU == 4, "an 8 x 13 tableau, eight lanes each");
+    const int l = tid & 7;
+    for (int w = __builtin_amdgcn_readfirstlane(tid >> 6); w < 8; w += NW) {
+        const unsigned shared = (unsigned)(w ^ ((w & 4) ? 3 : 0));
+        const unsigned g = ((unsigned)(tid >> 3) & 7u) | (shared << 3);
+        UgTableau<NS> R;
+        {
+            // T_0: column 0 = r0, 1..4 = C[j][:], 5..12 = W[:,c] (W is symmetric to the bit) [, G_0 = I]
+            const float* c0 = l == 0 ? &S.r0[0] : (l < 5 ? &S.C[l - 1][0] : &S.W[l - 5][0]);
+            const float* c1 = &S.W[l < 5 ? l + 3 : 0][0];              // lanes 5..7: an unused column, kept finite
+            const float4 a0 = *reinterpret_cast<const float4*>(c0), a1 = *reinterpret_cast<const float4*>(c0 + 4);
+            const float4 b0 = *reinterpret_cast<const float4*>(c1), b1 = *reinterpret_cast<const float4*>(c1 + 4);
+            R.c[0][0] = a0.x; R.c[0][1] = a0.y; R.c[0][2] = a0.z; R.c[0][3] = a0.w;
+            R.c[0][4] = a1.x; R.c[0][5] = a1.y; R.c[0][6] = a1.z; R.c[0][7] = a1.w;
+            R.c[1][0] = b0.x; R.c[1][1] = b0.y; R.c[1][2] = b0.z; R.c[1][3] = b0.w;
+            R.c[1][4] = b1.x; R.c[1][5] = b1.y; R.c[1][6] = b1.z; R.c[1][7] = b1.w;
+            if constexpr (!UCOL) {
+#pragma unroll
+                for (int i = 0; i < NC; ++i) R.c[2][i] = (l == i) ? 1.f : 0.f;
+            }
+        }
+        R.set = 0u;
+        ug_pivot<0>(R, (g & 1u) != 0u, S.Wd[0]);
+        ug_pivot<1>(R, (g & 2u) != 0u, S.Wd[1]);
+        ug_pivot<2>(R, (g & 4u) != 0u, S.Wd[2]);
+        if (shared & 1u) ug_pivot<3>(R, true, S.Wd[3]);
+        if (shared & 2u) ug_pivot<4>(R, true, S.Wd[4]);
+        if (shared & 4u) ug_pivot<5>(R, true, S.Wd[5]);
+        UgTableau<NS> R6 = R, R7 = R;
+        ug_pivot<6>(R6, true, S.Wd[6]);
+        ug_pivot<7>(R7, true, S.Wd[7]);
+        UgTableau<NS> R67 = R6;
+        ug_pivot<7>(R67, true, S.Wd[7]);
+        // the stores last, back to back: a broadcast queued behind stores would wait for them
+        ug_emit_entry<Model, UCOL>(S, g, R, l);
+        ug_emit_entry<Model, UCOL>(S, g | 64u, R6, l);
+        ug_emit_entry<Model, UCOL>(S, g | 128u, R7, l);
+        ug_emit_entry<Model, UCOL>(S, g | 192u, R67, l);
     }
 }
 
@@ -569,6 +702,86 @@ __device__ unsigned long long ug_stamps[kUgStampWgs * kUgStampSlots];
 #define UG_STAMP(slot) do {} while (0)
 #endif
 
+// The workgroup's prologue: the f32 geometry of the step QP at (x, u) (wave 0), what follows from it (W, r0, J D^-1, C:
+// one quantity per thread) and the table (everyone; `build` false skips it: timing experiments).  Ends on a barrier.
+template <class Model, bool UCOL>
+__device__ __forceinline__ void ug_prologue(const ModelParams& p, const double* x, const double* u, bool build,
+                                            UgLds<Model>& S, int tid) {
+    constexpr int n = Model::NX, m = Model::NU, NC = Model::NC;
+    const int lane = tid & 63, wave = tid >> 6;
+    if (wave == 0) {
+        // the model's QP assembly (trigonometry, closest points): one wave, every lane the same; lane 0 stores
+        float xb[n], ub[m], q[n], Dinv[n], b0[n], J[NC][n], phi[NC];
+#pragma unroll
+        for (int i = 0; i < n; ++i) xb[i] = (float)x[i];
+#pragma unroll
+        for (int j = 0; j < m; ++j) ub[j] = (float)u[j];
+        Model::template assemble<float>(p, xb, ub, q, Dinv, b0, J, phi);
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                S.phi[i] = phi[i];
+#pragma unroll
+                for (int k = 0; k < n; ++k) S.Jc[i][k] = J[i][k];
+            }
+#pragma unroll
+            for (int k = 0; k < n; ++k) { S.Db0[k] = b0[k] * Dinv[k]; S.q[k] = q[k]; S.Dinv[k] = Dinv[k]; }
+#pragma unroll
+            for (int j = 0; j < m; ++j) S.DK[j] = Dinv[Model::act(j)] * Model::template stiffness<float>(p, j);
+        }
+    }
+    __syncthreads();
+    // what follows from it, one quantity per thread (the expressions of irs_contact_qp_dual_exact_try):
+    //   W = J D^-1 J' (entry (i,j) from the row pair (max, min): symmetric to the bit), r0 = phi - J D^-1 b,
+    //   J D^-1, C = J D^-1[:, act] K
+    if (tid < NC * NC) {
+        const int i = tid / NC, j = tid % NC, hi = i > j ? i : j, lo = i > j ? j : i;
+        float w = (S.Jc[hi][0] * S.Dinv[0]) * S.Jc[lo][0];
+#pragma unroll
+        for (int k = 1; k < n; ++k) w = w + (S.Jc[hi][k] * S.Dinv[k]) * S.Jc[lo][k];
+        S.W[i][j] = w;
+        if (i == j) {
+            S.Wd[i] = w;
+            S.invw[i] = (float)kContactPgsOmega * irs_rcp_fast(w);
+        }
+    } else if (tid < NC * NC + NC) {
+        const int i = tid - NC * NC;
+        float ri = S.phi[i];
+#pragma unroll
+        for (int k = 0; k < n; ++k) ri = ri - S.Jc[i][k] * S.Db0[k];
+        S.r0[i] = ri;
+    } else if (tid < 2 * NC * NC + NC) {
+        const int e = tid - (NC * NC + NC), k = e / NC, c = e % NC;
+        if (k < n) S.JD[k][c] = S.Jc[c][k] * S.Dinv[k];
+    } else if (tid < 2 * NC * NC + NC + m * NC) {
+        const int e = tid - (2 * NC * NC + NC), j = e / NC, c = e % NC;
+        S.C[j][c] = (S.Jc[c][Model::act(j)] * S.Dinv[Model::act(j)]) * Model::template stiffness<float>(p, j);
+    }
+    __syncthreads();
+    UG_STAMP(1);
+    if (build) {
+        if constexpr (kUgTableLdl) {
+            for (int e = tid; e < 2 * (1 << NC); e += kUgBlock) ug_build_entry<Model, UCOL>(S, (unsigned)(e >> 1), e & 1);
+        } else {
+            ug_build_table<Model, UCOL>(S, tid);
+        }
+    }
+    __syncthreads();
+}
+
+// One workgroup runs the prologue at one state and copies the table out (irs_debug_ug_table; the pad of an entry as 0).
+template <class Model, bool UCOL>
+__global__ __launch_bounds__(kUgBlock) void ug_table_kernel(ModelParams p, const double* x, const double* u, float* out) {
+    __shared__ UgLds<Model> S;
+    const int tid = threadIdx.x;
+    ug_prologue<Model, UCOL>(p, x, u, true, S, tid);
+    constexpr int NE = 1 << Model::NC;
+    for (int q = tid; q < NE * kUgTabStride; q += kUgBlock) {
+        const int c = q % kUgTabStride;
+        out[q] = (c > kUgTabSet && c < kUgTabX) ? 0.f : S.tab[q / kUgTabStride][c];
+    }
+}
+
 // BATCH (smooth_common.hpp, SmoothRow): grid (nblk, B T); `a` is then the view of the row's problem, set up at the entry
 template <class Model, int MODE, bool RNG, bool FUSE, bool BATCH>
 __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, std::conditional_t<BATCH, SmoothBatch, SmoothSolo> bat) {
@@ -603,62 +816,10 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
     const bool nominal_wave = blk == 0 && wave == NW - 1;
     double nom_r = 0.0;
     if (nominal_wave && !(a.diag & 2)) nom_r = ug_nominal_geometry<Model>(a, nomL, t, lane);
-    if (wave == 0) {
-        // the model's QP assembly (trigonometry, closest points): one wave, every lane the same; lane 0 stores
-        float xb[n], ub[m], q[n], Dinv[n], b0[n], J[NC][n], phi[NC];
-#pragma unroll
-        for (int i = 0; i < n; ++i) xb[i] = (float)a.x_trj[(size_t)t * n + i];
-#pragma unroll
-        for (int j = 0; j < m; ++j) ub[j] = (float)a.u_trj[(size_t)t * m + j];
-        Model::template assemble<float>(a.p, xb, ub, q, Dinv, b0, J, phi);
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < NC; ++i) {
-                S.phi[i] = phi[i];
-#pragma unroll
-                for (int k = 0; k < n; ++k) S.Jc[i][k] = J[i][k];
-            }
-#pragma unroll
-            for (int k = 0; k < n; ++k) { S.Db0[k] = b0[k] * Dinv[k]; S.q[k] = q[k]; S.Dinv[k] = Dinv[k]; }
-#pragma unroll
-            for (int j = 0; j < m; ++j) S.DK[j] = Dinv[Model::act(j)] * Model::template stiffness<float>(a.p, j);
-        }
-    }
     if constexpr (TR::FIRST_B) {
         for (int q = tid; q < (1 << NC); q += BLOCK) hist[q] = 0u;
     }
-    __syncthreads();
-    // what follows from it, one quantity per thread (the expressions of irs_contact_qp_dual_exact_try):
-    //   W = J D^-1 J' (entry (i,j) from the row pair (max, min): symmetric to the bit), r0 = phi - J D^-1 b,
-    //   J D^-1, C = J D^-1[:, act] K
-    if (tid < NC * NC) {
-        const int i = tid / NC, j = tid % NC, hi = i > j ? i : j, lo = i > j ? j : i;
-        float w = (S.Jc[hi][0] * S.Dinv[0]) * S.Jc[lo][0];
-#pragma unroll
-        for (int k = 1; k < n; ++k) w = w + (S.Jc[hi][k] * S.Dinv[k]) * S.Jc[lo][k];
-        S.W[i][j] = w;
-        if (i == j) {
-            S.Wd[i] = w;
-            S.invw[i] = (float)kContactPgsOmega * irs_rcp_fast(w);
-        }
-    } else if (tid < NC * NC + NC) {
-        const int i = tid - NC * NC;
-        float ri = S.phi[i];
-#pragma unroll
-        for (int k = 0; k < n; ++k) ri = ri - S.Jc[i][k] * S.Db0[k];
-        S.r0[i] = ri;
-    } else if (tid < 2 * NC * NC + NC) {
-        const int e = tid - (NC * NC + NC), k = e / NC, c = e % NC;
-        if (k < n) S.JD[k][c] = S.Jc[c][k] * S.Dinv[k];
-    } else if (tid < 2 * NC * NC + NC + m * NC) {
-        const int e = tid - (2 * NC * NC + NC), j = e / NC, c = e % NC;
-        S.C[j][c] = (S.Jc[c][Model::act(j)] * S.Dinv[Model::act(j)]) * Model::template stiffness<float>(a.p, j);
-    }
-    __syncthreads();
-    UG_STAMP(1);
-    if (!(a.diag & 4))
-        for (int e = tid; e < 2 * (1 << NC); e += BLOCK) ug_build_entry<Model, UCOL>(S, (unsigned)(e >> 1), e & 1);
-    __syncthreads();
+    ug_prologue<Model, UCOL>(a.p, a.x_trj + (size_t)t * n, a.u_trj + (size_t)t * m, !(a.diag & 4), S, tid);
 
     UG_STAMP(2);
     // the uniform operands of the sweeps, in VECTOR registers (one copy per lane).  Measured on gfx950
@@ -905,6 +1066,35 @@ extern "C" int irs_debug_ug_stamps(unsigned long long* host_out, int n_wgs) {
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(ug_stamps), (size_t)n_wgs * kUgStampSlots * sizeof(unsigned long long));
 }
 #endif
+
+// The table of one state as the sample pass builds it (first_order: the first-order pass's, whose X block is G): 256
+// entries of 116 floats in the layout above.  params, x (7), u (4) and out are HOST pointers.  A test hook, not part of
+// include/irs_hip.h.
+extern "C" int irs_debug_ug_table(int model, const double* params, const double* x, const double* u, int first_order,
+                                  float* out_256x116) {
+    using Model = PlanarHandExactModel;
+    if (model != IRS_MODEL_PLANAR_HAND_EXACT) return IRS_ERR_UNSUPPORTED;
+    IRS_CHECK_ARG(x && u && out_256x116, "null pointer");
+    ModelParams p;
+    int rc = irs_load_params(model, params, Model::NPARAMS, &p);
+    if (rc != IRS_OK) return rc;
+    constexpr size_t NOUT = (size_t)(1 << Model::NC) * kUgTabStride;
+    double* dxu = nullptr;
+    float* dout = nullptr;
+    if (hipMalloc(&dxu, (Model::NX + Model::NU) * sizeof(double)) != hipSuccess) return IRS_ERR_HIP;
+    if (hipMalloc(&dout, NOUT * sizeof(float)) != hipSuccess) { (void)hipFree(dxu); return IRS_ERR_HIP; }
+    hipError_t e = hipMemcpy(dxu, x, Model::NX * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dxu + Model::NX, u, Model::NU * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        if (first_order) hipLaunchKernelGGL((ug_table_kernel<Model, false>), dim3(1), dim3(kUgBlock), 0, 0, p, dxu, dxu + Model::NX, dout);
+        else hipLaunchKernelGGL((ug_table_kernel<Model, kUgStepColumns>), dim3(1), dim3(kUgBlock), 0, 0, p, dxu, dxu + Model::NX, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(out_256x116, dout, NOUT * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(dxu);
+    (void)hipFree(dout);
+    return e == hipSuccess ? IRS_OK : IRS_ERR_HIP;
+}
 
 bool irs_smooth_ug_supported(int model, int mode) {
     const char* e = getenv("IRS_UG");
