@@ -1429,8 +1429,9 @@ def quasistatic_bounds(x_trj, idx, x_bounds_abs=None, u_bounds_abs=None, u_bound
     if u_bounds_abs is not None:
         u_lo, u_hi = x_trj[:-1, idx] + u_bounds_abs[0], x_trj[:-1, idx] + u_bounds_abs[1]
     if u_bounds_rel is not None:
-        du_lo = np.tile(np.asarray(u_bounds_rel[0], float), (T, 1))
-        du_hi = np.tile(np.asarray(u_bounds_rel[1], float), (T, 1))
+        # (m) rows repeat over the horizon; (T, m) rows are per time step, as the abs offsets may be
+        du_lo = np.broadcast_to(np.asarray(u_bounds_rel[0], float), (T, m)).copy()
+        du_hi = np.broadcast_to(np.asarray(u_bounds_rel[1], float), (T, m)).copy()
     return x_lo, x_hi, u_lo, u_hi, du_lo, du_hi
 
 
