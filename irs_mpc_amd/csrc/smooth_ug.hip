@@ -17,11 +17,14 @@
 //     the sample loop applies it to: G_A r = h_A + H_A du in the QP's four parameters (h_A = G_A r0, H_A = G_A C':
 //     8 + 32 floats) and, for the dual steps, U_A = G_A W (64 floats): 256 x 116 floats in LDS;
 //   * a sample is solved by a few projected sweeps (a guess of A), then primal-dual active-set iterations that
-//     cost ONE affine table row (12 reads, 40 FMA) each: A <- (A minus rows with lam_i <= 0) + rows with slack < 0,
-//     until the KKT conditions hold -- the exact optimum of the QP, certified per sample;
-//   * samples that do not settle within the iteration cap are parked in the wave's LDS ring (as in smooth.hip)
-//     and finished 64 at a time by the Goldfarb-Idnani dual active-set method (finite, no cycling), whose step
-//     reads its direction as one column of U_A (first-order pass: one row of W and a product with G_A);
+//     cost ONE affine table row (12 reads, 40 FMA) each: A <- (A minus the ONE row with the most negative lam_i) +
+//     every row with slack < 0 (ug_pdas: releasing all rows with lam_i <= 0 at once cycles on this W), until the KKT
+//     conditions hold -- the exact optimum of the QP, certified per sample;
+//   * samples that do not settle within the iteration cap (a tenth of the benchmark's) are parked in the wave's LDS ring
+//     (as in smooth.hip) and finished 64 at a time: first more of the same iterations from the parked set, which
+//     settle all but a few in 10^5, then, for what is left, the Goldfarb-Idnani dual active-set method (finite, no
+//     cycling), whose step reads its direction as one column of U_A (first-order pass: one row of W and a product
+//     with G_A);
 //   * zero-order statistics: sum z z', sum z lam', sum z -- the primal step is a UNIFORM linear map of lam, so
 //     it is applied once per workgroup to the sums (sum z df' = (sum z lam') (J D^-1) - ...), not per sample;
 //   * first-order statistics: the derivative of the step through its active set depends on the active set
@@ -38,8 +41,15 @@ namespace {
 #ifndef IRS_UG_SWEEPS
 #define IRS_UG_SWEEPS 6
 #endif
+#ifndef IRS_UG_FLIP_ALL
+#define IRS_UG_FLIP_ALL 0
+#endif
+constexpr bool kUgFlipAll = IRS_UG_FLIP_ALL != 0;           // the iteration flips every non-optimal row at once (the rule the single release replaced, with its caps 4 / 0; same-day timing)
 #ifndef IRS_UG_PDAS
-#define IRS_UG_PDAS 4
+#define IRS_UG_PDAS (IRS_UG_FLIP_ALL ? 4 : 3)
+#endif
+#ifndef IRS_UG_PDAS_FLUSH
+#define IRS_UG_PDAS_FLUSH (IRS_UG_FLIP_ALL ? 0 : 8)
 #endif
 #ifndef IRS_UG_BLOCK
 #define IRS_UG_BLOCK 512
@@ -47,6 +57,7 @@ namespace {
 constexpr int kUgBlock = IRS_UG_BLOCK;
 constexpr int kUgSweeps = IRS_UG_SWEEPS;      // projected sweeps that guess the active set
 constexpr int kUgPdas = IRS_UG_PDAS;          // primal-dual active-set iterations of the first attempt
+constexpr int kUgPdasFlush = IRS_UG_PDAS_FLUSH;   // further iterations a parked sample gets in the flush, before the dual steps
 #ifndef IRS_UG_STEP_COLUMNS
 #define IRS_UG_STEP_COLUMNS 1
 #endif
@@ -189,6 +200,55 @@ __device__ __forceinline__ float ug_rhs(const UgUni<Model::NC>& U, const UgLds<M
     return 1e-6f * scale;
 }
 
+// Up to CAP primal-dual active-set iterations from the set `a`, one affine table row each.  With v the row at the
+// reduced set ap and `bad` the rows that are not optimal (the sign bits of v):
+//   every row off ap whose slack is below -tol joins (viol = bad & ~ap);
+//   of the rows on ap whose multiplier is not positive (neg = bad & ap) exactly ONE leaves, the most negative one:
+//       a <- (ap & ~worst) | viol.
+// Flipping every bad row at once (-DIRS_UG_FLIP_ALL=1: a <- ap ^ bad, the rule this one replaced) cycles on this W,
+// which is no M-matrix: 13 % of the benchmark's samples are unsettled after 4 iterations and still 6 % after 11;
+// releasing one row at a time leaves 3 % after 4, 0.4 % after 6 and 0.03 % after 11.
+// The worst row is the maximum of one unsigned key per row: the bit pattern of v_i (a row off ap pushed to +3e38, so
+// its sign bit is clear) with the low three mantissa bits replaced by 7 - i.  Among keys with the sign bit set the
+// largest is the most negative multiplier; multipliers that agree in all but those three bits tie, and the tie goes to
+// the LOWEST row index (tests/helpers/ug_release_twin.py packs the same key).
+// A lane that is `done` keeps lam and a.  A lane that settles takes lam = v on the set, 0 off it; else `a` is the set to
+// try next (a warm start for more iterations or for ug_full).
+template <class Model, int CAP>
+__device__ __forceinline__ void ug_pdas(const UgLds<Model>& S, const float* du, float tolv, unsigned& a, float* lam, bool& done) {
+    constexpr int NC = Model::NC;
+    static_assert(NC == 8, "the release key packs a row index into three mantissa bits");
+    for (int it = 0; it < CAP; ++it) {
+        float v[NC], tau[NC];
+        const unsigned ap = ug_lookup_affine<Model>(S, a, du, tolv, v, tau);
+        // the sign bits, shifted in one v_alignbit each: row 0 ends in bit 0.  A multiplier of exactly +0 stays: it
+        // satisfies the KKT conditions as it is
+        unsigned bad = 0u;
+#pragma unroll
+        for (int i = NC - 1; i >= 0; --i) bad = __builtin_amdgcn_alignbit(bad, __float_as_uint(v[i]), 31);
+        unsigned next;
+        if constexpr (kUgFlipAll) {
+            next = ap ^ bad;
+        } else {
+            unsigned key = 0u;
+#pragma unroll
+            for (int i = 0; i < NC; ++i)
+                key = max(key, (__float_as_uint(fmaf(tau[i], 3.0e38f, v[i])) & ~7u) | (unsigned)(7 - i));
+            const unsigned worst = (bad & ap) != 0u ? (0x80u >> (key & 7u)) : 0u;
+            next = (ap & ~worst) | (bad & ~ap);
+        }
+        if (!done) {
+            if (bad == 0u) {
+#pragma unroll
+                for (int i = 0; i < NC; ++i) lam[i] = fmaf(-tau[i], v[i], v[i]);      // v on the set, 0 off it
+                done = true;
+            }
+            a = next;
+        }
+        if (__all(done)) break;
+    }
+}
+
 // FIRST ATTEMPT: sweeps guess the active set, primal-dual active-set iterations settle it.  true: lam is the exact
 // optimum (KKT certified); false: `a` is the set the iteration stopped on (a warm start for ug_full).
 template <class Model>
@@ -213,25 +273,7 @@ __device__ __forceinline__ bool ug_try(const UgUni<Model::NC>& U, const UgLds<Mo
 #pragma unroll
     for (int i = 0; i < NC; ++i) a |= (lam[i] > 0.f) ? (1u << i) : 0u;
     bool done = (diag & 32) != 0;
-    for (int it = 0; it < kUgPdas; ++it) {
-        float v[NC], tau[NC];
-        const unsigned ap = ug_lookup_affine<Model>(S, a, du, tolv, v, tau);
-        // rows that are not optimal flip: a multiplier <= 0 leaves the set, a slack < -tol joins it
-        // (the sign bits, shifted in one v_alignbit each: row 0 ends in bit 0.  A multiplier of exactly +0 stays: it
-        // satisfies the KKT conditions as it is)
-        unsigned bad = 0u;
-#pragma unroll
-        for (int i = NC - 1; i >= 0; --i) bad = __builtin_amdgcn_alignbit(bad, __float_as_uint(v[i]), 31);
-        if (!done) {
-            if (bad == 0u) {
-#pragma unroll
-                for (int i = 0; i < NC; ++i) lam[i] = fmaf(-tau[i], v[i], v[i]);      // v on the set, 0 off it
-                done = true;
-            }
-            a = ap ^ bad;
-        }
-        if (__all(done)) break;
-    }
+    ug_pdas<Model, kUgPdas>(S, du, tolv, a, lam, done);
     a_out = a;
     return done;
 }
@@ -698,8 +740,23 @@ __device__ unsigned long long ug_stamps[kUgStampWgs * kUgStampSlots];
                 ug_stamps[wg_ * kUgStampSlots + (slot)] = __builtin_amdgcn_s_memtime();         \
         }                                                                                       \
     } while (0)
+// samples per launch that [0] park, [1] settle in the flush's iterations, [2] enter the dual steps (irs_debug_ug_counts,
+// tests/tools/ug_counts.py):
+// counted per wave in scalars and added once, after the last stamp -- atomics inside the stamped phases stretch the timeline
+__device__ unsigned ug_counts[3];
+#define UG_COUNT_DECL unsigned ug_cnt_[3] = {0u, 0u, 0u}
+#define UG_COUNT(k, pred) ug_cnt_[k] += (unsigned)__popcll(__ballot(pred))
+#define UG_COUNT_FLUSH                                                                          \
+    do {                                                                                        \
+        if ((threadIdx.x & 63) == 0)                                                            \
+            for (int k_ = 0; k_ < 3; ++k_)                                                      \
+                if (ug_cnt_[k_] != 0u) atomicAdd(&ug_counts[k_], ug_cnt_[k_]);                  \
+    } while (0)
 #else
 #define UG_STAMP(slot) do {} while (0)
+#define UG_COUNT_DECL do {} while (0)
+#define UG_COUNT(k, pred) do {} while (0)
+#define UG_COUNT_FLUSH do {} while (0)
 #endif
 
 // The workgroup's prologue: the f32 geometry of the step QP at (x, u) (wave 0), what follows from it (W, r0, J D^-1, C:
@@ -843,6 +900,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
 
     if (nominal_wave && !(a.diag & 2)) ug_nominal<Model, UCOL>(a, U, S, nomL, nom_r, t, lane);
     if (nominal_wave) UG_STAMP(8);
+    UG_COUNT_DECL;
     if (!(a.diag & 8)) {
         // 64-sample blocks are dealt round robin to the waves of the timestep: rounds 0 .. kUgNomRounds - 1 to all but
         // the nominal wave (which is busy with the f64 step for about that long), later rounds to all of them
@@ -886,9 +944,20 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
                 const int slot = (qhead + (on ? lane : 0)) & (kUgRing - 1);
 #pragma unroll
                 for (int j = 0; j < m; ++j) du[j] = ring[slot * QE + j];
-                const unsigned wm = __float_as_uint(ring[slot * QE + m]);
+                unsigned wm = __float_as_uint(ring[slot * QE + m]);
                 const float tolv = ug_rhs<Model>(U, S, du, r);
-                ug_full<Model, UCOL>(S, r, du, tolv, wm, lam, (a.diag & 128) ? 8 : ((a.diag & 256) ? 12 : 4 * NC));
+                // the iteration goes on from the parked set; what it still does not settle takes the dual steps
+                // (a lane past `take` carries lane 0's sample and finishes with it)
+                bool settled = false;
+                if constexpr (kUgPdasFlush > 0) ug_pdas<Model, kUgPdasFlush>(S, du, tolv, wm, lam, settled);
+                UG_COUNT(1, on && settled);
+                UG_COUNT(2, on && !settled);
+                if (!__all(settled)) {
+                    float lf[NC];
+                    ug_full<Model, UCOL>(S, r, du, tolv, wm, lf, (a.diag & 128) ? 8 : ((a.diag & 256) ? 12 : 4 * NC));
+#pragma unroll
+                    for (int i = 0; i < NC; ++i) lam[i] = settled ? lam[i] : lf[i];
+                }
                 qhead += take;
             } else {
                 const int sidx = bk * 64 + lane;
@@ -916,6 +985,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
                 if (a.diag & 16) fin_ = true;
                 const bool hard = on && !fin_;
                 const unsigned long long bal = __ballot(hard);
+                UG_COUNT(0, hard);
                 if (hard) {
                     const int slot = (qtail + __popcll(bal & ((1ull << lane) - 1ull))) & (kUgRing - 1);
 #pragma unroll
@@ -1038,6 +1108,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
     UG_STAMP(4);
     smooth_finish<Model, MODE, FUSE, BLOCK, true, std::remove_cv_t<std::remove_reference_t<decltype(a)>>>(a, red, red64, tot, fin, s_ticket, t, blk, tid, a.fnom + (size_t)t * n);
     UG_STAMP(5);
+    UG_COUNT_FLUSH;
 }
 
 template <class Model, int MODE>
@@ -1064,6 +1135,13 @@ void ug_launch_batch_m(const SmoothArgs& a, const SmoothBatch& bat, int B, hipSt
 extern "C" int irs_debug_ug_stamps(unsigned long long* host_out, int n_wgs) {
     if (n_wgs > kUgStampWgs) n_wgs = kUgStampWgs;
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(ug_stamps), (size_t)n_wgs * kUgStampSlots * sizeof(unsigned long long));
+}
+// the three sample counts since the last reset (reset != 0: zero them after the copy)
+extern "C" int irs_debug_ug_counts(unsigned* host_out3, int reset) {
+    hipError_t e = hipMemcpyFromSymbol(host_out3, HIP_SYMBOL(ug_counts), 3 * sizeof(unsigned));
+    const unsigned zero[3] = {0u, 0u, 0u};
+    if (e == hipSuccess && reset) e = hipMemcpyToSymbol(HIP_SYMBOL(ug_counts), zero, sizeof(zero));
+    return (int)e;
 }
 #endif
 
