@@ -33,21 +33,23 @@
 #include <climits>
 
 #include "boxqp.hpp"
+#include "boxqp_layout.hpp"
 #include "wave.hpp"
 
 namespace {
 
 template <int N, int M>
 struct BoxLayout {
-    // per-timestep factor record
-    static constexpr int oAcl = 0, oK = oAcl + N * N, oMinv = oK + M * N, oHinv = oMinv + M * N,
-                         oB = oHinv + M * M, oC = oB + N * M, oD = oC + N, oQx = oD + N, S = oQx + N;
+    // per-timestep factor record: box_rec_layout (boxqp_layout.hpp) at compile time
+    static constexpr BoxRec rec = box_rec_layout(N, M);
+    static constexpr int oAcl = rec.oAcl, oK = rec.oK, oMinv = rec.oMinv, oHinv = rec.oHinv, oB = rec.oB, oC = rec.oC,
+                         oD = rec.oD, oQx = rec.oQx, S = rec.S;
     static __host__ __device__ size_t doubles(int T) {
         // factor records + qx_T + wx,yx,zx (T+1,N) + wu,yu,zu,k (T,M) + scratch
         return (size_t)T * S + N + 3 * (size_t)(T + 1) * N + 4 * (size_t)T * M + 4 * N * N + 8 * N + 4 * M + 64;
     }
     // records in HBM: stride padded to 16 B; on chip only the 3-slot staging ring stays in place of the records
-    static constexpr int SP = (S + 1) / 2 * 2, RING = 3;
+    static constexpr int SP = rec.SP, RING = kBoxRing;
     static __host__ __device__ size_t hbm_doubles(int T) { return doubles(T) - (size_t)T * S + (size_t)RING * SP; }
     static size_t record_bytes(int T) { return ((size_t)T * SP * sizeof(double) + 255) / 256 * 256; }
 };
@@ -596,16 +598,6 @@ BoxPlan irs_box_plan(int model, int T, int kind, BoxWs ws) {
     return p;
 }
 
-static size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
-// Whether a workspace can hold what plan `p` puts there: `count` slices of round256(p.records) bytes (one per problem
-// of the launch; stride, need: the bytes of one, of all), 256-byte aligned.  The entries word their own errors.
-struct WsFit { size_t stride, need; bool small, misaligned; };
-static WsFit ws_fit(const BoxPlan& p, size_t count, const void* ws, size_t ws_bytes) {
-    const size_t stride = round256(p.records);
-    return {stride, count * stride, ws_bytes < count * stride, (reinterpret_cast<uintptr_t>(ws) & 255) != 0};
-}
-
 // The ADMM kernel on a filled BoxArgs, where the plan puts it: records on chip, or in `ws` -- whenever one is given
 // (policy Always), or only where they do not fit LDS (IfNeeded).  du: the position-controlled form.
 int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, BoxWs policy,
@@ -650,358 +642,7 @@ int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, vo
     return IRS_OK;
 }
 
-// What every entry starts its BoxArgs with: all else null / zero, the model's constants, the horizon, and the strides
-// of the bound rows -- per-time rows (n / m), else one constant row (0).  The entry sets the rest by name.
-static int box_begin(BoxArgs* a, int model, const double* params, int n_params, int T, bool rows) {
-    *a = BoxArgs{};
-    const int rc = irs_load_params(model, params, n_params, &a->p);
-    if (rc != IRS_OK) return rc;
-    int n = 0, m = 0, np;
-    if (rows) irs_model_info(model, &n, &m, &np);
-    a->sx = n; a->su = m; a->sd = m; a->T = T;
-    return IRS_OK;
-}
-
-// a workspace the records must go to (the _wsx entries of the ADMM kernel): 256-byte aligned, large enough
-static int check_box_workspace(const char* fn, int model, int T, int du, const void* ws, size_t ws_bytes) {
-    if (ws == nullptr) return IRS_OK;
-    const BoxPlan p = irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::Always);
-    const WsFit f = ws_fit(p, 1, ws, ws_bytes);
-    if (f.misaligned) {
-        irs_set_error("%s: the workspace must be 256-byte aligned", fn);
-        return IRS_ERR_INVALID_ARG;
-    }
-    if (p.max_T == 0) {
-        irs_set_error("%s: model %d has no %s form", fn, model, du ? "position-controlled" : "plain");
-        return IRS_ERR_UNSUPPORTED;
-    }
-    if (f.small) {
-        irs_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, f.need);
-        return IRS_ERR_WORKSPACE;
-    }
-    return IRS_OK;
-}
-
-// `model` has no active-set form on the tiles: it does not fit them, or it is not position controlled at all
-static int no_tile_form(const char* fn, int model, int T) {
-    irs_set_error(irs_box_plan(model, T, IRS_BOX_ADMM_DU, BoxWs::None).max_T > 0
-                      ? "%s: model %d does not fit the 16 x 16 tile"
-                      : "%s: model %d is not position controlled", fn, model);
-    return IRS_ERR_UNSUPPORTED;
-}
-
-// solver 0 of the quasistatic descent: the tiles where the model fits them and their records have a place, else the
-// lanes where they fit LDS, else ADMM
-static int auto_solver(int model, int T, bool one_box, const void* ws, size_t ws_bytes) {
-    if (!one_box) return 1;
-    const BoxPlan tiles = irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, ws ? BoxWs::IfNeeded : BoxWs::None);
-    if (tiles.place != BoxPlace::None && ws_bytes >= tiles.records) return 3;
-    return irs_box_plan(model, T, IRS_BOX_ACTIVE_SET, BoxWs::None).place == BoxPlace::Lanes ? 2 : 1;
-}
-
-// The checks of an irs_admm_settings (fn: the entry, for the message) and what the launch takes from it: *adapt is
-// left null for adaptive == 0 -- the fixed-rho kernel -- and else points at *ad, filled with the rule's constants.
-static int read_admm_settings(const char* fn, const irs_admm_settings* s, double* adapt_out, BoxAdapt* ad,
-                              const BoxAdapt** adapt) {
-    *adapt = nullptr;
-    if (s == nullptr) {
-        irs_set_error("%s: settings must not be NULL", fn);
-        return IRS_ERR_INVALID_ARG;
-    }
-    if (!irs_admm_settings_ok(s->rho, s->relax, s->max_iter, s->eps)) {
-        irs_set_error("%s: bad ADMM parameter", fn);
-        return IRS_ERR_INVALID_ARG;
-    }
-    if (s->adaptive == 0) return IRS_OK;
-    if (!irs_admm_adapt_ok(s->check_every, s->trigger, s->max_refactor)) {
-        irs_set_error("%s: the adaptive penalty needs check_every > 0, trigger > 1 and max_refactor >= 0", fn);
-        return IRS_ERR_INVALID_ARG;
-    }
-    *ad = BoxAdapt{s->check_every, s->max_refactor, s->trigger, adapt_out};
-    *adapt = ad;
-    return IRS_OK;
-}
-
-// The lazy entries: the kernel's lazy form is compiled on top of the adaptive one, so a fixed penalty (adaptive == 0:
-// *adapt null after read_admm_settings) runs there with a rule that never fires -- max_refactor = 0.
-static void lazy_adapt(double* adapt_out, BoxAdapt* ad, const BoxAdapt** adapt) {
-    if (*adapt != nullptr) return;
-    *ad = BoxAdapt{1, 0, 2.0, adapt_out};
-    *adapt = ad;
-}
-
 extern "C" {
-
-size_t irs_tvlqr_box_lds_bytes(int model, int T) {
-    return T > 0 ? irs_box_plan(model, T, IRS_BOX_ADMM, BoxWs::None).lds : 0;
-}
-
-size_t irs_quasistatic_box_lds_bytes(int model, int T, int solver) {
-    const int kind = solver == 2 ? IRS_BOX_ACTIVE_SET : solver == 3 ? IRS_BOX_ACTIVE_SET_MFMA : IRS_BOX_ADMM_DU;
-    return T > 0 ? irs_box_plan(model, T, kind, BoxWs::None).lds : 0;
-}
-
-size_t irs_tvlqr_box_workspace_bytes(int model, int T, int du) {
-    return T > 0 ? irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::IfNeeded).records : 0;
-}
-
-size_t irs_tvlqr_box_hbm_lds_bytes(int model, int T, int du) {
-    return T > 0 ? irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::Always).lds : 0;
-}
-
-size_t irs_box_records_bytes(int model, int T, int kind) {
-    return T > 0 ? irs_box_plan(model, T, kind, BoxWs::Always).records : 0;
-}
-
-size_t irs_quasistatic_descent_workspace_bytes(int model, int T, int solver) {
-    if (T <= 0 || solver < 0 || solver > 3 || solver == 2) return 0;
-    const size_t tiles = solver != 1 ? irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, BoxWs::IfNeeded).records : 0;
-    const size_t admm = solver != 3 ? irs_box_plan(model, T, IRS_BOX_ADMM_DU, BoxWs::IfNeeded).records : 0;
-    return tiles > admm ? tiles : admm;
-}
-
-int irs_box_horizon_limit(int model, int kind) {
-    return kind >= IRS_BOX_ADMM && kind <= IRS_BOX_ACTIVE_SET_MFMA ? irs_box_plan(model, 1, kind, BoxWs::IfNeeded).max_T
-                                                                   : 0;
-}
-
-int irs_tvlqr_box_descent(int model, const double* params, int n_params, int T, const double* At,
-                          const double* Bt, const double* ct, const double* Q, const double* Qd,
-                          const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                          const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                          double rho, double relax, int max_iter, double eps, double* x_new,
-                          double* u_new, int* info, void* stream) {
-    return irs_tvlqr_box_descent_if(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, xlo, xhi, ulo,
-                                    uhi, rho, relax, max_iter, eps, x_new, u_new, nullptr, info, nullptr, stream);
-}
-
-int irs_tvlqr_box_descent_if(int model, const double* params, int n_params, int T, const double* At,
-                             const double* Bt, const double* ct, const double* Q, const double* Qd,
-                             const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                             const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                             double rho, double relax, int max_iter, double eps, double* x_new,
-                             double* u_new, double* cost, int* info, const int* run_flag, void* stream) {
-    // (both messages keep the name of the internal function that used to make these checks: an entry's error text
-    // does not change)
-    if (!(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi && x_new && u_new &&
-          info)) {
-        irs_set_error("irs_tvlqr_box_descent_ifw: bad argument");
-        return IRS_ERR_INVALID_ARG;
-    }
-    if (!irs_admm_settings_ok(rho, relax, max_iter, eps)) {
-        irs_set_error("irs_tvlqr_box_descent_ifw: bad ADMM parameter");
-        return IRS_ERR_INVALID_ARG;
-    }
-    BoxArgs a;
-    const int rc = box_begin(&a, model, params, n_params, T, false);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi;
-    a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.max_iter = max_iter; a.eps = eps;
-    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info; a.run_flag = run_flag;
-    return irs_box_admm_launch("irs_tvlqr_box_descent", model, false, a, nullptr, 0, BoxWs::None,
-                               static_cast<hipStream_t>(stream));
-}
-
-int irs_tvlqr_box_descent_wsx(int model, const double* params, int n_params, int T, const double* At,
-                              const double* Bt, const double* ct, const double* Q, const double* Qd,
-                              const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                              double rho, double relax, int max_iter, double eps, double* x_new,
-                              double* u_new, int* info, void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
-                  x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(irs_admm_settings_ok(rho, relax, max_iter, eps), "bad ADMM parameter");
-    int rc = check_box_workspace(__func__, model, T, 0, workspace, workspace_bytes);
-    if (rc != IRS_OK) return rc;
-    BoxArgs a;
-    rc = box_begin(&a, model, params, n_params, T, false);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi;
-    a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.max_iter = max_iter; a.eps = eps;
-    a.x_new = x_new; a.u_new = u_new; a.info = info;
-    return irs_box_admm_launch("irs_tvlqr_box_descent", model, false, a, workspace, workspace_bytes, BoxWs::Always,
-                               static_cast<hipStream_t>(stream));
-}
-
-int irs_tvlqr_box_descent_set(int model, const double* params, int n_params, int T, const double* At,
-                              const double* Bt, const double* ct, const double* Q, const double* Qd,
-                              const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                              const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                              const irs_admm_settings* settings, double* x_new, double* u_new, int* info,
-                              double* adapt_out, void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
-                  x_new && u_new && info, "bad argument");
-    BoxAdapt ad;
-    const BoxAdapt* adapt;
-    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
-    if (rc != IRS_OK) return rc;
-    rc = check_box_workspace(__func__, model, T, 0, workspace, workspace_bytes);
-    if (rc != IRS_OK) return rc;
-    BoxArgs a;
-    rc = box_begin(&a, model, params, n_params, T, false);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi;
-    a.alpha = alpha_R; a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter;
-    a.eps = settings->eps;
-    a.x_new = x_new; a.u_new = u_new; a.info = info;
-    return irs_box_admm_launch("irs_tvlqr_box_descent", model, false, a, workspace, workspace_bytes, BoxWs::Always,
-                               static_cast<hipStream_t>(stream), adapt);
-}
-
-int irs_quasistatic_box_descent(int model, const double* params, int n_params, int T, const double* At,
-                                const double* Bt, const double* ct, const double* Q, const double* Qd,
-                                const double* R, const double* xd_trj, const double* x0,
-                                const double* x_lo, const double* x_hi, const double* u_lo,
-                                const double* u_hi, const double* du_lo, const double* du_hi,
-                                int solver, double rho, double relax, int max_iter, double eps,
-                                double* x_new, double* u_new, double* cost, int* info, void* stream) {
-    return irs_quasistatic_box_descent_ws(model, params, n_params, T, At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo, x_hi,
-                                          u_lo, u_hi, du_lo, du_hi, solver, rho, relax, max_iter, eps, x_new,
-                                          u_new, cost, info, nullptr, stream);
-}
-
-int irs_quasistatic_box_descent_ws(int model, const double* params, int n_params, int T, const double* At,
-                                   const double* Bt, const double* ct, const double* Q, const double* Qd,
-                                   const double* R, const double* xd_trj, const double* x0,
-                                   const double* x_lo, const double* x_hi, const double* u_lo,
-                                   const double* u_hi, const double* du_lo, const double* du_hi,
-                                   int solver, double rho, double relax, int max_iter, double eps,
-                                   double* x_new, double* u_new, double* cost, int* info, double* act_io,
-                                   void* stream) {
-    return irs_quasistatic_box_descent_wsx(model, params, n_params, T, At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo, x_hi,
-                                           u_lo, u_hi, du_lo, du_hi, solver, rho, relax, max_iter, eps, x_new,
-                                           u_new, cost, info, act_io, nullptr, 0, stream);
-}
-
-int irs_quasistatic_box_descent_wsx(int model, const double* params, int n_params, int T, const double* At,
-                                    const double* Bt, const double* ct, const double* Q, const double* Qd,
-                                    const double* R, const double* xd_trj, const double* x0,
-                                    const double* x_lo, const double* x_hi, const double* u_lo,
-                                    const double* u_hi, const double* du_lo, const double* du_hi,
-                                    int solver, double rho, double relax, int max_iter, double eps,
-                                    double* x_new, double* u_new, double* cost, int* info, double* act_io,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(solver >= 0 && solver <= 3,
-                  "solver must be 0 (auto), 1 (ADMM), 2 (active set, lanes) or 3 (active set, matrix-core tiles)");
-    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
-                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
-    IRS_CHECK_ARG(irs_admm_settings_ok(rho, relax, max_iter, eps), "bad ADMM parameter");
-    BoxArgs a;
-    int rc = box_begin(&a, model, params, n_params, T, true);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.alpha = 1.0;      // tv_lqr.py:107 adds du'R du as an expression: the full quadratic
-    a.rho = rho; a.relax = relax; a.max_iter = max_iter; a.eps = eps;
-    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info; a.act_io = act_io;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // one control box (or none) and no state bounds: the exact active-set solvers apply
-    const bool one_box = x_lo == nullptr && !(u_lo != nullptr && du_lo != nullptr);
-    if ((solver == 2 || solver == 3) && !one_box) {
-        irs_set_error("irs_quasistatic_box_descent: the active-set solvers handle ONE of u / du bounds and no x bounds");
-        return IRS_ERR_UNSUPPORTED;
-    }
-    if (solver == 0) solver = auto_solver(model, T, one_box, workspace, workspace_bytes);
-    if (solver == 1)    // records in the workspace only when they do not fit LDS
-        return irs_box_admm_launch("irs_quasistatic_box_descent", model, true, a, workspace, workspace_bytes,
-                                   BoxWs::IfNeeded, st);
-    const BoxPlan p = irs_box_plan(model, T, solver == 3 ? IRS_BOX_ACTIVE_SET_MFMA : IRS_BOX_ACTIVE_SET,
-                                   workspace != nullptr ? BoxWs::IfNeeded : BoxWs::None);
-    if (p.max_T == 0) return no_tile_form("irs_quasistatic_box_descent", model, T);
-    if (p.place == BoxPlace::None || workspace_bytes < p.records) {
-        if (solver == 3)
-            irs_set_error("irs_quasistatic_box_descent: horizon T=%d needs a %zu-byte workspace for the matrix-core "
-                          "active-set solver (records do not fit LDS)", T, p.records);
-        else
-            irs_set_error("irs_quasistatic_box_descent: horizon T=%d needs %zu bytes of LDS (max ~160 KB)", T, p.lds);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    const int kind = du_lo != nullptr ? 1 : 0;
-    rc = solver == 3 ? irs_ctrlbox_mfma_launch(model, a, kind, p, static_cast<double*>(workspace), st)
-                     : irs_ctrlbox_launch(model, a, kind, p, st);
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-// the ADMM form (solver 1) alone, with its settings in a struct: the adaptive penalty is the ADMM kernel's
-int irs_quasistatic_box_descent_set(int model, const double* params, int n_params, int T, const double* At,
-                                    const double* Bt, const double* ct, const double* Q, const double* Qd,
-                                    const double* R, const double* xd_trj, const double* x0,
-                                    const double* x_lo, const double* x_hi, const double* u_lo,
-                                    const double* u_hi, const double* du_lo, const double* du_hi,
-                                    int solver, const irs_admm_settings* settings, double* x_new, double* u_new,
-                                    double* cost, int* info, double* adapt_out, void* workspace,
-                                    size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(solver == 1, "solver must be 1 (ADMM): the settings are the ADMM kernel's");
-    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
-                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
-    BoxAdapt ad;
-    const BoxAdapt* adapt;
-    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
-    if (rc != IRS_OK) return rc;
-    BoxArgs a;
-    rc = box_begin(&a, model, params, n_params, T, true);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.alpha = 1.0;      // tv_lqr.py:107, as irs_quasistatic_box_descent_wsx
-    a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter; a.eps = settings->eps;
-    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info;
-    return irs_box_admm_launch("irs_quasistatic_box_descent", model, true, a, workspace, workspace_bytes,
-                               BoxWs::IfNeeded, static_cast<hipStream_t>(stream), adapt);
-}
-
-// ---- B problems per launch (solver 3's method) ---------------------------------------------------------------------
-size_t irs_quasistatic_descent_batch_workspace_bytes(int model, int T, int B) {
-    if (T <= 0 || B <= 0) return 0;
-    return (size_t)B * round256(irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, BoxWs::IfNeeded).records);
-}
-
-int irs_quasistatic_box_descent_batch(int model, const double* params, int n_params, int T, int B, const double* At,
-                                      const double* Bt, const double* ct, const double* Q, const double* Qd,
-                                      const double* R, const double* xd_trj, const double* x0, const double* u_lo,
-                                      const double* u_hi, const double* du_lo, const double* du_hi, int max_iter,
-                                      double eps, double* x_new, double* u_new, double* cost, int* info, double* act_io,
-                                      void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && B > 0, "T and B must be positive");
-    IRS_CHECK_ARG(At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG((u_lo == nullptr) == (u_hi == nullptr) && (du_lo == nullptr) == (du_hi == nullptr),
-                  "give both sides of a bound or neither");
-    IRS_CHECK_ARG((u_lo != nullptr) != (du_lo != nullptr), "give exactly one of the u / du bound pairs");
-    IRS_CHECK_ARG(max_iter > 0 && eps > 0.0, "bad solver parameter");
-    BoxArgs a;
-    int rc = box_begin(&a, model, params, n_params, T, true);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.alpha = 1.0; a.rho = 10.0; a.relax = 1.6; a.max_iter = max_iter; a.eps = eps;
-    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info; a.act_io = act_io;
-    // a workspace puts the records there at any horizon (as irs_tvlqr_box_descent_wsx does); without one they must
-    // fit LDS
-    const BoxPlan p = irs_box_plan(model, T, IRS_BOX_ACTIVE_SET_MFMA, workspace != nullptr ? BoxWs::Always : BoxWs::None);
-    if (p.max_T == 0) return no_tile_form("irs_quasistatic_box_descent_batch", model, T);
-    const WsFit f = ws_fit(p, (size_t)B, workspace, workspace_bytes);
-    if (p.place == BoxPlace::None || f.small) {
-        irs_set_error("irs_quasistatic_box_descent_batch: horizon T=%d, B=%d needs a workspace of %zu bytes (given: %zu)",
-                      T, B, f.need, workspace_bytes);
-        return IRS_ERR_WORKSPACE;
-    }
-    if (p.place == BoxPlace::TilesHbm && f.misaligned) {
-        irs_set_error("irs_quasistatic_box_descent_batch: the workspace must be 256-byte aligned");
-        return IRS_ERR_INVALID_ARG;
-    }
-    rc = irs_ctrlbox_mfma_launch(model, a, du_lo != nullptr ? 1 : 0, p, static_cast<double*>(workspace),
-                                 static_cast<hipStream_t>(stream), B, f.stride);
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
 
 int irs_quasistatic_bound_rows_batch(int n, int m, int T, int B, const double* x_trj, const int* indices_u_into_x,
                                      const double* offsets, int per_time, int rel, double* lo, double* hi,
@@ -1015,163 +656,6 @@ int irs_quasistatic_bound_rows_batch(int n, int m, int T, int B, const double* x
                        rel != 0, lo, hi);
     IRS_CHECK_LAUNCH();
     return IRS_OK;
-}
-
-int irs_tvlqr_box_solve(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                        const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                        const double* xd_trj, const double* x0, int position_controlled,
-                        const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
-                        const double* du_lo, const double* du_hi, double rho, double relax, int max_iter,
-                        double eps, double* x_star, double* u_star, int* info, void* stream) {
-    return irs_tvlqr_box_solve_wsx(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0,
-                                   position_controlled, x_lo, x_hi, u_lo, u_hi, du_lo, du_hi, rho, relax, max_iter, eps,
-                                   x_star, u_star, info, nullptr, 0, stream);
-}
-
-// solve_tvlqr (irs_lqr/tv_lqr.py:30-145) stand-alone: ONE bounded QP, its plan returned.
-int irs_tvlqr_box_solve_wsx(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                            const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                            const double* xd_trj, const double* x0, int position_controlled,
-                            const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
-                            const double* du_lo, const double* du_hi, double rho, double relax, int max_iter,
-                            double eps, double* x_star, double* u_star, int* info, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_star && u_star && info, "bad argument");
-    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
-                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
-    IRS_CHECK_ARG(position_controlled || du_lo == nullptr, "du bounds need the position-controlled form");
-    IRS_CHECK_ARG(irs_admm_settings_ok(rho, relax, max_iter, eps), "bad ADMM parameter");
-    int rc = check_box_workspace(__func__, model, T, position_controlled ? 1 : 0, workspace, workspace_bytes);
-    if (rc != IRS_OK) return rc;
-    BoxArgs a;
-    rc = box_begin(&a, model, params, n_params, T, true);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.alpha = alpha_R; a.rho = rho; a.relax = relax; a.max_iter = max_iter; a.eps = eps;
-    a.x_new = x_star; a.u_new = u_star; a.info = info; a.single_tail = 1;
-    return irs_box_admm_launch("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes,
-                               BoxWs::Always, static_cast<hipStream_t>(stream));
-}
-
-int irs_tvlqr_box_solve_set(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                            const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                            const double* xd_trj, const double* x0, int position_controlled,
-                            const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
-                            const double* du_lo, const double* du_hi, const irs_admm_settings* settings,
-                            double* x_star, double* u_star, int* info, double* adapt_out, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_star && u_star && info, "bad argument");
-    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
-                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
-    IRS_CHECK_ARG(position_controlled || du_lo == nullptr, "du bounds need the position-controlled form");
-    BoxAdapt ad;
-    const BoxAdapt* adapt;
-    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
-    if (rc != IRS_OK) return rc;
-    rc = check_box_workspace(__func__, model, T, position_controlled ? 1 : 0, workspace, workspace_bytes);
-    if (rc != IRS_OK) return rc;
-    BoxArgs a;
-    rc = box_begin(&a, model, params, n_params, T, true);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.alpha = alpha_R; a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter;
-    a.eps = settings->eps;
-    a.x_new = x_star; a.u_new = u_star; a.info = info; a.single_tail = 1;
-    return irs_box_admm_launch("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes,
-                               BoxWs::Always, static_cast<hipStream_t>(stream), adapt);
-}
-
-// ---- lazily enforced bounds: the _set entries plus the set and its counters ------------------------------------------
-int irs_tvlqr_box_descent_lazy(int model, const double* params, int n_params, int T, const double* At,
-                               const double* Bt, const double* ct, const double* Q, const double* Qd,
-                               const double* R, double alpha_R, const double* xd_trj, const double* x0,
-                               const double* xlo, const double* xhi, const double* ulo, const double* uhi,
-                               const irs_admm_settings* settings, double* x_new, double* u_new, int* info,
-                               double* adapt_out, void* workspace, size_t workspace_bytes, int* enforced_io,
-                               double* lazy_out, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && xlo && xhi && ulo && uhi &&
-                  x_new && u_new && info, "bad argument");
-    BoxAdapt ad;
-    const BoxAdapt* adapt;
-    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
-    if (rc != IRS_OK) return rc;
-    rc = check_box_workspace(__func__, model, T, 0, workspace, workspace_bytes);
-    if (rc != IRS_OK) return rc;
-    BoxArgs a;
-    rc = box_begin(&a, model, params, n_params, T, false);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = xlo; a.xhi = xhi; a.ulo = ulo; a.uhi = uhi;
-    a.alpha = alpha_R; a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter;
-    a.eps = settings->eps;
-    a.x_new = x_new; a.u_new = u_new; a.info = info;
-    lazy_adapt(adapt_out, &ad, &adapt);
-    const BoxLazy lazy{enforced_io, lazy_out};
-    return irs_box_admm_launch("irs_tvlqr_box_descent", model, false, a, workspace, workspace_bytes, BoxWs::Always,
-                               static_cast<hipStream_t>(stream), adapt, &lazy);
-}
-
-int irs_tvlqr_box_solve_lazy(int model, const double* params, int n_params, int T, const double* At, const double* Bt,
-                             const double* ct, const double* Q, const double* Qd, const double* R, double alpha_R,
-                             const double* xd_trj, const double* x0, int position_controlled,
-                             const double* x_lo, const double* x_hi, const double* u_lo, const double* u_hi,
-                             const double* du_lo, const double* du_hi, const irs_admm_settings* settings,
-                             double* x_star, double* u_star, int* info, double* adapt_out, void* workspace,
-                             size_t workspace_bytes, int* enforced_io, double* lazy_out, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_star && u_star && info, "bad argument");
-    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
-                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
-    IRS_CHECK_ARG(position_controlled || du_lo == nullptr, "du bounds need the position-controlled form");
-    BoxAdapt ad;
-    const BoxAdapt* adapt;
-    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
-    if (rc != IRS_OK) return rc;
-    rc = check_box_workspace(__func__, model, T, position_controlled ? 1 : 0, workspace, workspace_bytes);
-    if (rc != IRS_OK) return rc;
-    BoxArgs a;
-    rc = box_begin(&a, model, params, n_params, T, true);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.alpha = alpha_R; a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter;
-    a.eps = settings->eps;
-    a.x_new = x_star; a.u_new = u_star; a.info = info; a.single_tail = 1;
-    lazy_adapt(adapt_out, &ad, &adapt);
-    const BoxLazy lazy{enforced_io, lazy_out};
-    return irs_box_admm_launch("irs_tvlqr_box_solve", model, position_controlled != 0, a, workspace, workspace_bytes,
-                               BoxWs::Always, static_cast<hipStream_t>(stream), adapt, &lazy);
-}
-
-int irs_quasistatic_box_descent_lazy(int model, const double* params, int n_params, int T, const double* At,
-                                     const double* Bt, const double* ct, const double* Q, const double* Qd,
-                                     const double* R, const double* xd_trj, const double* x0,
-                                     const double* x_lo, const double* x_hi, const double* u_lo,
-                                     const double* u_hi, const double* du_lo, const double* du_hi,
-                                     int solver, const irs_admm_settings* settings, double* x_new, double* u_new,
-                                     double* cost, int* info, double* adapt_out, void* workspace,
-                                     size_t workspace_bytes, int* enforced_io, double* lazy_out, void* stream) {
-    IRS_CHECK_ARG(T > 0 && At && Bt && ct && Q && Qd && R && xd_trj && x0 && x_new && u_new && info, "bad argument");
-    IRS_CHECK_ARG(solver == 1, "solver must be 1 (ADMM): the lazily enforced bounds are the ADMM kernel's");
-    IRS_CHECK_ARG((x_lo == nullptr) == (x_hi == nullptr) && (u_lo == nullptr) == (u_hi == nullptr) &&
-                  (du_lo == nullptr) == (du_hi == nullptr), "give both sides of a bound or neither");
-    BoxAdapt ad;
-    const BoxAdapt* adapt;
-    int rc = read_admm_settings(__func__, settings, adapt_out, &ad, &adapt);
-    if (rc != IRS_OK) return rc;
-    BoxArgs a;
-    rc = box_begin(&a, model, params, n_params, T, true);
-    if (rc != IRS_OK) return rc;
-    a.At = At; a.Bt = Bt; a.ct = ct; a.Q = Q; a.Qd = Qd; a.R = R; a.xd = xd_trj; a.x0 = x0;
-    a.xlo = x_lo; a.xhi = x_hi; a.ulo = u_lo; a.uhi = u_hi; a.dlo = du_lo; a.dhi = du_hi;
-    a.alpha = 1.0;      // tv_lqr.py:107, as irs_quasistatic_box_descent_wsx
-    a.rho = settings->rho; a.relax = settings->relax; a.max_iter = settings->max_iter; a.eps = settings->eps;
-    a.x_new = x_new; a.u_new = u_new; a.cost = cost; a.info = info;
-    lazy_adapt(adapt_out, &ad, &adapt);
-    const BoxLazy lazy{enforced_io, lazy_out};
-    return irs_box_admm_launch("irs_quasistatic_box_descent", model, true, a, workspace, workspace_bytes,
-                               BoxWs::IfNeeded, static_cast<hipStream_t>(stream), adapt, &lazy);
 }
 
 }  // extern "C"

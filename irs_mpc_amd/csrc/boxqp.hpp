@@ -50,6 +50,14 @@ struct BoxPlan {
 };
 // boxqp.hip: the one placement decision of every bounded descent and size query.  kind: IRS_BOX_*.  No HIP calls.
 BoxPlan irs_box_plan(int model, int T, int kind, BoxWs ws);
+inline size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
+// Whether a workspace can hold what plan `p` puts there: `count` slices of round256(p.records) bytes (one per problem
+// of the launch; stride, need: the bytes of one, of all), 256-byte aligned.  The entries word their own errors.
+struct WsFit { size_t stride, need; bool small, misaligned; };
+inline WsFit ws_fit(const BoxPlan& p, size_t count, const void* ws, size_t ws_bytes) {
+    const size_t stride = round256(p.records);
+    return {stride, count * stride, ws_bytes < count * stride, (reinterpret_cast<uintptr_t>(ws) & 255) != 0};
+}
 inline bool irs_admm_settings_ok(double rho, double relax, int max_iter, double eps) {
     return rho > 0.0 && relax > 0.0 && relax < 2.0 && max_iter > 0 && eps > 0.0;
 }

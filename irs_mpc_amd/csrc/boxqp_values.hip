@@ -7,8 +7,8 @@
 // launches on the same stream.  The launch boundary is the hand-off: nothing waits on the host or on another stream.
 //
 //   box_values_begin_kernel   one wave, once per descent: the backward factorisation of the whole horizon.  Writes to
-//     the workspace one record per step (Acl, K, Minv, Hinv, B, c, d, qx: BoxLayout's content, offsets by runtime
-//     (n, m)), the masks (over the rows 1..T of x and 0..T-1 of u), Qd xd_T, zeroed warm-start vectors, and -- last --
+//     the workspace one record per step (Acl, K, Minv, Hinv, B, c, d, qx: box_rec_layout of the runtime
+//     (n, m), boxqp.hip's own record), the masks (over the rows 1..T of x and 0..T-1 of u), Qd xd_T, zeroed warm-start vectors, and -- last --
 //     the header (begun mark, n, m, T, rho, relax).  info = [t+1 of a non-PD Hessian, 0, 0].
 //   box_values_tail_kernel<RC>   one wave, once per tail t: the tail QP t..T from the realised state x_t, warm started
 //     from the workspace.  Its ADMM vectors are in LDS while it runs; the records are staged from HBM through a 3-slot
@@ -20,13 +20,13 @@
 //
 // What the workspace keeps between tails is the warm start (w, y): z and k are recomputed from x_t by the first
 // iteration of every tail, so they stay in LDS.  One block owns the workspace: plain stores, no atomics.
+#include "boxqp_layout.hpp"
 #include "irs_common.hpp"
 #include "wave.hpp"
 
 namespace {
 
 constexpr int kMaxN = 32, kMaxM = 16;       // the limits of irs_tvlqr_riccati and the values pass
-constexpr int kRing = 3;
 constexpr int kHdr = 8;                     // header doubles: begun, n, m, T, rho, relax, 0, 0
 constexpr double kBegun = 4952534258564131.0;
 constexpr double INF = __builtin_huge_val();
@@ -34,18 +34,6 @@ constexpr double INF = __builtin_huge_val();
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) v2d gv2d;          // global, not flat: see boxqp.hip
 typedef __attribute__((address_space(1))) double gdbl;
-
-// per-step factor record for runtime (n, m): BoxLayout<N, M>'s fields in its order
-struct Rec {
-    int oAcl, oK, oMinv, oHinv, oB, oC, oD, oQx, S, SP;
-};
-__host__ __device__ inline Rec rec_layout(int n, int m) {
-    Rec r;
-    r.oAcl = 0; r.oK = n * n; r.oMinv = r.oK + m * n; r.oHinv = r.oMinv + m * n; r.oB = r.oHinv + m * m;
-    r.oC = r.oB + n * m; r.oD = r.oC + n; r.oQx = r.oD + n; r.S = r.oQx + n;
-    r.SP = (r.S + 1) / 2 * 2;               // stride padded to 16 B
-    return r;
-}
 
 // the workspace, in doubles: header | mx (32) | mu (16) | Qd xd_T (32) | wx, yx (T+1,n), wu, yu (T,m) | T records
 struct Ws {
@@ -56,13 +44,13 @@ __host__ __device__ inline Ws ws_layout(int n, int m, int T) {
     w.oMx = kHdr; w.oMu = w.oMx + kMaxN; w.oQxT = w.oMu + kMaxM; w.oWx = w.oQxT + kMaxN;
     w.oYx = w.oWx + (size_t)(T + 1) * n; w.oWu = w.oYx + (size_t)(T + 1) * n; w.oYu = w.oWu + (size_t)T * m;
     w.oRec = (w.oYu + (size_t)T * m + 1) / 2 * 2;
-    w.total = w.oRec + (size_t)T * rec_layout(n, m).SP;
+    w.total = w.oRec + (size_t)T * box_rec_layout(n, m).SP;
     return w;
 }
 
 // LDS doubles of a tail launch: the ring | qxT, p, g, mx (n each) | s, mu (m each) | wx, yx, zx (T+1,n) | wu, yu, zu, k
 __host__ __device__ inline size_t tail_lds_doubles(int n, int m, int T) {
-    return (size_t)kRing * rec_layout(n, m).SP + 4 * n + 2 * m + 3 * (size_t)(T + 1) * n + 4 * (size_t)T * m;
+    return (size_t)kBoxRing * box_rec_layout(n, m).SP + 4 * n + 2 * m + 3 * (size_t)(T + 1) * n + 4 * (size_t)T * m;
 }
 
 // The one planner: what the size queries answer and what the launch path reads.  No HIP calls.
@@ -73,7 +61,7 @@ struct ValuesBoxPlan {
     int max_T;          // the longest horizon whose ADMM vectors fit LDS beside the ring
 };
 ValuesBoxPlan values_box_plan(int n, int m, int T) {
-    const Rec r = rec_layout(n, m);
+    const BoxRec r = box_rec_layout(n, m);
     const size_t budget = IRS_LDS_BUDGET / sizeof(double), base = tail_lds_doubles(n, m, 0);
     ValuesBoxPlan p;
     p.rc = (r.SP / 2 + 63) / 64;
@@ -99,7 +87,7 @@ __global__ __launch_bounds__(64) void box_values_begin_kernel(BeginArgs a) {
     __shared__ double Hs[kMaxM * kMaxM], Lm[kMaxM * kMaxM], Yw[kMaxM * kMaxM], Dg[kMaxM], Di[kMaxM];
     __shared__ double mxv[kMaxN], muv[kMaxM];
     const int n = a.n, m = a.m, T = a.T, lane = threadIdx.x;
-    const Rec L = rec_layout(n, m);
+    const BoxRec L = box_rec_layout(n, m);
     const Ws W = ws_layout(n, m, T);
     gdbl* ws = (gdbl*)a.ws;
     if (lane == 0) ws[0] = 0.0;                       // not begun until the header is written, last
@@ -288,7 +276,7 @@ __global__ __launch_bounds__(64) void box_values_tail_kernel(TailArgs a) {
         return;
     }
     const double rho = hdr[4], al = hdr[5], hr = 0.5 * rho;
-    const Rec L = rec_layout(n, m);
+    const BoxRec L = box_rec_layout(n, m);
     const Ws W = ws_layout(n, m, T);
     gdbl* ws = (gdbl*)a.ws;
     auto zlo_ = [&](int t, int i) -> double { return a.xlo ? a.xlo[(size_t)t * a.sx + i] : -INF; };
@@ -297,7 +285,7 @@ __global__ __launch_bounds__(64) void box_values_tail_kernel(TailArgs a) {
     auto vhi_ = [&](int t, int j) -> double { return a.uhi ? a.uhi[(size_t)t * a.su + j] : INF; };
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* F = lds;                                   // the ring: 3 x L.SP
-    double* qxT = F + (size_t)kRing * L.SP;
+    double* qxT = F + (size_t)kBoxRing * L.SP;
     double* pv = qxT + n;
     double* gv = pv + n;
     double* mxv = gv + n;
@@ -332,7 +320,7 @@ __global__ __launch_bounds__(64) void box_values_tail_kernel(TailArgs a) {
             if (r * 64 + lane < NC) st.v[r] = src[r * 64 + lane];
     };
     auto put = [&](int t, const Stage& st) {
-        v2d* dst = reinterpret_cast<v2d*>(F + (size_t)(t % kRing) * L.SP);
+        v2d* dst = reinterpret_cast<v2d*>(F + (size_t)(t % kBoxRing) * L.SP);
 #pragma unroll
         for (int r = 0; r < RC; ++r)
             if (r * 64 + lane < NC) dst[r * 64 + lane] = st.v[r];
@@ -353,7 +341,7 @@ __global__ __launch_bounds__(64) void box_values_tail_kernel(TailArgs a) {
         if (lane < n) pv[lane] = -(qxT[lane] + hr * mxv[lane] * (wx[(size_t)T * n + lane] - yx[(size_t)T * n + lane]));
         wave_sync();
         auto bw_step = [&](int t, auto hook) {
-            const double* rec = F + (size_t)(t % kRing) * L.SP;
+            const double* rec = F + (size_t)(t % kBoxRing) * L.SP;
             if (lane < n) gv[lane] = rec[L.oD + lane] + pv[lane];
             else if (lane < n + m) {
                 const int j = lane - n;
@@ -381,7 +369,7 @@ __global__ __launch_bounds__(64) void box_values_tail_kernel(TailArgs a) {
         };
         // forward sweep on the linear model: u = K x + k, x+ = Acl x + B k + c
         auto fw_step = [&](int t, auto hook) {
-            const double* rec = F + (size_t)(t % kRing) * L.SP;
+            const double* rec = F + (size_t)(t % kBoxRing) * L.SP;
             const double* xt = zx + (size_t)t * n;
             if (lane < n) {
                 double s = rec[L.oC + lane];

@@ -283,6 +283,28 @@ class DeviceModel:
                 raise ValueError("enforced must have %d entries, not %s" % (count, tuple(o["enforced"].shape)))
         o["lazy"] = torch.empty((3,), dtype=F64, device=device)
 
+    def _box_admm_call(self, family, prefix, outs, ws, o, rho, relax, max_iter, eps, adaptive_rho, lazy_bounds, enforced,
+                       components, wsx_extra=()):
+        """One bounded-ADMM launch of `family` (a C entry's name without its suffix).  prefix: the entry's arguments
+        from T to its bounds (and solver); outs: its output pointers.  Picks the entry -- _wsx for the fixed penalty,
+        _set for adaptive_rho, _lazy for lazy_bounds (`components` entries in its set) -- appends that entry's tail,
+        and adds to `o` what the entry writes besides `outs`."""
+        dev = o["info"].device
+        if lazy_bounds or adaptive_rho:
+            if "adapt" not in o:
+                o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
+            if lazy_bounds:
+                self._lazy_outputs(o, enforced, components, dev)
+            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=bool(adaptive_rho))
+            name, tail = family + "_set", [ctypes.byref(st), *outs, _ptr(o["adapt"], F64), *_ws_args(ws)]
+            if lazy_bounds:
+                name, tail = family + "_lazy", tail + [o["enforced"].data_ptr(), _ptr(o["lazy"], F64)]
+        else:
+            name = family + "_wsx"
+            tail = [float(rho), float(relax), int(max_iter), float(eps), *outs, *wsx_extra, *_ws_args(ws)]
+        check(getattr(self.lib, name)(self.model_id, self._p, self._np, *prefix, *tail, _stream()), name)
+        return o
+
     def tvlqr_box_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, xlo, xhi, ulo, uhi, alpha_R=0.5,
                           rho=10.0, relax=1.6, max_iter=5000, eps=1e-8, records_in_hbm=False, adaptive_rho=False,
                           lazy_bounds=False, enforced=None):
@@ -303,38 +325,11 @@ class DeviceModel:
                  u_new=torch.empty((T, self.m), dtype=F64, device=dev),
                  info=torch.empty((3,), dtype=torch.int32, device=dev))
         ws = self._box_workspace(T, False, dev, force=records_in_hbm)
-        if lazy_bounds:
-            o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
-            self._lazy_outputs(o, enforced, self.n + self.m, dev)
-            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=bool(adaptive_rho))
-            check(self.lib.irs_tvlqr_box_descent_lazy(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
-                                                      _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
-                                                      float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(xlo, F64),
-                                                      _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64), ctypes.byref(st),
-                                                      _ptr(o["x_new"], F64), _ptr(o["u_new"], F64), o["info"].data_ptr(),
-                                                      _ptr(o["adapt"], F64), *_ws_args(ws), o["enforced"].data_ptr(),
-                                                      _ptr(o["lazy"], F64), _stream()),
-                  "irs_tvlqr_box_descent_lazy")
-            return o
-        if adaptive_rho:
-            o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
-            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=True)
-            check(self.lib.irs_tvlqr_box_descent_set(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
-                                                     _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
-                                                     float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(xlo, F64),
-                                                     _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64), ctypes.byref(st),
-                                                     _ptr(o["x_new"], F64), _ptr(o["u_new"], F64), o["info"].data_ptr(),
-                                                     _ptr(o["adapt"], F64), *_ws_args(ws), _stream()),
-                  "irs_tvlqr_box_descent_set")
-            return o
-        check(self.lib.irs_tvlqr_box_descent_wsx(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
-                                                 _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
-                                                 float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(xlo, F64),
-                                                 _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64), float(rho),
-                                                 float(relax), int(max_iter), float(eps), _ptr(o["x_new"], F64),
-                                                 _ptr(o["u_new"], F64), o["info"].data_ptr(), *_ws_args(ws), _stream()),
-              "irs_tvlqr_box_descent_wsx")
-        return o
+        prefix = [T, *(_ptr(a, F64) for a in (At, Bt, ct, Q, Qd, R)), float(alpha_R),
+                  *(_ptr(a, F64) for a in (xd_trj, x0, xlo, xhi, ulo, uhi))]
+        outs = [_ptr(o["x_new"], F64), _ptr(o["u_new"], F64), o["info"].data_ptr()]
+        return self._box_admm_call("irs_tvlqr_box_descent", prefix, outs, ws, o, rho, relax, max_iter, eps,
+                                   adaptive_rho, lazy_bounds, enforced, self.n + self.m)
 
     def tvlqr_box_solve(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo=None, x_hi=None, u_lo=None, u_hi=None,
                         du_lo=None, du_hi=None, position_controlled=False, alpha_R=0.5, rho=10.0, relax=1.6,
@@ -351,41 +346,11 @@ class DeviceModel:
                  u_star=torch.zeros((T, Bt.shape[2]), dtype=F64, device=dev),
                  info=torch.full((3,), -1, dtype=torch.int32, device=dev))
         ws = self._box_workspace(T, position_controlled, dev, force=records_in_hbm)   # None while they fit on chip
-        if lazy_bounds:
-            o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
-            self._lazy_outputs(o, enforced, At.shape[1] + (2 if position_controlled else 1) * Bt.shape[2], dev)
-            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=bool(adaptive_rho))
-            check(self.lib.irs_tvlqr_box_solve_lazy(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
-                                                    _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
-                                                    float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64),
-                                                    1 if position_controlled else 0, _ptr(x_lo, F64), _ptr(x_hi, F64),
-                                                    _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64),
-                                                    ctypes.byref(st), _ptr(o["x_star"], F64), _ptr(o["u_star"], F64),
-                                                    o["info"].data_ptr(), _ptr(o["adapt"], F64), *_ws_args(ws),
-                                                    o["enforced"].data_ptr(), _ptr(o["lazy"], F64), _stream()),
-                  "irs_tvlqr_box_solve_lazy")
-            return o
-        if adaptive_rho:
-            o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
-            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=True)
-            check(self.lib.irs_tvlqr_box_solve_set(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
-                                                   _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
-                                                   float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64),
-                                                   1 if position_controlled else 0, _ptr(x_lo, F64), _ptr(x_hi, F64),
-                                                   _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64),
-                                                   ctypes.byref(st), _ptr(o["x_star"], F64), _ptr(o["u_star"], F64),
-                                                   o["info"].data_ptr(), _ptr(o["adapt"], F64), *_ws_args(ws),
-                                                   _stream()), "irs_tvlqr_box_solve_set")
-            return o
-        check(self.lib.irs_tvlqr_box_solve_wsx(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
-                                               _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
-                                               float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64),
-                                               1 if position_controlled else 0, _ptr(x_lo, F64), _ptr(x_hi, F64),
-                                               _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64),
-                                               float(rho), float(relax), int(max_iter), float(eps),
-                                               _ptr(o["x_star"], F64), _ptr(o["u_star"], F64), o["info"].data_ptr(),
-                                               *_ws_args(ws), _stream()), "irs_tvlqr_box_solve_wsx")
-        return o
+        prefix = [T, *(_ptr(a, F64) for a in (At, Bt, ct, Q, Qd, R)), float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64),
+                  1 if position_controlled else 0, *(_ptr(a, F64) for a in (x_lo, x_hi, u_lo, u_hi, du_lo, du_hi))]
+        outs = [_ptr(o["x_star"], F64), _ptr(o["u_star"], F64), o["info"].data_ptr()]
+        return self._box_admm_call("irs_tvlqr_box_solve", prefix, outs, ws, o, rho, relax, max_iter, eps, adaptive_rho,
+                                   lazy_bounds, enforced, At.shape[1] + (2 if position_controlled else 1) * Bt.shape[2])
 
     SOLVER_AUTO, SOLVER_ADMM, SOLVER_ACTIVE_SET, SOLVER_ACTIVE_SET_MFMA = 0, 1, 2, 3
 
@@ -424,41 +389,15 @@ class DeviceModel:
             assert b is None or tuple(b.shape) == shape, (tuple(b.shape), shape)
         assert act is None or tuple(act.shape) == (T, self.m)
         ws = self._descent_workspace(T, solver, dev) if int(solver) in (0, 1, 3) else None
-        if lazy_bounds:
-            if int(solver) != 1:
-                raise ValueError("lazy_bounds belongs to the ADMM kernel: solver must be 1, not %d" % int(solver))
-            if "adapt" not in o:
-                o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
-            self._lazy_outputs(o, enforced, self.n + 2 * self.m, dev)
-            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=bool(adaptive_rho))
-            check(self.lib.irs_quasistatic_box_descent_lazy(
-                self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64), _ptr(ct, F64), _ptr(Q, F64),
-                _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(x_lo, F64), _ptr(x_hi, F64),
-                _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64), 1, ctypes.byref(st),
-                _ptr(o["x_new"], F64), _ptr(o["u_new"], F64), _ptr(o["cost"], F64), o["info"].data_ptr(),
-                _ptr(o["adapt"], F64), *_ws_args(ws), o["enforced"].data_ptr(), _ptr(o["lazy"], F64), _stream()),
-                "irs_quasistatic_box_descent_lazy")
-            return o
-        if adaptive_rho:
-            if int(solver) != 1:
-                raise ValueError("adaptive_rho belongs to the ADMM kernel: solver must be 1, not %d" % int(solver))
-            if "adapt" not in o:
-                o["adapt"] = torch.empty((3,), dtype=F64, device=dev)
-            st = _lib.admm_settings(rho, relax, max_iter, eps, adaptive=True)
-            check(self.lib.irs_quasistatic_box_descent_set(
-                self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64), _ptr(ct, F64), _ptr(Q, F64),
-                _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(x_lo, F64), _ptr(x_hi, F64),
-                _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64), 1, ctypes.byref(st),
-                _ptr(o["x_new"], F64), _ptr(o["u_new"], F64), _ptr(o["cost"], F64), o["info"].data_ptr(),
-                _ptr(o["adapt"], F64), *_ws_args(ws), _stream()), "irs_quasistatic_box_descent_set")
-            return o
-        check(self.lib.irs_quasistatic_box_descent_wsx(
-            self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64), _ptr(ct, F64), _ptr(Q, F64),
-            _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(x_lo, F64), _ptr(x_hi, F64),
-            _ptr(u_lo, F64), _ptr(u_hi, F64), _ptr(du_lo, F64), _ptr(du_hi, F64), int(solver), float(rho),
-            float(relax), int(max_iter), float(eps), _ptr(o["x_new"], F64), _ptr(o["u_new"], F64), _ptr(o["cost"], F64),
-            o["info"].data_ptr(), _ptr(act, F64), *_ws_args(ws), _stream()), "irs_quasistatic_box_descent_wsx")
-        return o
+        for flag, on in (("lazy_bounds", lazy_bounds), ("adaptive_rho", adaptive_rho)):
+            if on and int(solver) != 1:
+                raise ValueError("%s belongs to the ADMM kernel: solver must be 1, not %d" % (flag, int(solver)))
+        prefix = [T, *(_ptr(a, F64) for a in (At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo, x_hi, u_lo, u_hi, du_lo, du_hi)),
+                  int(solver)]
+        outs = [_ptr(o["x_new"], F64), _ptr(o["u_new"], F64), _ptr(o["cost"], F64), o["info"].data_ptr()]
+        return self._box_admm_call("irs_quasistatic_box_descent", prefix, outs, ws, o, rho, relax, max_iter, eps,
+                                   adaptive_rho, lazy_bounds, enforced, self.n + 2 * self.m,
+                                   wsx_extra=[_ptr(act, F64)])
 
     # ---- B quasistatic descents per launch ------------------------------------
     def _descent_batch_workspace(self, T, B, device, force=False):
