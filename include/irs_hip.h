@@ -796,6 +796,31 @@ int irs_cem_refit_drawn(int T, int m, int B, int n_elite, const double *u_mean, 
                         uint64_t seed, uint32_t iter, uint64_t sample_offset, const double *costs,
                         int *elite_idx, double *u_new, double *std_new, void *stream);
 
+/* ---- Model-free CEM rollout: one stage per call, the caller steps the plant ----------------------------
+ * irs_cem_rollout_costs[_drawn] for a system that has no device functor (a TorchDynamicalSystem): the time
+ * loop is the caller's.  For t = 0 .. T the caller makes one call with x (B,n) DEV f64 holding the B states
+ * at step t -- x0 in every row at t = 0, afterwards whatever its dynamics returned for (x, u_t) of the call
+ * before.  Stage t of candidate b
+ *   - adds (x[b] - xd_trj[t])' Q (x[b] - xd_trj[t]) to costs[b]; t = T is the terminal stage and also uses Q
+ *     (cem.py:138-139); at t = 0 costs[b] is WRITTEN, so costs (B) DEV f64 needs no clearing;
+ *   - for t < T writes the candidate's control of step t -- u_cand[b,t,:] of the supplied (B,T,m) tensor, or
+ *     the drawn one (the stream of irs_cem_candidates: same counters, same bits) -- to u_t[b,:] (B,m) DEV f64
+ *     out, and adds u' R u.  At t = T u_t is not touched and may be NULL.
+ * Q (n,n), R (m,m) dense, xd_trj (T+1,n).  1 <= n <= 32, 1 <= m <= 16.  All arithmetic f64, the terms added in
+ * the order irs_cem_rollout_costs adds them; a non-finite state gives a non-finite cost for that candidate
+ * only.  After stage T costs holds what irs_cem_rollout_costs returns for the same dynamics; selection and
+ * refit are irs_cem_refit / irs_cem_refit_drawn.  One launch on `stream`, no allocation, no host
+ * synchronisation.  Decided before any HIP call:
+ *   IRS_ERR_INVALID_ARG  n outside 1..32, m outside 1..16; T or B <= 0; t outside 0..T; a null pointer (u_t
+ *                        only while t < T)                                                               */
+int irs_cem_values_stage(int n, int m, int T, int B, int t, const double *x, const double *u_cand,
+                         const double *Q, const double *R, const double *xd_trj,
+                         double *u_t, double *costs, void *stream);
+int irs_cem_values_stage_drawn(int n, int m, int T, int B, int t, const double *x, const double *u_mean,
+                               const double *std, uint64_t seed, uint32_t iter, uint64_t sample_offset,
+                               const double *Q, const double *R, const double *xd_trj,
+                               double *u_t, double *costs, void *stream);
+
 /* CrossEntropyMethod.iterate (cem.py:186-216) / CrossEntropyMethodQuasistatic.iterate
  * (cem_quasistatic.py:200-258) as ONE call: n_descents x (price B drawn candidates, select, refit, roll
  * out the new mean (cem.py:182) and price it with the cost the candidates got), enqueued back to back on

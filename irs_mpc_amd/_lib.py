@@ -154,6 +154,10 @@ SIGNATURES["irs_cem_rollout_costs_quasistatic_drawn"] = (c_int, [c_int, POINTER(
                                                                  _dp, c_void_p])
 SIGNATURES["irs_cem_refit_drawn"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, c_uint64, c_uint32, c_uint64, _dp, _dp,
                                              _dp, _dp, c_void_p])
+SIGNATURES["irs_cem_values_stage"] = (c_int, [c_int, c_int, c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                              c_void_p])
+SIGNATURES["irs_cem_values_stage_drawn"] = (c_int, [c_int, c_int, c_int, c_int, c_int, _dp, _dp, _dp, c_uint64, c_uint32,
+                                                    c_uint64, _dp, _dp, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_cem_iterate_scratch_bytes"] = (c_size_t, [c_int, c_int, c_int, c_int])
 SIGNATURES["irs_cem_iterate"] = (c_int, [POINTER(CemIterateCall), c_void_p])
 SIGNATURES["irs_tvlqr_box_descent"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,

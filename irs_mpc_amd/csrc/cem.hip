@@ -18,6 +18,10 @@
 // with the same (seed, iter), so there is no second keying.  It is that generator with the radius of the rare pairs
 // with u1 -> 1 formed from 1 - u1 (philox_normal4<true>): the candidates are held to the f64 restatement element by
 // element (std (2e-5 |z| + 2e-6)), which the f32 rounding of u1 next to 1 misses about once in 3e4 pairs.
+//
+// Model-free form (irs_cem_values_stage[_drawn]): for a system that is a torch callable, step 1 is T + 1 launches of
+// cem_values_stage_kernel -- the time-loop body of cem_rollout_kernel without the dynamics -- with the callable
+// stepping all B states between them; steps 2-3 are the kernels above, which never see a Model.
 #include "boxqp.hpp"      // has_u_into_x
 #include "philox.hpp"
 
@@ -180,6 +184,116 @@ __global__ __launch_bounds__(64) void cem_rollout_quasistatic_kernel(ModelParams
         for (int i = 0; i < n; ++i) x[i] = xn[i];
     }
     costs[b] = cost;
+}
+
+// ---- model-free rollout: one stage of B candidate rollouts, the plant stepped by the caller between launches ----
+// cem_rollout_kernel with the dynamics taken out (TorchDeviceModel.cem_rollout_costs: the torch callable steps all B
+// states between two stages).  Stage t of candidate b: costs[b] (+)= e' Q e + u' R u with e = x[b] - xd_t and u the
+// candidate's control of step t, which is also written to u_t[b] for the callable; the terms are added in the order
+// of cem_rollout_kernel's time loop, so equal states give equal bits.  Stage 0 writes costs, stage T has no control.
+//
+// One lane per candidate, n <= 32 and m <= 16 at run time.  A lane's row of x is n doubles at stride n: read by the
+// lane itself, a wave's load would touch 64 rows with 8 bytes of each.  The workgroup's kStageBlock rows are one
+// contiguous range of x, so the workgroup reads that range linearly -- lane i at base + 8 i, 512 bytes a wave and
+// instruction -- into an LDS tile and every lane then works on its row there; u_t leaves the same way.  Rows are
+// pitched to an odd number of doubles: the 32 lanes of an LDS access group then sit on 32 distinct bank pairs.
+// Eight bytes a lane, not sixteen: the range starts at row b0 of a tensor the C ABI only knows to be 8-byte aligned,
+// and the stage is bound by its launch, not its loads (B (n + m + 2) doubles: 1.6 MB at B = 50 000, n = 2, m = 1).
+constexpr int kStageBlock = 128;
+constexpr int kStageMaxN = 32, kStageMaxM = 16;      // torch_system.MAX_DIM_X / MAX_DIM_U
+
+__host__ __device__ constexpr int stage_pitch(int w) { return w | 1; }
+
+// Q (n n) | R (m m) | xd_t (n) | e tile (kStageBlock, pitch n) | u tile (kStageBlock, pitch m): 61 696 bytes at most
+size_t stage_lds_bytes(int n, int m) {
+    return sizeof(double) * (size_t)(n * n + m * m + n + kStageBlock * (stage_pitch(n) + stage_pitch(m)));
+}
+
+// The controls of step t of candidates b0 .. b0 + rows into the tile us (pitch mp) and out to u_t (B,m).
+// Supplied: a row is m consecutive doubles at stride T m; thread q takes element q of the (rows, m) block, so a
+// wave reads whole rows and writes u_t linearly -- the value stored is the value loaded.
+__device__ __forceinline__ void stage_controls(const CemSupplied& src, int m, int mp, int T, int t, int b0, int rows,
+                                               double* __restrict__ us, double* __restrict__ u_t) {
+    for (int q = threadIdx.x; q < rows * m; q += kStageBlock) {
+        const int r = q / m, j = q - r * m;
+        const double v = src.u_cand[((size_t)(b0 + r) * T + t) * m + j];
+        us[r * mp + j] = v;
+        u_t[(size_t)b0 * m + q] = v;
+    }
+}
+
+// Drawn: the lane draws its own row (ceil(m/4) Philox calls, as CemDrawn::row with m known at run time: the same
+// counters, the same cem_candidate), the workgroup then writes the tile out linearly.
+__device__ __forceinline__ void stage_controls(const CemDrawn& src, int m, int mp, int, int t, int b0, int rows,
+                                               double* __restrict__ us, double* __restrict__ u_t) {
+    const int r = threadIdx.x;
+    if (r < rows) {
+        const uint64_t gidx = src.lane(b0 + r, 0, 0);
+        for (int blk = 0; 4 * blk < m; ++blk) {
+            float z[4];
+            philox_normal4<true>(gidx, (uint32_t)t, (uint32_t)blk, src.iter, src.seed, z);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int j = 4 * blk + c;
+                if (j < m) us[r * mp + j] = cem_candidate(src.mean[(size_t)t * m + j], src.std[(size_t)t * m + j], z[c]);
+            }
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < rows * m; q += kStageBlock) {
+        const int rr = q / m;
+        u_t[(size_t)b0 * m + q] = us[rr * mp + (q - rr * m)];
+    }
+}
+
+template <class Src>
+__global__ __launch_bounds__(kStageBlock) void cem_values_stage_kernel(int n, int m, int T, int B, int t, Src src,
+                                                                       const double* __restrict__ x,
+                                                                       const double* __restrict__ Q,
+                                                                       const double* __restrict__ R,
+                                                                       const double* __restrict__ xd_trj,
+                                                                       double* __restrict__ u_t,
+                                                                       double* __restrict__ costs) {
+    extern __shared__ double stage_lds[];
+    const int np = stage_pitch(n), mp = stage_pitch(m);
+    double* Qs = stage_lds;
+    double* Rs = Qs + n * n;
+    double* xds = Rs + m * m;
+    double* es = xds + n;
+    double* us = es + kStageBlock * np;
+    const int tid = threadIdx.x;
+    const int b0 = blockIdx.x * kStageBlock;
+    const int rows = min(kStageBlock, B - b0);
+    for (int q = tid; q < n * n; q += kStageBlock) Qs[q] = Q[q];
+    for (int q = tid; q < m * m; q += kStageBlock) Rs[q] = R[q];
+    for (int q = tid; q < n; q += kStageBlock) xds[q] = xd_trj[(size_t)t * n + q];
+    const double* xb = x + (size_t)b0 * n;
+    for (int q = tid; q < rows * n; q += kStageBlock) {
+        const int r = q / n;
+        es[r * np + (q - r * n)] = xb[q];
+    }
+    if (t < T) stage_controls(src, m, mp, T, t, b0, rows, us, u_t);      // t is uniform: every thread or none
+    __syncthreads();
+    if (tid >= rows) return;
+    double* e = es + tid * np;
+    const double* u = us + tid * mp;
+    double cost = t == 0 ? 0.0 : costs[b0 + tid];
+    for (int j = 0; j < n; ++j) e[j] -= xds[j];
+    // (x_t - xd_t)' Q (x_t - xd_t); the terminal term also uses Q (cem.py:138-139).  No min / max, no compare: a
+    // non-finite state makes this candidate's cost non-finite and no other's.
+    for (int i = 0; i < n; ++i) {
+        double r = 0.0;
+        for (int j = 0; j < n; ++j) r += Qs[i * n + j] * e[j];
+        cost += e[i] * r;
+    }
+    if (t < T) {
+        for (int i = 0; i < m; ++i) {
+            double r = 0.0;
+            for (int j = 0; j < m; ++j) r += Rs[i * m + j] * u[j];
+            cost += u[i] * r;
+        }
+    }
+    costs[b0 + tid] = cost;
 }
 
 // Order-preserving map f64 -> u64 (NaN sorts last: a diverged rollout is never elite).
@@ -406,6 +520,25 @@ int position_controlled(int model) {
     return rc;
 }
 
+// What both stage entries refuse, before any HIP call; nullptr if the sizes and the shared pointers are fine.
+const char* stage_argument_error(int n, int m, int T, int B, int t, const double* x, const double* Q, const double* R,
+                                 const double* xd_trj, const double* u_t, const double* costs) {
+    if (n < 1 || n > kStageMaxN) return "n must be in 1..32";
+    if (m < 1 || m > kStageMaxM) return "m must be in 1..16";
+    if (T <= 0 || B <= 0) return "T and B must be positive";
+    if (t < 0 || t > T) return "t must be in 0..T";
+    if (!x || !Q || !R || !xd_trj || !costs) return "null pointer";
+    if (t < T && !u_t) return "u_t is null at a stage t < T";
+    return nullptr;
+}
+
+template <class Src>
+void launch_stage(int n, int m, int T, int B, int t, const Src& src, const double* x, const double* Q, const double* R,
+                  const double* xd_trj, double* u_t, double* costs, hipStream_t st) {
+    hipLaunchKernelGGL((cem_values_stage_kernel<Src>), dim3((B + kStageBlock - 1) / kStageBlock), dim3(kStageBlock),
+                       stage_lds_bytes(n, m), st, n, m, T, B, t, src, x, Q, R, xd_trj, u_t, costs);
+}
+
 void launch_refit_drawn(int T, int m, int B, int n_elite, const CemDrawn& src, const double* costs, int* elite_idx,
                         double* u_new, double* std_new, hipStream_t st) {
     hipLaunchKernelGGL(cem_select_kernel, dim3(1), dim3(kSelBlock), 0, st, costs, B, n_elite, elite_idx);
@@ -524,6 +657,30 @@ int irs_cem_refit_drawn(int T, int m, int B, int n_elite, const double* u_mean, 
                   "u_new / std_new must not alias u_mean / std (the refit reads the old ones while it writes)");
     launch_refit_drawn(T, m, B, n_elite, CemDrawn{u_mean, std, seed, sample_offset, iter}, costs, elite_idx, u_new,
                        std_new, static_cast<hipStream_t>(stream));
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+// ---- model-free rollout: one stage per call, the caller steps the plant between calls ---------------------------
+
+int irs_cem_values_stage(int n, int m, int T, int B, int t, const double* x, const double* u_cand, const double* Q,
+                         const double* R, const double* xd_trj, double* u_t, double* costs, void* stream) {
+    const char* bad = stage_argument_error(n, m, T, B, t, x, Q, R, xd_trj, u_t, costs);
+    IRS_CHECK_ARG(bad == nullptr, bad);
+    IRS_CHECK_ARG(u_cand != nullptr, "null pointer");
+    launch_stage(n, m, T, B, t, CemSupplied{u_cand}, x, Q, R, xd_trj, u_t, costs, static_cast<hipStream_t>(stream));
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+int irs_cem_values_stage_drawn(int n, int m, int T, int B, int t, const double* x, const double* u_mean,
+                               const double* std, uint64_t seed, uint32_t iter, uint64_t sample_offset, const double* Q,
+                               const double* R, const double* xd_trj, double* u_t, double* costs, void* stream) {
+    const char* bad = stage_argument_error(n, m, T, B, t, x, Q, R, xd_trj, u_t, costs);
+    IRS_CHECK_ARG(bad == nullptr, bad);
+    IRS_CHECK_ARG(u_mean != nullptr && std != nullptr, "null pointer");
+    launch_stage(n, m, T, B, t, CemDrawn{u_mean, std, seed, sample_offset, iter}, x, Q, R, xd_trj, u_t, costs,
+                 static_cast<hipStream_t>(stream));
     IRS_CHECK_LAUNCH();
     return IRS_OK;
 }

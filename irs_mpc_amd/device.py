@@ -56,7 +56,43 @@ def smooth_geometry(model_id, mode, T, N, rng=False):
                 wg0_rr=out[5], branch=_lib.SMOOTH_PLANS[out[6]])
 
 
-class DeviceModel:
+class CemModelFree:
+    """The CEM calls that never see the plant -- selection + refit, the candidate writer -- for every class with a
+    `lib`: DeviceModel and torch_system.TorchDeviceModel."""
+
+    def cem_refit(self, u_cand, costs, n_elite):
+        """Elite selection + mean/std refit: returns elite_idx (n_elite), u_new (T,m), std_new (T,m)."""
+        B, T, m = u_cand.shape
+        dev = u_cand.device
+        idx = torch.empty((n_elite,), dtype=torch.int32, device=dev)
+        u_new = torch.empty((T, m), dtype=F64, device=dev)
+        std_new = torch.empty((T, m), dtype=F64, device=dev)
+        check(self.lib.irs_cem_refit(T, m, B, int(n_elite), _ptr(u_cand, F64), _ptr(costs, F64), idx.data_ptr(),
+                                     _ptr(u_new, F64), _ptr(std_new, F64), _stream()), "irs_cem_refit")
+        return idx, u_new, std_new
+
+    def cem_candidates(self, u_mean, std, B, seed, it, sample_offset=0):
+        """The (B,T,m) candidates the drawn kernels see (verification only)."""
+        T, m = u_mean.shape
+        u_cand = torch.empty((B, T, m), dtype=F64, device=u_mean.device)
+        check(self.lib.irs_cem_candidates(T, m, int(B), _ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it),
+                                          int(sample_offset), _ptr(u_cand, F64), _stream()), "irs_cem_candidates")
+        return u_cand
+
+    def cem_refit_drawn(self, u_mean, std, seed, it, costs, n_elite, sample_offset=0):
+        """cem_refit with the elites regenerated from their indices: elite_idx, u_new, std_new (fresh tensors)."""
+        T, m = u_mean.shape
+        dev = u_mean.device
+        idx = torch.empty((n_elite,), dtype=torch.int32, device=dev)
+        u_new = torch.empty((T, m), dtype=F64, device=dev)
+        std_new = torch.empty((T, m), dtype=F64, device=dev)
+        check(self.lib.irs_cem_refit_drawn(T, m, costs.shape[0], int(n_elite), _ptr(u_mean, F64), _ptr(std, F64),
+                                           int(seed), int(it), int(sample_offset), _ptr(costs, F64), idx.data_ptr(),
+                                           _ptr(u_new, F64), _ptr(std_new, F64), _stream()), "irs_cem_refit_drawn")
+        return idx, u_new, std_new
+
+
+class DeviceModel(CemModelFree):
     """A registered device functor (irs_model_id) with its constants bound."""
 
     def __init__(self, model_id, params):
@@ -476,26 +512,7 @@ class DeviceModel:
               "irs_cem_rollout_costs_quasistatic")
         return costs
 
-    def cem_refit(self, u_cand, costs, n_elite):
-        """Elite selection + mean/std refit: returns elite_idx (n_elite), u_new (T,m), std_new (T,m)."""
-        B, T, m = u_cand.shape
-        dev = u_cand.device
-        idx = torch.empty((n_elite,), dtype=torch.int32, device=dev)
-        u_new = torch.empty((T, m), dtype=F64, device=dev)
-        std_new = torch.empty((T, m), dtype=F64, device=dev)
-        check(self.lib.irs_cem_refit(T, m, B, int(n_elite), _ptr(u_cand, F64), _ptr(costs, F64), idx.data_ptr(),
-                                     _ptr(u_new, F64), _ptr(std_new, F64), _stream()), "irs_cem_refit")
-        return idx, u_new, std_new
-
     # device-resident form: the candidates are drawn inside the kernels (include/irs_hip.h), never stored
-    def cem_candidates(self, u_mean, std, B, seed, it, sample_offset=0):
-        """The (B,T,m) candidates the drawn kernels see (verification only)."""
-        T, m = u_mean.shape
-        u_cand = torch.empty((B, T, m), dtype=F64, device=u_mean.device)
-        check(self.lib.irs_cem_candidates(T, m, int(B), _ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it),
-                                          int(sample_offset), _ptr(u_cand, F64), _stream()), "irs_cem_candidates")
-        return u_cand
-
     def cem_rollout_costs_drawn(self, u_mean, std, B, seed, it, x0, Q, R, xd_trj, sample_offset=0):
         """cem_rollout_costs of B candidates drawn around u_mean (T,m) with std (T,m)."""
         costs = torch.empty((int(B),), dtype=F64, device=u_mean.device)
@@ -516,18 +533,6 @@ class DeviceModel:
                                                                _ptr(costs, F64), _stream()),
               "irs_cem_rollout_costs_quasistatic_drawn")
         return costs
-
-    def cem_refit_drawn(self, u_mean, std, seed, it, costs, n_elite, sample_offset=0):
-        """cem_refit with the elites regenerated from their indices: elite_idx, u_new, std_new (fresh tensors)."""
-        T, m = u_mean.shape
-        dev = u_mean.device
-        idx = torch.empty((n_elite,), dtype=torch.int32, device=dev)
-        u_new = torch.empty((T, m), dtype=F64, device=dev)
-        std_new = torch.empty((T, m), dtype=F64, device=dev)
-        check(self.lib.irs_cem_refit_drawn(T, m, costs.shape[0], int(n_elite), _ptr(u_mean, F64), _ptr(std, F64),
-                                           int(seed), int(it), int(sample_offset), _ptr(costs, F64), idx.data_ptr(),
-                                           _ptr(u_new, F64), _ptr(std_new, F64), _stream()), "irs_cem_refit_drawn")
-        return idx, u_new, std_new
 
     def cem_iterate(self, u_trj0, std0, x0, Q, Qd, R, xd_trj, B, n_elite, n_descents, seed, iter0=1,
                     quasistatic=False):
@@ -932,3 +937,24 @@ def box_values_solve(At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo=None, x_hi=None, u_l
     u_star = torch.zeros((T, m), dtype=F64, device=h["device"])
     box_values_tail(h, 0, x0, max_iter, eps, x_plan=x_star, u_plan=u_star)
     return dict(x_star=x_star, u_star=u_star, info=h["info"])
+
+
+# ---- model-free CEM rollout (csrc/cem.hip, cem_values_stage_kernel): the caller steps the plant between the stages ----
+def cem_values_stage(t, x, u_cand, Q, R, xd_trj, u_t, costs):
+    """Stage t of B candidate rollouts on the supplied candidates u_cand (B,T,m) (irs_cem_values_stage): x (B,n) are
+    the states at step t; costs (B) gets this stage's cost terms (written at t = 0, added after), u_t (B,m) the
+    controls of step t (None at t = T).  One launch."""
+    B, T, m = u_cand.shape
+    check(_lib.load().irs_cem_values_stage(x.shape[1], m, T, B, int(t), _ptr(x, F64), _ptr(u_cand, F64), _ptr(Q, F64),
+                                           _ptr(R, F64), _ptr(xd_trj, F64), _ptr(u_t, F64), _ptr(costs, F64),
+                                           _stream()), "irs_cem_values_stage")
+
+
+def cem_values_stage_drawn(t, x, u_mean, std, seed, it, sample_offset, Q, R, xd_trj, u_t, costs):
+    """cem_values_stage with the controls drawn around u_mean (T,m) with std (T,m) -- the stream of cem_candidates --
+    for the B = x.shape[0] candidates sample_offset .. sample_offset + B (irs_cem_values_stage_drawn)."""
+    T, m = u_mean.shape
+    check(_lib.load().irs_cem_values_stage_drawn(x.shape[1], m, T, x.shape[0], int(t), _ptr(x, F64), _ptr(u_mean, F64),
+                                                 _ptr(std, F64), int(seed), int(it), int(sample_offset), _ptr(Q, F64),
+                                                 _ptr(R, F64), _ptr(xd_trj, F64), _ptr(u_t, F64), _ptr(costs, F64),
+                                                 _stream()), "irs_cem_values_stage_drawn")

@@ -30,9 +30,16 @@ Bounds: a box bound that binds takes the stepped bounded descent when IrsLqrPara
 float64 step of the callable, all on the current stream with nothing read on the host); without the flag it raises
 NotImplementedError, as a compiled model is then needed.
 
+CrossEntropyMethod: the B candidate rollouts are T + 1 stage launches of csrc/cem.hip (cem_values_stage_kernel: the
+candidate's control of step t out, its cost terms in) with one float64 call of the callable on (B,n), (B,m) between
+two of them; selection and refit are the model-free kernels of the compiled systems.  With CemParameters.device_seed
+the candidates are drawn inside the stages, no (B,T,m) tensor exists, and `iterate` enqueues every descent before it
+reads anything back (TorchDeviceModel.cem_iterate).
+
 Limits: dim_x <= 32, dim_u <= 16; samples are evaluated in float32; a rollout is T torch steps; the bounded descent
 has the fixed penalty only (qp_adaptive_rho and qp_lazy_bounds are compiled-only) and a horizon limit
-(box_horizon_limit); no fused `irs_iterate` loop.  CrossEntropyMethod, the quasistatic classes and the
+(box_horizon_limit); no fused `irs_iterate` loop; the candidate rollouts of a CEM descent are T + 1 stage launches and
+T calls of the callable where a compiled system's are one launch.  The quasistatic classes (CrossEntropyMethodQuasistatic among them) and the
 position-controlled form of `solve_tvlqr` stay compiled-models-only.
 """
 import numpy as np
@@ -70,9 +77,9 @@ class TorchDynamicalSystem(DynamicalSystem):
         return self.dm().jacobian_xu_batch(dev.to_dev(x), dev.to_dev(u)).cpu().numpy()
 
 
-class TorchDeviceModel:
-    """What `IrsLqr` calls on `system.dm()`, for a TorchDynamicalSystem: the method names, signatures and result keys
-    of device.DeviceModel."""
+class TorchDeviceModel(dev.CemModelFree):
+    """What `IrsLqr` and `CrossEntropyMethod` call on `system.dm()`, for a TorchDynamicalSystem: the method names,
+    signatures and result keys of device.DeviceModel."""
 
     compiled = False            # no device functor: no fused loop; bounded descents are stepped (tvlqr_box_descent)
     model_id = None
@@ -268,3 +275,52 @@ class TorchDeviceModel:
             dev.box_values_tail(h, t, x_new[t], max_iter, eps, u_t=u_new[t])
             x_new[t + 1] = self._step(x_new[t], u_new[t])
         return dict(x_new=x_new, u_new=u_new, info=h["info"])
+
+    # ---- CEM baseline: DeviceModel's surface (cem_refit, cem_refit_drawn, cem_candidates: dev.CemModelFree) ---------
+    def _cem_rollout(self, B, T, x0, xd_trj, stage):
+        """The time loop of B rollouts: stage(t, x, u_t, costs) for t = 0..T with one float64 call of the callable
+        between two stages -- T + 1 launches and T torch steps on the current stream, nothing read on the host."""
+        x = x0.expand(B, self.n).contiguous()
+        u_t = torch.empty((B, self.m), dtype=dev.F64, device=x0.device)
+        costs = torch.empty((B,), dtype=dev.F64, device=x0.device)
+        for t in range(T):
+            stage(t, x, u_t, costs)
+            x = self._f(x, u_t)
+        stage(T, x, None, costs)
+        return costs
+
+    def cem_rollout_costs(self, u_cand, x0, Q, R, xd_trj):
+        """costs (B) of the B candidate sequences u_cand (B,T,m): rollout + evaluate_cost each."""
+        return self._cem_rollout(u_cand.shape[0], u_cand.shape[1], x0, xd_trj, lambda t, x, u_t, costs:
+                                 dev.cem_values_stage(t, x, u_cand, Q, R, xd_trj, u_t, costs))
+
+    def cem_rollout_costs_drawn(self, u_mean, std, B, seed, it, x0, Q, R, xd_trj, sample_offset=0):
+        """cem_rollout_costs of B candidates drawn around u_mean (T,m) with std (T,m): no (B,T,m) tensor."""
+        return self._cem_rollout(int(B), u_mean.shape[0], x0, xd_trj, lambda t, x, u_t, costs:
+                                 dev.cem_values_stage_drawn(t, x, u_mean, std, seed, it, sample_offset, Q, R, xd_trj,
+                                                            u_t, costs))
+
+    def cem_iterate(self, u_trj0, std0, x0, Q, Qd, R, xd_trj, B, n_elite, n_descents, seed, iter0=1,
+                    quasistatic=False):
+        """n_descents CEM descents enqueued back to back, nothing read back: the dict of device histories
+        DeviceModel.cem_iterate returns -- u_hist, std_hist (n_descents,T,m), x_hist (n_descents,T+1,n), cost_hist
+        (n_descents).  Descent i draws around descent i - 1's refit with generator iteration iter0 + i, as
+        irs_cem_iterate does; here the loop is the host's and only enqueues."""
+        if quasistatic:
+            raise NotImplementedError("the quasistatic CEM cost needs a compiled position-controlled model; a "
+                                      "TorchDynamicalSystem runs CrossEntropyMethod only")
+        T, m = u_trj0.shape
+        device, k = u_trj0.device, int(n_descents)
+        o = {"u_hist": torch.empty((k, T, m), dtype=dev.F64, device=device),
+             "std_hist": torch.empty((k, T, m), dtype=dev.F64, device=device),
+             "x_hist": torch.empty((k, T + 1, self.n), dtype=dev.F64, device=device),
+             "cost_hist": torch.empty((k,), dtype=dev.F64, device=device)}
+        mean, std = u_trj0, std0
+        for i in range(k):
+            costs = self.cem_rollout_costs_drawn(mean, std, B, seed, int(iter0) + i, x0, Q, R, xd_trj)
+            _, mean, std = self.cem_refit_drawn(mean, std, seed, int(iter0) + i, costs, n_elite)
+            x_new, cost = self.rollout_cost(x0, mean, Q, R, xd_trj)        # the mean's rollout (cem.py:182)
+            for key, v in (("u_hist", mean), ("std_hist", std), ("x_hist", x_new)):
+                o[key][i].copy_(v)
+            o["cost_hist"][i:i + 1].copy_(cost.reshape(1))
+        return o
