@@ -151,7 +151,7 @@ int irs_sums_len(int model, int mode);
 size_t irs_smooth_workspace_bytes(int model, int mode, int T, int N);
 
 /* The launch geometry the irs_smooth* calls use for (model, mode, T, N); rng != 0: device-drawn samples.  Makes
- * no launch and needs no device.  The sample pass launches exactly what this reports (one planner, csrc/smooth.hip:
+ * no launch and needs no device.  The sample pass launches exactly what this reports (one planner, csrc/smooth_api.hip:
  * smooth_geometry); like the launch it honours IRS_UG, read per call.  out[]:
  *   [0] family (irs_smooth_family): which sample loop runs
  *   [1] block   threads per workgroup        [2] nblk  workgroups per timestep (grid = nblk x T)

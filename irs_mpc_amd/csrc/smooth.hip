@@ -21,8 +21,9 @@
 //   With several GPUs step 4 is a separate launch (smooth_finalize_kernel) after the
 //   all-reduce of `sums`.
 //
-// Which lane reads which sample is planned on the host in ONE place, smooth_geometry() below (reported by
-// irs_smooth_geometry, restated loop by loop in oracle/smooth_cases.py).
+// Which lane reads which sample is planned on the host in ONE place, smooth_geometry() of smooth_api.hip (reported by
+// irs_smooth_geometry, restated loop by loop in oracle/smooth_cases.py).  This file holds the kernels and their
+// launches (the interface at its end, declared in smooth_common.hpp); every entry point, check and plan is there.
 //
 // Inter-workgroup hand-off follows cdna_hip_programming.md Guideline 16: partials are
 // stored sc1 (agent-scope relaxed atomic stores), every storing wave drains vmcnt, the
@@ -31,19 +32,6 @@
 #include "smooth_common.hpp"
 
 namespace {
-
-template <class Model, int MODE>
-constexpr bool defer_samples() {
-    return irs_contact_exact<Model>::value && MODE != IRS_SMOOTH_ZERO_ORDER_AB && contact_rows<Model>() <= 8;
-}
-// the matrix-core Gram loop (256-thread workgroups): zero-order, one 16-wide tile, too many statistics for registers
-template <class Model, int MODE>
-constexpr bool gram_on_matrix_cores() {
-    using TR = SmoothTraits<Model, MODE>;
-    return MODE == IRS_SMOOTH_ZERO_ORDER_AB && TR::d <= 16 && TR::n <= 16 && TR::PP > 64;
-}
-// the f64 nominal step of workgroup 0 costs its wave about this many sample trips (parked-sample kernels)
-constexpr int kNominalTrips = 2;
 
 constexpr int kDeferRing = 128;     // entries per wave: < 64 waiting + <= 64 new ones
 
@@ -569,132 +557,6 @@ __global__ void rng_samples_kernel(float* dx, float* du, SmoothArgs a) {
     for (int j = 0; j < m; ++j) du[row * m + j] = z[n + j] * a.std[n + j];
 }
 
-// Planner knobs (environment overrides are for tuning experiments only).
-int env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    int v = e ? atoi(e) : dflt;
-    return v < 1 ? 1 : v;
-}
-int tune_spt() { static int v = env_int("IRS_SPT", 32); return v; }                 // samples per lane aimed for
-int tune_single_max() { static int v = env_int("IRS_SINGLE_MAX", 16384); return v; } // <= : one WG per t
-int tune_max_wg() { static int v = env_int("IRS_MAX_WG", 1024); return v; }         // grid cap, light kernels
-int tune_max_wg_heavy() { static int v = env_int("IRS_MAX_WG_HEAVY", 256); return v; }  // 1 wave/SIMD kernels
-int tune_min_wg() { static int v = env_int("IRS_MIN_WG", 256); return v; }          // fill the CUs
-
-constexpr int kBigBlock = 1024;
-
-// Chooses the launch geometry for (T, N).  `light` = the kernel's accumulators fit a
-// 1024-thread workgroup (SmoothTraits::LIGHT).  Measured on MI355X (profiles/): every extra
-// workgroup costs more (its hand-off: write-through stores + ticket) than it gains in
-// streaming parallelism once the CUs are covered, so grids stay SMALL:
-//  * light, samples supplied, N <= tune_single_max(): ONE 1024-thread workgroup per
-//    timestep -- no inter-workgroup hand-off at all;
-//  * otherwise 256-thread workgroups, ~tune_spt() samples per lane, at least enough
-//    workgroups to cover the CUs (while each lane still has >= 4 samples) and at most
-//    ~4 per CU (light kernels) or 1 per CU (kernels that hold 1 wave per SIMD).
-void plan_grid(int T, int N, bool light, bool rng, int* chunk, int* nblk, int* block, bool contact = false) {
-    if (light && !rng && N <= tune_single_max()) {
-        *block = kBigBlock;
-        *nblk = 1;
-        *chunk = (N + kBigBlock - 1) / kBigBlock * kBigBlock;
-        return;
-    }
-    *block = kBlock;
-    if (T < 1) T = 1;
-    const int spt = tune_spt();
-    int nb = (N + kBlock * spt - 1) / (kBlock * spt);
-    int fill = (tune_min_wg() + T - 1) / T;               // blocks per t that cover the CUs
-    // ... keeping >= 4 samples per lane -- 1 for a contact kernel, whose sample costs more than a workgroup's
-    // hand-off (planar hand N = 1000: one workgroup per time step 51 us, four 2x faster)
-    int by4 = contact ? (N + kBlock - 1) / kBlock : (N + kBlock * 4 - 1) / (kBlock * 4);
-    if (fill > by4) fill = by4;
-    if (nb < fill) nb = fill;
-    // heavy kernels: 1 workgroup per CU, 2 once there is enough work to hide the tail.  Contact
-    // kernels never: since the active-set polish they need more than 256 registers (VGPRs + AGPRs), one
-    // wave per SIMD is all a CU can hold, and a second workgroup per CU would only queue behind the first
-    // (before the polish, two per CU won 7 % from N = 1e5 on and lost below that: profiles/).
-    const long long two_per_cu = contact ? (1LL << 62) : 2000000;
-    const int heavy_cap = tune_max_wg_heavy() * ((long long)N * T >= two_per_cu ? 2 : 1);
-    int max_blk = (light ? tune_max_wg() : heavy_cap) / T;
-    if (max_blk < 1) max_blk = 1;
-    if (nb > max_blk) nb = max_blk;
-    if (nb < 1) nb = 1;
-    int c = (N + nb - 1) / nb;
-    c = (c + kBlock - 1) / kBlock * kBlock;
-    *chunk = c;
-    *nblk = (N + c - 1) / c;
-    if (*nblk < 1) *nblk = 1;
-}
-
-template <class Model, int MODE>
-int sums_len_t() { return SmoothTraits<Model, MODE>::P; }
-
-template <class Model>
-bool light_m(int mode) {
-    switch (mode) {
-        case IRS_SMOOTH_ZERO_ORDER_AB: return SmoothTraits<Model, IRS_SMOOTH_ZERO_ORDER_AB>::LIGHT;
-        case IRS_SMOOTH_FIRST_ORDER: return SmoothTraits<Model, IRS_SMOOTH_FIRST_ORDER>::LIGHT;
-        case IRS_SMOOTH_ZERO_ORDER_B: return SmoothTraits<Model, IRS_SMOOTH_ZERO_ORDER_B>::LIGHT;
-    }
-    return false;
-}
-
-bool is_light(int model, int mode) {
-    switch (model) {
-        case IRS_MODEL_PENDULUM: return light_m<PendulumModel>(mode);
-        case IRS_MODEL_QUADROTOR: return light_m<QuadrotorModel>(mode);
-        case IRS_MODEL_BICYCLE: return light_m<BicycleModel>(mode);
-        case IRS_MODEL_THREE_CART: return light_m<ThreeCartModel>(mode);
-        case IRS_MODEL_PLANAR_HAND: return light_m<PlanarHandModel>(mode);
-        case IRS_MODEL_BOX_PIVOT: return light_m<BoxPivotModel>(mode);
-        case IRS_MODEL_BOX_ON_BOX: return light_m<BoxOnBoxModel>(mode);
-        case IRS_MODEL_BOX_PUSH: return light_m<BoxPushModel>(mode);
-        case IRS_MODEL_PLANAR_HAND_EXACT: return light_m<PlanarHandExactModel>(mode);
-        case IRS_MODEL_BOX_PIVOT_EXACT: return light_m<BoxPivotExactModel>(mode);
-        case IRS_MODEL_BOX_PUSH_EXACT: return light_m<BoxPushExactModel>(mode);
-    }
-    return false;
-}
-
-// contact models, in every smoothing mode (nominal_in_wg0<Model, MODE>)
-bool has_nominal_in_wg0(int model, int /*mode*/) {
-    bool r = false;
-    IRS_DISPATCH_MODEL(model, { r = !Model::HAS_JACOBIAN; });
-    return r;
-}
-
-// what the f64 nominal step costs the wave of workgroup 0 that evaluates it, in 64-sample trips of the same kernel
-// (measured per kernel family; IRS_NOMINAL_TRIPS overrides for tuning)
-int nominal_trips(int model, int mode);
-
-// smooth_kernel's DEFER path (defer_samples<Model, MODE>)
-bool uses_parked_samples(int model, int mode) {
-    bool r = false;
-    IRS_DISPATCH_MODEL(model, {
-        r = mode == IRS_SMOOTH_FIRST_ORDER ? defer_samples<Model, IRS_SMOOTH_FIRST_ORDER>()
-                                           : mode == IRS_SMOOTH_ZERO_ORDER_B ? defer_samples<Model, IRS_SMOOTH_ZERO_ORDER_B>() : false;
-    });
-    return r;
-}
-
-int nominal_trips(int model, int mode) {
-    static int ov = env_int("IRS_NOMINAL_TRIPS", -1);      // (env_int clamps to >= 1: unset, this is 1 -- DESIGN section 7)
-    if (ov >= 0) return ov;
-    (void)model; (void)mode;
-    return kNominalTrips;      // measured: 1-3 trips are equal for every contact kernel (planar hand exact / sweeps /
-                               // first-order, box pivoting); 4 and more lose a trip
-}
-
-template <class Model>
-int sums_len_m(int mode) {
-    switch (mode) {
-        case IRS_SMOOTH_ZERO_ORDER_AB: return sums_len_t<Model, IRS_SMOOTH_ZERO_ORDER_AB>();
-        case IRS_SMOOTH_FIRST_ORDER: return sums_len_t<Model, IRS_SMOOTH_FIRST_ORDER>();
-        case IRS_SMOOTH_ZERO_ORDER_B: return sums_len_t<Model, IRS_SMOOTH_ZERO_ORDER_B>();
-    }
-    return -1;
-}
-
 template <class Model, int MODE, int BLOCK>
 void launch_smooth_b(const SmoothArgs& a, bool rng, bool fuse, hipStream_t st) {
     dim3 grid(a.nblk, a.T), block(BLOCK);
@@ -715,464 +577,43 @@ void launch_smooth_m(const SmoothArgs& a, bool rng, bool fuse, hipStream_t st) {
     launch_smooth_b<Model, MODE, kBlock>(a, rng, fuse, st);
 }
 
-template <class Model>
-int launch_smooth(int mode, const SmoothArgs& a, bool rng, bool fuse, hipStream_t st) {
-    switch (mode) {
-        case IRS_SMOOTH_ZERO_ORDER_AB: launch_smooth_m<Model, IRS_SMOOTH_ZERO_ORDER_AB>(a, rng, fuse, st); break;
-        case IRS_SMOOTH_FIRST_ORDER: launch_smooth_m<Model, IRS_SMOOTH_FIRST_ORDER>(a, rng, fuse, st); break;
-        case IRS_SMOOTH_ZERO_ORDER_B: launch_smooth_m<Model, IRS_SMOOTH_ZERO_ORDER_B>(a, rng, fuse, st); break;
-        default: return IRS_ERR_UNSUPPORTED;
-    }
-    return IRS_OK;
-}
-
-template <class Model>
-int launch_finalize(int mode, const SmoothArgs& a, hipStream_t st) {
-    dim3 grid(a.T), block(64);
-    switch (mode) {
-        case IRS_SMOOTH_ZERO_ORDER_AB:
-            hipLaunchKernelGGL((smooth_finalize_kernel<Model, IRS_SMOOTH_ZERO_ORDER_AB>), grid, block, 0, st, a);
-            break;
-        case IRS_SMOOTH_FIRST_ORDER:
-            hipLaunchKernelGGL((smooth_finalize_kernel<Model, IRS_SMOOTH_FIRST_ORDER>), grid, block, 0, st, a);
-            break;
-        case IRS_SMOOTH_ZERO_ORDER_B:
-            hipLaunchKernelGGL((smooth_finalize_kernel<Model, IRS_SMOOTH_ZERO_ORDER_B>), grid, block, 0, st, a);
-            break;
-        default: return IRS_ERR_UNSUPPORTED;
-    }
-    return IRS_OK;
-}
-
-struct SmoothOut {   // finalize outputs; all null = accumulate only
-    double* At; double* Bt; double* ct; int* info; long long n_total;
-};
-
-// The launch geometry of one sample pass: the ONE statement of which kernel family runs (T, N) and how its samples
-// are split over workgroups.  smooth_common launches what this returns; irs_smooth_geometry reports it.
-struct SmoothGeometry {
-    int family;      // IRS_SMOOTH_FAMILY_*
-    int block, nblk; // threads per workgroup, workgroups per timestep
-    int chunk0, chunk, wg0_rr;   // SmoothArgs (0, 0, INT_MAX for the uniform-geometry family: it deals 64-sample blocks)
-    int branch;      // IRS_SMOOTH_PLAN_*: which contact re-planning set chunk0 / chunk
-};
-
-bool uses_matrix_cores(int model, int mode) {
-    if (mode != IRS_SMOOTH_ZERO_ORDER_AB) return false;
-    bool r = false;
-    IRS_DISPATCH_MODEL(model, { r = gram_on_matrix_cores<Model, IRS_SMOOTH_ZERO_ORDER_AB>(); });
-    return r;
-}
-
-int smooth_geometry(int model, int mode, int T, int N, bool rng, SmoothGeometry* g) {
-    IRS_CHECK_ARG(T > 0 && N > 0, "T and N must be positive");
-    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
-    if (irs_sums_len(model, mode) <= 0) return IRS_ERR_UNSUPPORTED;
-    g->branch = IRS_SMOOTH_PLAN_NONE;
-    g->wg0_rr = 0x7fffffff;
-    if (irs_smooth_ug_supported(model, mode)) {
-        // exact 8-row contact model, u-only mode: the uniform-geometry pass (smooth_ug.hip)
-        g->family = IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY;
-        g->nblk = irs_smooth_ug_nblk(T, N);
-        g->block = 512;
-        g->chunk = g->chunk0 = 0;
-        return IRS_OK;
-    }
-    const bool contact = has_nominal_in_wg0(model, mode);
-    plan_grid(T, N, is_light(model, mode), rng, &g->chunk, &g->nblk, &g->block, contact);
-    g->chunk0 = g->chunk;
-    g->family = is_light(model, mode) ? IRS_SMOOTH_FAMILY_LANES_LIGHT      // four samples per lane per trip when supplied
-                : uses_matrix_cores(model, mode) ? IRS_SMOOTH_FAMILY_GRAM_MATRIX_CORE
-                : uses_parked_samples(model, mode) ? IRS_SMOOTH_FAMILY_CONTACT_PARKED
-                : contact ? IRS_SMOOTH_FAMILY_CONTACT_WAVE_DEALT : IRS_SMOOTH_FAMILY_LANES_HEAVY;
-    bool planned = false;
-    if (g->nblk >= 2 && g->block == kBlock && contact) {
-        // contact kernels balance by WAVE trips (64 samples): B blocks plus the nominal step's kNominalTrips
-        // over 4 nblk waves -> tt trips each; workgroup 0: tt - kNominalTrips rounds over its four waves, then
-        // kNominalTrips rounds over three.  (Chunks rounded to whole workgroup trips, as below, left three of the
-        // five workgroups of the benchmark's N = 1e4 with 9 trips and one with 5 + the nominal step.)
-        const int NW = kBlock / 64, B = (N + 63) / 64, nw = g->nblk * NW;
-        const int kNom = nominal_trips(model, mode);
-        const int tt = (B + kNom + nw - 1) / nw, rr = tt - kNom;
-        if (rr >= 1) {
-            const int c0b = NW * rr + (NW - 1) * kNom;
-            const int restb = B > c0b ? (B - c0b + (g->nblk - 1) - 1) / (g->nblk - 1) : 0;
-            if (restb <= NW * tt) {
-                g->chunk0 = c0b * 64;
-                g->chunk = restb > 0 ? restb * 64 : 64;
-                g->wg0_rr = rr;
-                g->branch = IRS_SMOOTH_PLAN_TRIPS;
-                planned = true;
-            }
-        }
-    }
-    if (!planned && g->nblk >= 2 && g->block == kBlock && contact) {
-        // workgroup 0 gives up kNominalCost samples per lane and evaluates the f64 nominal step
-        int c0 = g->chunk - kNominalCost * kBlock;
-        if (c0 < kBlock) c0 = kBlock;
-        int rest = (N - c0 + (g->nblk - 1) - 1) / (g->nblk - 1);
-        rest = (rest + kBlock - 1) / kBlock * kBlock;
-        if (c0 < g->chunk && c0 + (long long)(g->nblk - 1) * rest >= N && rest <= g->chunk + kBlock) {
-            g->chunk0 = c0;
-            g->chunk = rest;
-            g->branch = IRS_SMOOTH_PLAN_COST;
-        }
-    }
-    return IRS_OK;
-}
-
-int smooth_common(int model, const double* params, int n_params, int mode, int T, int N,
-                  const double* x_trj, const double* u_trj, SmoothArgs& a, bool rng, double* sums,
-                  const SmoothOut* out, void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && N > 0, "T and N must be positive");
-    IRS_CHECK_ARG(x_trj && u_trj && sums && workspace, "null pointer");
-    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
-    IRS_CHECK_ARG((size_t)T * sizeof(int) <= kCounterBytes, "T too large for the arrival counters (max 1024)");
-    int rc = irs_load_params(model, params, n_params, &a.p);
-    if (rc != IRS_OK) return rc;
-    size_t need = irs_smooth_workspace_bytes(model, mode, T, N);
-    if (workspace_bytes < need) {
-        irs_set_error("irs_smooth: workspace %zu < %zu bytes", workspace_bytes, need);
-        return IRS_ERR_WORKSPACE;
-    }
-    a.x_trj = x_trj; a.u_trj = u_trj;
-    a.T = T; a.N = N;
-    SmoothGeometry g;
-    rc = smooth_geometry(model, mode, T, N, rng, &g);
-    if (rc != IRS_OK) return rc;
-    a.block = g.block; a.nblk = g.nblk; a.chunk0 = g.chunk0; a.chunk = g.chunk; a.wg0_rr = g.wg0_rr;
-    if (g.family == IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY) {
-        // exact 8-row contact model, u-only mode: the uniform-geometry pass (smooth_ug.hip)
-        a.diag = getenv("IRS_DIAG") ? atoi(getenv("IRS_DIAG")) : 0;      // timing experiments only
-        a.counters = static_cast<int*>(workspace);
-        a.fnom = reinterpret_cast<double*>(static_cast<char*>(workspace) + kCounterBytes);
-        a.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + kCounterBytes + fnom_bytes(T));
-        a.sums = sums;
-        if (out != nullptr) {
-            IRS_CHECK_ARG(out->At && out->Bt && out->ct && out->info && out->n_total > 0, "null output pointer");
-            a.At = out->At; a.Bt = out->Bt; a.ct = out->ct; a.info = out->info;
-            a.n_total = (double)out->n_total;
-        }
-        rc = irs_smooth_ug_launch(model, mode, a, rng, out != nullptr, static_cast<hipStream_t>(stream));
-        if (rc != IRS_OK) return rc;
-        IRS_CHECK_LAUNCH();
-        return IRS_OK;
-    }
-    { static int dg = getenv("IRS_DIAG") ? atoi(getenv("IRS_DIAG")) : 0; a.diag = dg; }
-    a.counters = static_cast<int*>(workspace);
-    a.fnom = reinterpret_cast<double*>(static_cast<char*>(workspace) + kCounterBytes);
-    a.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + kCounterBytes + fnom_bytes(T));
-    a.sums = sums;
-    const bool fuse = out != nullptr;
-    if (fuse) {
-        IRS_CHECK_ARG(out->At && out->Bt && out->ct && out->info && out->n_total > 0, "null output pointer");
-        a.At = out->At; a.Bt = out->Bt; a.ct = out->ct; a.info = out->info;
-        a.n_total = (double)out->n_total;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    IRS_DISPATCH_MODEL(model, { rc = launch_smooth<Model>(mode, a, rng, fuse, st); });
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-// modes that perturb u only never read dx / std_x
-bool u_noise_only(int model, int mode) {
-    if (mode == IRS_SMOOTH_ZERO_ORDER_B) return true;
-    bool contact = false;
-    IRS_DISPATCH_MODEL(model, { contact = !Model::HAS_JACOBIAN; });
-    return contact && mode == IRS_SMOOTH_FIRST_ORDER;
-}
-
-int fill_rng(int model, int mode, const double* std_x, const double* std_u, uint64_t seed, uint32_t iter,
-             uint64_t sample_offset, SmoothArgs& a) {
-    IRS_CHECK_ARG(std_u != nullptr, "std_u is null");
-    IRS_CHECK_ARG(std_x != nullptr || u_noise_only(model, mode), "std_x is null");
-    int n, m, np;
-    int rc = irs_model_info(model, &n, &m, &np);
-    if (rc != IRS_OK) return rc;
-    for (int i = 0; i < n; ++i) a.std[i] = std_x ? (float)std_x[i] : 0.f;
-    for (int j = 0; j < m; ++j) a.std[n + j] = (float)std_u[j];
-    a.seed = seed; a.iter = iter; a.sample_offset = sample_offset;
-    return IRS_OK;
-}
-
-int check_samples(const float* dx, const float* du, int model, int mode) {
-    IRS_CHECK_ARG(du != nullptr, "du is null");
-    IRS_CHECK_ARG(dx != nullptr || u_noise_only(model, mode), "dx is null");
-    IRS_CHECK_ARG((reinterpret_cast<uintptr_t>(dx) & 15) == 0 && (reinterpret_cast<uintptr_t>(du) & 15) == 0,
-                  "dx/du must be 16-byte aligned");
-    return IRS_OK;
-}
-
-// ---- B problems per launch --------------------------------------------------------------------------------
-size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
-
-// what the batched sample pass serves: what the uniform-geometry kernel serves (IRS_UG is read per call)
-int smooth_batch_supported(int model, int mode, int* n, int* m, int* np) {
-    const int rc = irs_model_info(model, n, m, np);
-    if (rc != IRS_OK) return rc;
-    return irs_smooth_ug_supported(model, mode) ? IRS_OK : IRS_ERR_UNSUPPORTED;
-}
-
 }  // namespace
 
-extern "C" {
+// ---- the launch interface (smooth_common.hpp): what smooth_api.hip calls once a call is checked and planned ----------
 
-size_t irs_smooth_batch_workspace_bytes(int model, int mode, int T, int N, int B) {
-    int n, m, np;
-    if (B <= 0 || smooth_batch_supported(model, mode, &n, &m, &np) != IRS_OK) return 0;
-    return (size_t)B * round256(irs_smooth_workspace_bytes(model, mode, T, N));
+int irs_smooth_launch(int model, int mode, const SmoothArgs& a, bool rng, bool fuse, hipStream_t st) {
+    int rc = IRS_ERR_UNSUPPORTED;
+    IRS_DISPATCH_MODEL(model, IRS_DISPATCH_MODE(mode, { launch_smooth_m<Model, MODE>(a, rng, fuse, st); rc = IRS_OK; }));
+    return rc;
 }
 
-int irs_smooth_batch_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(workspace != nullptr && workspace_bytes > 0, "no workspace");
-    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) { irs_set_error("irs_smooth_batch_workspace_init: %s", hipGetErrorString(e)); return IRS_ERR_HIP; }
-    return IRS_OK;
-}
-
-int irs_smooth_rng_batch(int model, const double* params, int n_params, int mode, int T, int N, int B,
-                         const double* x_trj, long long x_stride, const double* u_trj, long long u_stride,
-                         const double* std_u, const uint64_t* seed, uint32_t iter,
-                         double* sums, double* At, double* Bt, double* ct, int* info,
-                         void* workspace, size_t workspace_bytes, void* stream) {
-    // every argument error is decided before the first HIP call
-    IRS_CHECK_ARG(B > 0 && T > 0 && N > 0, "B, T and N must be positive");
-    IRS_CHECK_ARG((size_t)T * sizeof(int) <= kCounterBytes, "T too large for the arrival counters (max 1024)");
-    IRS_CHECK_ARG((long long)B * T <= 65535, "B * T beyond the grid's 65535 rows");
-    IRS_CHECK_ARG(x_trj && u_trj && std_u && seed && sums && At && Bt && ct && info, "null pointer");
-    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
-    int n = 0, m = 0, np = 0;
-    int rc = smooth_batch_supported(model, mode, &n, &m, &np);
-    if (rc != IRS_OK) {
-        irs_set_error("irs_smooth_rng_batch: model %d, mode %d: the batched sample pass serves the uniform-geometry kernel "
-                      "(IRS_MODEL_PLANAR_HAND_EXACT in IRS_SMOOTH_ZERO_ORDER_B and IRS_SMOOTH_FIRST_ORDER, IRS_UG not 0)",
-                      model, mode);
-        return IRS_ERR_UNSUPPORTED;
+// every registered model's (NX, NU) in turn; the macro's refusal of the first id past the last model ends the search
+int irs_rng_samples_launch(int n, int m, float* dx, float* du, const SmoothArgs& a, hipStream_t st) {
+    for (int model = 0;; ++model) {
+        IRS_DISPATCH_MODEL(model, {
+            if (Model::NX == n && Model::NU == m) {
+                hipLaunchKernelGGL((rng_samples_kernel<Model::NX, Model::NU>), dim3((a.N + 255) / 256, a.T), dim3(256), 0, st,
+                                   dx, du, a);
+                return IRS_OK;
+            }
+        });
     }
-    if (params == nullptr || n_params != np) {
-        irs_set_error("irs_smooth_rng_batch: model %d expects %d params, got %d", model, np, n_params);
-        return IRS_ERR_INVALID_ARG;
-    }
-    IRS_CHECK_ARG(x_stride >= (long long)T * n && u_stride >= (long long)T * m,
-                  "x_stride / u_stride shorter than a problem's T rows");
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    rc = irs_load_params(model, params, n_params, &a.p);
-    if (rc != IRS_OK) return rc;
-    SmoothGeometry g;
-    rc = smooth_geometry(model, mode, T, N, true, &g);
-    if (rc != IRS_OK) return rc;
-    const int P4 = (irs_sums_len(model, mode) + 3) / 4 * 4;
-    IRS_CHECK_ARG((size_t)T * g.nblk * P4 * sizeof(float) <= 0xffffffffull,
-                  "a problem's partial sums exceed the hand-off's 32-bit buffer size");
-    if (g.family != IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY) {
-        irs_set_error("irs_smooth_rng_batch: no batched kernel for the planned kernel family %d", g.family);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    // B slices of the single-problem layout, 256-byte aligned
-    const size_t stride = round256(irs_smooth_workspace_bytes(model, mode, T, N)), need = (size_t)B * stride;
-    if (workspace == nullptr || workspace_bytes < need) {
-        irs_set_error("irs_smooth_rng_batch: workspace %zu < %zu bytes (%d slices of %zu)", workspace_bytes, need, B, stride);
-        return IRS_ERR_WORKSPACE;
-    }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
-        irs_set_error("irs_smooth_rng_batch: the workspace must be 256-byte aligned");
-        return IRS_ERR_WORKSPACE;
-    }
-    // problem 0's arguments; the kernel's entry moves them to the row's problem (SmoothRow)
-    a.x_trj = x_trj; a.u_trj = u_trj;
-    a.T = T; a.N = N;
-    a.block = g.block; a.nblk = g.nblk; a.chunk0 = g.chunk0; a.chunk = g.chunk; a.wg0_rr = g.wg0_rr;
-    a.iter = iter;
-    a.diag = getenv("IRS_DIAG") ? atoi(getenv("IRS_DIAG")) : 0;      // timing experiments only, as the single entry
-    a.counters = static_cast<int*>(workspace);
-    a.fnom = reinterpret_cast<double*>(static_cast<char*>(workspace) + kCounterBytes);
-    a.partial = reinterpret_cast<float*>(static_cast<char*>(workspace) + kCounterBytes + fnom_bytes(T));
-    a.sums = sums; a.At = At; a.Bt = Bt; a.ct = ct; a.info = info;
-    a.n_total = (double)N;
-    const SmoothBatch bat{x_stride, u_stride, (long long)stride, reinterpret_cast<const unsigned long long*>(seed), std_u};
-    rc = irs_smooth_ug_launch_batch(model, mode, a, bat, B, static_cast<hipStream_t>(stream));
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
 }
 
-int irs_sums_len(int model, int mode) {
-    if (mode < 0 || mode > 2) { irs_set_error("irs_sums_len: unknown mode %d", mode); return IRS_ERR_INVALID_ARG; }
-    IRS_DISPATCH_MODEL(model, { return sums_len_m<Model>(mode); });
-    return IRS_ERR_UNSUPPORTED;
+int irs_smooth_finalize_launch(int model, int mode, const SmoothArgs& a, hipStream_t st) {
+    int rc = IRS_ERR_UNSUPPORTED;
+    IRS_DISPATCH_MODEL(model, IRS_DISPATCH_MODE(mode, {
+        hipLaunchKernelGGL((smooth_finalize_kernel<Model, MODE>), dim3(a.T), dim3(64), 0, st, a);
+        rc = IRS_OK;
+    }));
+    return rc;
 }
 
-size_t irs_smooth_workspace_bytes(int model, int mode, int T, int N) {
-    int P = irs_sums_len(model, mode);
-    if (P <= 0 || T <= 0 || N <= 0) return 0;
-    int chunk, nblk, block;
-    plan_grid(T, N, is_light(model, mode), /*rng=*/true, &chunk, &nblk, &block,       // the larger grid
-              has_nominal_in_wg0(model, mode));
-    if (irs_smooth_ug_supported(model, mode)) {
-        const int ug = irs_smooth_ug_nblk(T, N);
-        if (ug > nblk) nblk = ug;
-    }
-    return kCounterBytes + fnom_bytes(T) + (size_t)T * nblk * ((P + 3) / 4 * 4) * sizeof(float);
-}
-
-int irs_smooth_geometry(int model, int mode, int T, int N, int rng, int out[8]) {
-    IRS_CHECK_ARG(out != nullptr, "null pointer");
-    SmoothGeometry g;
-    int rc = smooth_geometry(model, mode, T, N, rng != 0, &g);
-    if (rc != IRS_OK) return rc;
-    out[0] = g.family; out[1] = g.block; out[2] = g.nblk; out[3] = g.chunk0; out[4] = g.chunk; out[5] = g.wg0_rr;
-    out[6] = g.branch; out[7] = 0;
-    return IRS_OK;
-}
-
-int irs_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(workspace != nullptr && workspace_bytes >= (size_t)kCounterBytes, "workspace too small");
-    hipError_t e = hipMemsetAsync(workspace, 0, kCounterBytes, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) { irs_set_error("irs_workspace_init: %s", hipGetErrorString(e)); return IRS_ERR_HIP; }
-    return IRS_OK;
-}
-
-int irs_smooth_accumulate(int model, const double* params, int n_params, int mode, int T, int N,
-                          const double* x_trj, const double* u_trj, const float* dx,
-                          const float* du, double* sums, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    int rc = check_samples(dx, du, model, mode);
-    if (rc != IRS_OK) return rc;
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dx = dx; a.du = du;
-    return smooth_common(model, params, n_params, mode, T, N, x_trj, u_trj, a, false, sums, nullptr,
-                         workspace, workspace_bytes, stream);
-}
-
-int irs_smooth_accumulate_rng(int model, const double* params, int n_params, int mode, int T, int N,
-                              const double* x_trj, const double* u_trj, const double* std_x,
-                              const double* std_u, uint64_t seed, uint32_t iter,
-                              uint64_t sample_offset, double* sums, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = fill_rng(model, mode, std_x, std_u, seed, iter, sample_offset, a);
-    if (rc != IRS_OK) return rc;
-    return smooth_common(model, params, n_params, mode, T, N, x_trj, u_trj, a, true, sums, nullptr,
-                         workspace, workspace_bytes, stream);
-}
-
-int irs_smooth(int model, const double* params, int n_params, int mode, int T, int N,
-               const double* x_trj, const double* u_trj, const float* dx, const float* du,
-               double* sums, double* At, double* Bt, double* ct, int* info, void* workspace,
-               size_t workspace_bytes, void* stream) {
-    int rc = check_samples(dx, du, model, mode);
-    if (rc != IRS_OK) return rc;
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dx = dx; a.du = du;
-    SmoothOut out{At, Bt, ct, info, (long long)N};
-    return smooth_common(model, params, n_params, mode, T, N, x_trj, u_trj, a, false, sums, &out,
-                         workspace, workspace_bytes, stream);
-}
-
-int irs_smooth_rng(int model, const double* params, int n_params, int mode, int T, int N,
-                   const double* x_trj, const double* u_trj, const double* std_x, const double* std_u,
-                   uint64_t seed, uint32_t iter, double* sums, double* At, double* Bt, double* ct,
-                   int* info, void* workspace, size_t workspace_bytes, void* stream) {
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = fill_rng(model, mode, std_x, std_u, seed, iter, 0, a);
-    if (rc != IRS_OK) return rc;
-    SmoothOut out{At, Bt, ct, info, (long long)N};
-    return smooth_common(model, params, n_params, mode, T, N, x_trj, u_trj, a, true, sums, &out,
-                         workspace, workspace_bytes, stream);
-}
-
-int irs_smooth_run(const irs_smooth_call* c, void* stream) {
-    IRS_CHECK_ARG(c != nullptr, "null call struct");
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc;
-    if (c->use_rng) {
-        rc = fill_rng(c->model, c->mode, c->std_x, c->std_u, c->seed, c->iter, c->sample_offset, a);
-    } else {
-        rc = check_samples(c->dx, c->du, c->model, c->mode);
-        a.dx = c->dx; a.du = c->du;
-    }
-    if (rc != IRS_OK) return rc;
-    SmoothOut out{c->At, c->Bt, c->ct, c->info, c->n_total};
-    return smooth_common(c->model, c->params, c->n_params, c->mode, c->T, c->N, c->x_trj, c->u_trj, a,
-                         c->use_rng != 0, c->sums, c->At ? &out : nullptr, c->workspace,
-                         c->workspace_bytes, stream);
-}
-
-int irs_rng_samples(int n, int m, int T, int N, const double* std_x, const double* std_u,
-                    uint64_t seed, uint32_t iter, uint64_t sample_offset, float* dx, float* du,
-                    void* stream) {
-    IRS_CHECK_ARG(T > 0 && N > 0 && dx && du && std_x && std_u, "bad argument");
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    for (int i = 0; i < n; ++i) a.std[i] = (float)std_x[i];
-    for (int j = 0; j < m; ++j) a.std[n + j] = (float)std_u[j];
-    a.seed = seed; a.iter = iter; a.sample_offset = sample_offset; a.T = T; a.N = N;
-    dim3 grid((N + 255) / 256, T), block(256);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 2 && m == 1) hipLaunchKernelGGL((rng_samples_kernel<2, 1>), grid, block, 0, st, dx, du, a);
-    else if (n == 12 && m == 4) hipLaunchKernelGGL((rng_samples_kernel<12, 4>), grid, block, 0, st, dx, du, a);
-    else if (n == 5 && m == 2) hipLaunchKernelGGL((rng_samples_kernel<5, 2>), grid, block, 0, st, dx, du, a);
-    else if (n == 6 && m == 2) hipLaunchKernelGGL((rng_samples_kernel<6, 2>), grid, block, 0, st, dx, du, a);
-    else if (n == 7 && m == 4) hipLaunchKernelGGL((rng_samples_kernel<7, 4>), grid, block, 0, st, dx, du, a);
-    else { irs_set_error("irs_rng_samples: unsupported (n,m)=(%d,%d)", n, m); return IRS_ERR_UNSUPPORTED; }
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-int irs_smooth_finalize(int model, const double* params, int n_params, int mode, int T,
-                        long long N_total, const double* x_trj, const double* u_trj,
-                        const double* sums, double* At, double* Bt, double* ct, int* info,
-                        void* stream) {
-    return irs_smooth_finalize_ws(model, params, n_params, mode, T, N_total, x_trj, u_trj, sums, At, Bt, ct, info,
-                                  nullptr, 0, stream);
-}
-
-int irs_smooth_finalize_ws(int model, const double* params, int n_params, int mode, int T,
-                           long long N_total, const double* x_trj, const double* u_trj,
-                           const double* sums, double* At, double* Bt, double* ct, int* info,
-                           const void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(T > 0 && N_total > 0, "T and N_total must be positive");
-    IRS_CHECK_ARG(workspace == nullptr || workspace_bytes >= (size_t)kCounterBytes + fnom_bytes(T),
-                  "workspace too small to hold the nominal steps");
-    IRS_CHECK_ARG(x_trj && u_trj && sums && At && Bt && ct && info, "null pointer");
-    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    int rc = irs_load_params(model, params, n_params, &a.p);
-    if (rc != IRS_OK) return rc;
-    a.x_trj = x_trj; a.u_trj = u_trj; a.sums = const_cast<double*>(sums);
-    a.At = At; a.Bt = Bt; a.ct = ct; a.info = info;
-    a.n_total = (double)N_total; a.T = T;
-    if (workspace != nullptr)
-        a.fnom = reinterpret_cast<double*>(static_cast<char*>(const_cast<void*>(workspace)) + kCounterBytes);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    IRS_DISPATCH_MODEL(model, { rc = launch_finalize<Model>(mode, a, st); });
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-int irs_exact_linearize(int model, const double* params, int n_params, int T, const double* x_trj,
-                        const double* u_trj, double* At, double* Bt, double* ct, void* stream) {
-    IRS_CHECK_ARG(T > 0 && x_trj && u_trj && At && Bt && ct, "bad argument");
-    ModelParams p;
-    int rc = irs_load_params(model, params, n_params, &p);
-    if (rc != IRS_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
+int irs_exact_linearize_launch(int model, const ModelParams& p, const double* x_trj, const double* u_trj, double* At,
+                               double* Bt, double* ct, int T, hipStream_t st) {
     IRS_DISPATCH_MODEL(model, {
-        hipLaunchKernelGGL((exact_linearize_kernel<Model>), dim3((T + 63) / 64), dim3(64), 0, st, p,
-                           x_trj, u_trj, At, Bt, ct, T);
+        hipLaunchKernelGGL((exact_linearize_kernel<Model>), dim3((T + 63) / 64), dim3(64), 0, st, p, x_trj, u_trj, At, Bt,
+                           ct, T);
     });
-    IRS_CHECK_LAUNCH();
     return IRS_OK;
 }
-
-}  // extern "C"

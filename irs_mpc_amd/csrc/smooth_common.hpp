@@ -49,6 +49,14 @@ struct SmoothBatch {
 };
 struct SmoothSolo {};
 
+// smooth.hip: the general sample pass, the stand-alone solve and their two companions.  Launches only: arguments are
+// checked and SmoothArgs is filled in smooth_api.hip.  IRS_ERR_UNSUPPORTED: no kernel for this model / mode / (n, m).
+int irs_smooth_launch(int model, int mode, const SmoothArgs& a, bool rng, bool fuse, hipStream_t st);
+int irs_smooth_finalize_launch(int model, int mode, const SmoothArgs& a, hipStream_t st);
+int irs_rng_samples_launch(int n, int m, float* dx, float* du, const SmoothArgs& a, hipStream_t st);
+int irs_exact_linearize_launch(int model, const ModelParams& p, const double* x_trj, const double* u_trj, double* At,
+                               double* Bt, double* ct, int T, hipStream_t st);
+
 // smooth_ug.hip: the uniform-geometry sample pass (exact 8-row contact models, u-only modes)
 bool irs_smooth_ug_supported(int model, int mode);
 int irs_smooth_ug_nblk(int T, int N);
@@ -59,10 +67,16 @@ int irs_smooth_ug_launch_batch(int model, int mode, const SmoothArgs& a, const S
 namespace {
 
 constexpr int kBlock = 256;
+constexpr int kBigBlock = 1024;       // light kernels on few supplied samples: one workgroup per timestep
 
-constexpr int kCounterBytes = 4096;   // head of the workspace: arrival counters
-// then T rows of f64 nominal steps (n <= 32)
-constexpr size_t fnom_bytes(int T) { return (size_t)T * 32 * sizeof(double); }
+// Runs BODY with `MODE` bound to the compile-time smoothing mode of a runtime `mode`; nothing for an unknown one.
+#define IRS_DISPATCH_MODE(mode, ...)                                                                      \
+    switch (mode) {                                                                                       \
+        case IRS_SMOOTH_ZERO_ORDER_AB: { constexpr int MODE = IRS_SMOOTH_ZERO_ORDER_AB; __VA_ARGS__; } break; \
+        case IRS_SMOOTH_FIRST_ORDER: { constexpr int MODE = IRS_SMOOTH_FIRST_ORDER; __VA_ARGS__; } break;     \
+        case IRS_SMOOTH_ZERO_ORDER_B: { constexpr int MODE = IRS_SMOOTH_ZERO_ORDER_B; __VA_ARGS__; } break;   \
+        default: break;                                                                                   \
+    }
 
 // models whose step is expensive and has no Jacobian (contact QPs): in the fused launch workgroup
 // 0 of every timestep takes fewer samples and evaluates the f64 nominal step the solve needs while
@@ -516,6 +530,22 @@ template <class Model>
 struct contact_rows_of<Model, std::void_t<decltype(Model::NC)>> { static constexpr int value = Model::NC; };
 template <class Model>
 constexpr int contact_rows() { return contact_rows_of<Model>::value; }
+
+// Which sample loop of smooth_kernel a (Model, MODE) compiles to -- read by the kernel and by the planner
+// (smooth_api.hip: smooth_geometry).
+// the parked-sample loop: exact contact models, u-only modes, at most 8 contact rows
+template <class Model, int MODE>
+constexpr bool defer_samples() {
+    return irs_contact_exact<Model>::value && MODE != IRS_SMOOTH_ZERO_ORDER_AB && contact_rows<Model>() <= 8;
+}
+// the matrix-core Gram loop (256-thread workgroups): zero-order, one 16-wide tile, too many statistics for registers
+template <class Model, int MODE>
+constexpr bool gram_on_matrix_cores() {
+    using TR = SmoothTraits<Model, MODE>;
+    return MODE == IRS_SMOOTH_ZERO_ORDER_AB && TR::d <= 16 && TR::n <= 16 && TR::PP > 64;
+}
+// the f64 nominal step of workgroup 0 costs its wave about this many sample trips (parked-sample kernels)
+constexpr int kNominalTrips = 2;
 
 
 // What every smoothing kernel does once its workgroup's per-wave partial statistics sit in `red` (NW rows of

@@ -167,42 +167,63 @@ class DeviceModel(CemModelFree):
             self._ws[key] = ws
         return ws
 
+    def _tv_shapes(self, lead, mode=None):
+        """The shapes of At, Bt, ct, info -- and of sums, given the mode -- behind the leading dimensions `lead`."""
+        shapes = dict(At=lead + (self.n, self.n), Bt=lead + (self.n, self.m), ct=lead + (self.n,), info=lead)
+        return shapes if mode is None else dict(sums=lead + (self.sums_len(mode),), **shapes)
+
+    @staticmethod
+    def _tv_alloc(shapes, device):
+        return {k: torch.empty(shape, dtype=torch.int32 if k == "info" else F64, device=device)
+                for k, shape in shapes.items()}
+
     def _tv_outputs(self, T, device, out):
         if out is not None:
             return out
-        return dict(sums=None,
-                    At=torch.empty((T, self.n, self.n), dtype=F64, device=device),
-                    Bt=torch.empty((T, self.n, self.m), dtype=F64, device=device),
-                    ct=torch.empty((T, self.n), dtype=F64, device=device),
-                    info=torch.empty((T,), dtype=torch.int32, device=device))
+        return dict(self._tv_alloc(self._tv_shapes((T,)), device), sums=None)
+
+    def smooth_call(self, mode, T, N, x_trj, u_trj, o, ws, dx=None, du=None, rng=None, n_total=None, sample_offset=0):
+        """The irs_smooth_call of one sample pass, for irs_smooth_run.  Samples supplied (dx, du) or, with
+        rng = (std_x, std_u, seed, iter), drawn on the device; o = dict(sums, At, Bt, ct, info) asks for the fused
+        solve, dict(sums) for the sums alone; ws = the workspace tensor; n_total (default N) = the samples per
+        timestep over all devices."""
+        c = _lib.SmoothCall()
+        self.fill_call(c)
+        c.mode, c.T, c.N = int(mode), int(T), int(N)
+        c.x_trj, c.u_trj = _ptr(x_trj, F64), _ptr(u_trj, F64)
+        if rng is not None:
+            std_x, std_u, seed, it = rng
+            c.use_rng, c.seed, c.sample_offset = 1, int(seed), int(sample_offset)
+            set_call_iter(c, it, std_x, std_u)
+        else:
+            c.dx, c.du = _ptr(dx, F32), _ptr(du, F32)
+        c.sums = _ptr(o["sums"], F64)
+        if "At" in o:
+            c.At, c.Bt, c.ct = (_ptr(o[k], F64) for k in ("At", "Bt", "ct"))
+            c.info = o["info"].data_ptr()
+        c.n_total = int(N if n_total is None else n_total)
+        c.workspace, c.workspace_bytes = ws.data_ptr(), ws.numel()
+        return c
+
+    def _smooth_run(self, mode, T, N, x_trj, u_trj, o, **samples):
+        """One irs_smooth_run into `o` (see smooth_call); a `sums` that is None is allocated."""
+        device = u_trj.device
+        if o["sums"] is None:
+            o["sums"] = torch.empty((T, self.sums_len(mode)), dtype=F64, device=device)
+        c = self.smooth_call(mode, T, N, x_trj, u_trj, o, self._workspace(mode, T, N, device), **samples)
+        check(self.lib.irs_smooth_run(ctypes.byref(c), _stream()), "irs_smooth_run")
+        return o
 
     def smooth(self, mode, x_trj, u_trj, dx, du, out=None):
         """Whole get_TV_matrices in one launch (single GPU), samples supplied.
         Returns dict(sums, At, Bt, ct, info); pass `out` (a previous result) to reuse buffers."""
         T, N = du.shape[0], du.shape[1]
-        o = self._tv_outputs(T, du.device, out)
-        if o["sums"] is None:
-            o["sums"] = torch.empty((T, self.sums_len(mode)), dtype=F64, device=du.device)
-        ws = self._workspace(mode, T, N, du.device)
-        check(self.lib.irs_smooth(self.model_id, self._p, self._np, mode, T, N, _ptr(x_trj, F64),
-                                  _ptr(u_trj, F64), _ptr(dx, F32), _ptr(du, F32), _ptr(o["sums"], F64),
-                                  _ptr(o["At"], F64), _ptr(o["Bt"], F64), _ptr(o["ct"], F64),
-                                  o["info"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "irs_smooth")
-        return o
+        return self._smooth_run(mode, T, N, x_trj, u_trj, self._tv_outputs(T, du.device, out), dx=dx, du=du)
 
     def smooth_rng(self, mode, x_trj, u_trj, N, std_x, std_u, seed, it, out=None):
         T = u_trj.shape[0]
-        o = self._tv_outputs(T, u_trj.device, out)
-        if o["sums"] is None:
-            o["sums"] = torch.empty((T, self.sums_len(mode)), dtype=F64, device=u_trj.device)
-        ws = self._workspace(mode, T, N, u_trj.device)
-        sx = dbl_array(std_x) if std_x is not None else None
-        check(self.lib.irs_smooth_rng(self.model_id, self._p, self._np, mode, T, N, _ptr(x_trj, F64),
-                                      _ptr(u_trj, F64), sx, dbl_array(std_u), int(seed), int(it),
-                                      _ptr(o["sums"], F64), _ptr(o["At"], F64), _ptr(o["Bt"], F64),
-                                      _ptr(o["ct"], F64), o["info"].data_ptr(), ws.data_ptr(), ws.numel(),
-                                      _stream()), "irs_smooth_rng")
-        return o
+        return self._smooth_run(mode, T, N, x_trj, u_trj, self._tv_outputs(T, u_trj.device, out),
+                                rng=(std_x, std_u, seed, it))
 
     # ---- B sample passes per launch ------------------------------------------
     def smooth_batch_supported(self, mode):
@@ -226,15 +247,8 @@ class DeviceModel(CemModelFree):
             assert B == 1 or t.stride(0) >= T * cols, (name, t.stride())
         assert tuple(std_u_dev.shape) == (B, self.m) and tuple(seed_dev.shape) == (B,) and seed_dev.dtype == torch.int64
         assert seed_dev.is_cuda and seed_dev.is_contiguous()
-        o = out
-        if o is None:
-            o = dict(sums=torch.empty((B, T, self.sums_len(mode)), dtype=F64, device=dev),
-                     At=torch.empty((B, T, self.n, self.n), dtype=F64, device=dev),
-                     Bt=torch.empty((B, T, self.n, self.m), dtype=F64, device=dev),
-                     ct=torch.empty((B, T, self.n), dtype=F64, device=dev),
-                     info=torch.empty((B, T), dtype=torch.int32, device=dev))
-        shapes = dict(sums=(B, T, self.sums_len(mode)), At=(B, T, self.n, self.n), Bt=(B, T, self.n, self.m),
-                      ct=(B, T, self.n), info=(B, T))
+        shapes = self._tv_shapes((B, T), mode)
+        o = out if out is not None else self._tv_alloc(shapes, dev)
         for name, shape in shapes.items():
             assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
         assert o["info"].dtype == torch.int32 and o["info"].is_contiguous()
@@ -561,27 +575,12 @@ class DeviceModel(CemModelFree):
     def smooth_accumulate(self, mode, x_trj, u_trj, dx, du, sums=None):
         """Sample pass on supplied samples: dx (T,N,n) f32 (None for ZERO_ORDER_B), du (T,N,m) f32."""
         T, N = du.shape[0], du.shape[1]
-        if sums is None:
-            sums = torch.empty((T, self.sums_len(mode)), dtype=F64, device=du.device)
-        ws = self._workspace(mode, T, N, du.device)
-        check(self.lib.irs_smooth_accumulate(self.model_id, self._p, self._np, mode, T, N,
-                                             _ptr(x_trj, F64), _ptr(u_trj, F64), _ptr(dx, F32), _ptr(du, F32),
-                                             _ptr(sums, F64), ws.data_ptr(), ws.numel(), _stream()),
-              "irs_smooth_accumulate")
-        return sums
+        return self._smooth_run(mode, T, N, x_trj, u_trj, dict(sums=sums), dx=dx, du=du)["sums"]
 
     def smooth_accumulate_rng(self, mode, x_trj, u_trj, N, std_x, std_u, seed, it, sample_offset=0, sums=None):
         T = u_trj.shape[0]
-        if sums is None:
-            sums = torch.empty((T, self.sums_len(mode)), dtype=F64, device=u_trj.device)
-        ws = self._workspace(mode, T, N, u_trj.device)
-        sx = dbl_array(std_x) if std_x is not None else None
-        check(self.lib.irs_smooth_accumulate_rng(self.model_id, self._p, self._np, mode, T, N,
-                                                 _ptr(x_trj, F64), _ptr(u_trj, F64), sx, dbl_array(std_u),
-                                                 int(seed), int(it), int(sample_offset), _ptr(sums, F64),
-                                                 ws.data_ptr(), ws.numel(), _stream()),
-              "irs_smooth_accumulate_rng")
-        return sums
+        return self._smooth_run(mode, T, N, x_trj, u_trj, dict(sums=sums), rng=(std_x, std_u, seed, it),
+                                sample_offset=sample_offset)["sums"]
 
     def rng_samples(self, T, N, std_x, std_u, seed, it, sample_offset=0):
         dev = require_gpu()
@@ -635,6 +634,17 @@ class DeviceModel(CemModelFree):
         return x_new, u_new, cost
 
 
+def set_call_iter(c, it, std_x, std_u):
+    """The iteration number and the standard deviations of an irs_smooth_call that draws on the device (std_x None:
+    left as it is -- zero in a fresh call, which is what the u-only modes read)."""
+    c.iter = int(it)
+    if std_x is not None:
+        for i, v in enumerate(std_x):
+            c.std_x[i] = float(v)
+    for i, v in enumerate(std_u):
+        c.std_u[i] = float(v)
+
+
 class SmoothPlan:
     """A pre-marshalled get_TV_matrices call (irs_smooth_call): `run()` is ONE FFI call
     that enqueues ONE kernel (fused path) and touches no Python-side allocation.
@@ -648,36 +658,17 @@ class SmoothPlan:
         self.dm, self.mode = dm, mode
         T = u_trj.shape[0]
         device = u_trj.device
-        c = _lib.SmoothCall()
-        dm.fill_call(c)
-        c.mode, c.T = mode, T
-        if rng is not None:
-            N = int(rng["N"])
-            c.use_rng = 1
-            c.seed, c.sample_offset = int(rng["seed"]), int(sample_offset)
-            self.set_iter(rng.get("iter", 1), rng.get("std_x"), rng["std_u"], call=c)
-        else:
-            N = du.shape[1]
-            c.use_rng = 0
-            c.dx, c.du = _ptr(dx, F32), _ptr(du, F32)
-        c.N = N
-        self.N = N
+        self.N = N = int(rng["N"]) if rng is not None else du.shape[1]
         self.sums = torch.empty((T, dm.sums_len(mode)), dtype=F64, device=device)
-        c.sums = self.sums.data_ptr()
-        self.out = None
-        if fuse:
-            self.out = dm._tv_outputs(T, device, None)
-            self.out["sums"] = self.sums
-            c.At, c.Bt, c.ct = (self.out[k].data_ptr() for k in ("At", "Bt", "ct"))
-            c.info = self.out["info"].data_ptr()
-        c.n_total = int(n_total if n_total is not None else N)
+        self.out = dict(dm._tv_outputs(T, device, None), sums=self.sums) if fuse else None
         self.ws = dm._workspace(mode, T, N, device)
-        c.workspace, c.workspace_bytes = self.ws.data_ptr(), self.ws.numel()
-        self.call = c
+        drawn = None if rng is None else (rng.get("std_x"), rng["std_u"], rng["seed"], rng.get("iter", 1))
+        self.call = dm.smooth_call(mode, T, N, x_trj, u_trj, self.out or dict(sums=self.sums), self.ws, dx=dx, du=du,
+                                   rng=drawn, n_total=n_total, sample_offset=sample_offset)
         self._keep = (dx, du)
-        self.set_trajectory(x_trj, u_trj)
+        self._xu = (x_trj, u_trj)
         self._fn = dm.lib.irs_smooth_run
-        self._ref = ctypes.byref(c)
+        self._ref = ctypes.byref(self.call)
 
     def set_trajectory(self, x_trj, u_trj):
         self._xu = (x_trj, u_trj)
@@ -687,14 +678,8 @@ class SmoothPlan:
         self._keep = (dx, du)
         self.call.dx, self.call.du = _ptr(dx, F32), _ptr(du, F32)
 
-    def set_iter(self, it, std_x, std_u, call=None):
-        c = call if call is not None else self.call
-        c.iter = int(it)
-        if std_x is not None:
-            for i, v in enumerate(std_x):
-                c.std_x[i] = float(v)
-        for i, v in enumerate(std_u):
-            c.std_u[i] = float(v)
+    def set_iter(self, it, std_x, std_u):
+        set_call_iter(self.call, it, std_x, std_u)
 
     def run(self, stream=None):
         rc = self._fn(self._ref, _stream() if stream is None else stream)

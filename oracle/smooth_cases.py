@@ -12,18 +12,18 @@ of the wave reads sample start + l), so ownership is stated per wave slot:
                               whose lanes load the clamped row s_end - 1 and must contribute nothing
 
 The five loops (line numbers: the kernels as of this file's commit):
-  * lanes, light, samples supplied (smooth.hip:377-410, U = 4): lane tid of workgroup b starts at s_begin + tid and
+  * lanes, light, samples supplied (smooth.hip:365-398, U = 4): lane tid of workgroup b starts at s_begin + tid and
     strides by 4 BLOCK; slot uu of a trip is sample s0 + uu BLOCK, valid while < s_end, else clamped and zeroed;
-  * lanes, one sample per trip (smooth.hip:377, U = 1: heavy kernels, and light ones with device-drawn samples):
-    s_begin + tid + k BLOCK, the next row prefetched (smooth.hip:362-375);
-  * matrix-core Gram (smooth.hip:107-109): wave w takes s_begin + 64 w + k BLOCK, lane l its sample l;
-  * contact, wave-dealt (smooth.hip:350-358 next_s0; smooth.hip:222-225 block_of with the parked-sample ring): trip k
+  * lanes, one sample per trip (smooth.hip:365, U = 1: heavy kernels, and light ones with device-drawn samples):
+    s_begin + tid + k BLOCK, the next row prefetched (smooth.hip:350-363);
+  * matrix-core Gram (smooth.hip:95-97): wave w takes s_begin + 64 w + k BLOCK, lane l its sample l;
+  * contact, wave-dealt (smooth.hip:338-346 next_s0; smooth.hip:210-213 block_of with the parked-sample ring): trip k
     of wave w takes 64-sample block 4 k + w of the workgroup; in workgroup 0 the last wave sits out after wg0_rr
     trips and the other three take blocks 4 rr + 3 (k - rr) + w;
   * uniform geometry (smooth_ug.hip:624-628): the V = 8 nblk waves of a timestep are numbered `me` -- workgroup 0's
     waves 0..6, then 8 b - 1 + w, the nominal wave (workgroup 0, wave 7) last -- and block_of(k) deals rounds 0, 1 to
     all but the nominal wave and every later round to all V.
-Workgroup b of the first four families owns [s_begin, s_end) = chunk0 + [(b-1) chunk, b chunk) cut at N (smooth.hip:90-91).
+Workgroup b of the first four families owns [s_begin, s_end) = chunk0 + [(b-1) chunk, b chunk) cut at N (smooth.hip:78-79).
 """
 import numpy as np
 
@@ -45,7 +45,7 @@ MODELS = {
 
 
 def wg_ranges(geom, N):
-    """[s_begin, s_end) of every workgroup of a timestep (smooth.hip:90-91); the uniform-geometry family has none."""
+    """[s_begin, s_end) of every workgroup of a timestep (smooth.hip:78-79); the uniform-geometry family has none."""
     b = np.arange(geom["nblk"])
     beg = np.where(b == 0, 0, geom["chunk0"] + (b - 1) * geom["chunk"])
     end = np.minimum(N, np.where(b == 0, geom["chunk0"], geom["chunk0"] + b * geom["chunk"]))
