@@ -31,7 +31,38 @@ class CemParameters:
         self.device_seed = None     # int: draw the candidates on the device (not a reference field)
 
 
-class CrossEntropyMethod:
+class CemDescent:
+    """What CrossEntropyMethod and CrossEntropyMethodQuasistatic share: one descent and, with device_seed, the head
+    of `iterate`.  The host class has batch_size, n_elite, T, dim_u, std_trj, device_seed, _dm and the device copies
+    _x0, _Q, _R, _xd; `it` is its iteration counter, Qd (a device tensor) asks for the quasistatic cost."""
+
+    def _cem_descent(self, u_trj, it, Qd=None):
+        """Candidate source -> costs -> elites and refit -> the mean's rollout -> std_trj; returns (x_mean, u_mean).
+        The source is the reference's host draw or, with device_seed, the stream of (device_seed, it): no candidate
+        tensor.  cost_array and elite_idx stay behind as attributes."""
+        if self.device_seed is None:
+            src = dev.CemSource.supplied(dev.to_dev(np.random.normal(u_trj, self.std_trj,
+                                                                     (self.batch_size, self.T, self.dim_u))))
+        else:
+            src = dev.CemSource.drawn(dev.to_dev(np.asarray(u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float)),
+                                      self.batch_size, self.device_seed, it)
+        self.cost_array = self._dm.cem_costs(src, self._x0, self._Q, self._R, self._xd, Qd=Qd)
+        self.elite_idx, u_mean, u_std = self._dm.cem_refit_from(src, self.cost_array, self.n_elite)
+        x_mean, _ = self._dm.rollout_cost(self._x0, u_mean, self._Q, self._R, self._xd)
+        self.std_trj = u_std.cpu().numpy()
+        return x_mean.cpu().numpy(), u_mean.cpu().numpy()
+
+    def _cem_iterate_histories(self, max_iterations, it, Qd=None):
+        """The descents the host loop would run from iteration `it`, through ONE cem_iterate call and one read-back:
+        (their number k, the histories of DeviceModel.cem_iterate as NumPy arrays)."""
+        k = max(1, max_iterations - it + 2)
+        o = self._dm.cem_iterate(dev.to_dev(np.asarray(self.u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float)),
+                                 self._x0, self._Q, Qd, self._R, self._xd, self.batch_size, self.n_elite, k,
+                                 self.device_seed, it, quasistatic=Qd is not None)
+        return k, {key: v.cpu().numpy() for key, v in o.items()}
+
+
+class CrossEntropyMethod(CemDescent):
     check_valid_system = IrsLqr.check_valid_system
     check_valid_params = IrsLqr.check_valid_params
 
@@ -69,42 +100,19 @@ class CrossEntropyMethod:
 
     def local_descent(self, x_trj, u_trj):
         """cem.py:151-184: sample, price, keep the elites, refit mean and std."""
-        if self.device_seed is not None:
-            return self._local_descent_drawn(u_trj)
-        candidates = dev.to_dev(np.random.normal(u_trj, self.std_trj, (self.batch_size, self.T, self.dim_u)))
-        self.cost_array = self._dm.cem_rollout_costs(candidates, self._x0, self._Q, self._R, self._xd)
-        self.elite_idx, u_mean, u_std = self._dm.cem_refit(candidates, self.cost_array, self.n_elite)
-        x_mean, _ = self._dm.rollout_cost(self._x0, u_mean, self._Q, self._R, self._xd)
-        self.std_trj = u_std.cpu().numpy()
-        return x_mean.cpu().numpy(), u_mean.cpu().numpy()
-
-    def _local_descent_drawn(self, u_trj):
-        """local_descent on the candidate stream of (device_seed, self.iter): no candidate tensor."""
-        mean, std = dev.to_dev(np.asarray(u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float))
-        self.cost_array = self._dm.cem_rollout_costs_drawn(mean, std, self.batch_size, self.device_seed, self.iter,
-                                                           self._x0, self._Q, self._R, self._xd)
-        self.elite_idx, u_mean, u_std = self._dm.cem_refit_drawn(mean, std, self.device_seed, self.iter,
-                                                                 self.cost_array, self.n_elite)
-        x_mean, _ = self._dm.rollout_cost(self._x0, u_mean, self._Q, self._R, self._xd)
-        self.std_trj = u_std.cpu().numpy()
-        return x_mean.cpu().numpy(), u_mean.cpu().numpy()
+        return self._cem_descent(u_trj, self.iter)
 
     def _iterate_drawn(self, max_iterations):
         """The loop below through ONE irs_cem_iterate call: every descent enqueued back to back, one read-back."""
-        k = max(1, max_iterations - self.iter + 2)          # descents the host loop would run from self.iter
-        o = self._dm.cem_iterate(dev.to_dev(np.asarray(self.u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float)),
-                                 self._x0, self._Q, None, self._R, self._xd, self.batch_size, self.n_elite, k,
-                                 self.device_seed, self.iter)
-        x_hist, u_hist, std_hist, cost_hist = (o[key].cpu().numpy() for key in ("x_hist", "u_hist", "std_hist",
-                                                                                "cost_hist"))
+        k, h = self._cem_iterate_histories(max_iterations, self.iter)
         for i in range(k):
-            x_new, u_new, cost_new = x_hist[i], u_hist[i], float(cost_hist[i])
+            x_new, u_new, cost_new = h["x_hist"][i], h["u_hist"][i], float(h["cost_hist"][i])
             if self.verbose:
                 print("Iteration: {:02d}  ||  Current Cost: {:05f}  ||  Elapsed time: {:05f} ".format(
                     self.iter, cost_new, time.time() - self.start_time))
             for log, item in ((self.x_trj_lst, x_new), (self.u_trj_lst, u_new), (self.cost_lst, cost_new)):
                 log.append(item)
-            self.std_trj = std_hist[i]
+            self.std_trj = h["std_hist"][i]
             if i == k - 1:
                 return self.x_trj, self.u_trj, self.cost
             self.cost, self.x_trj, self.u_trj = cost_new, x_new, u_new

@@ -19,7 +19,7 @@ import time
 
 import numpy as np
 
-from . import device as dev
+from .cem import CemDescent
 from .quasistatic_base import QuasistaticOptimizerBase
 
 
@@ -34,7 +34,7 @@ class CemQuasistaticParameters:
         self.device_seed = None     # int: draw the candidates on the device (not a reference field)
 
 
-class CrossEntropyMethodQuasistatic(QuasistaticOptimizerBase):
+class CrossEntropyMethodQuasistatic(CemDescent, QuasistaticOptimizerBase):
     def __init__(self, q_dynamics, params):
         goal = getattr(params, "x_trj_d", None)
         self._setup(q_dynamics, params, params.xd_trj if goal is None else goal)
@@ -44,27 +44,7 @@ class CrossEntropyMethodQuasistatic(QuasistaticOptimizerBase):
 
     def local_descent(self, x_trj, u_trj):
         """cem_quasistatic.py:168-211: sample, price, keep the elites, refit mean and std."""
-        if self.device_seed is not None:
-            return self._local_descent_drawn(u_trj)
-        candidates = dev.to_dev(np.random.normal(u_trj, self.std_trj, (self.batch_size, self.T, self.dim_u)))
-        self.cost_array = self._dm.cem_rollout_costs_quasistatic(candidates, self._x0, self._Q, self._Qd, self._R,
-                                                                 self._xd)
-        self.elite_idx, u_mean, u_std = self._dm.cem_refit(candidates, self.cost_array, self.n_elite)
-        x_mean, _ = self._dm.rollout_cost(self._x0, u_mean, self._Q, self._R, self._xd)
-        self.std_trj = u_std.cpu().numpy()
-        return x_mean.cpu().numpy(), u_mean.cpu().numpy()
-
-    def _local_descent_drawn(self, u_trj):
-        """local_descent on the candidate stream of (device_seed, self.current_iter): no candidate tensor."""
-        mean, std = dev.to_dev(np.asarray(u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float))
-        it = self.current_iter
-        self.cost_array = self._dm.cem_rollout_costs_quasistatic_drawn(mean, std, self.batch_size, self.device_seed, it,
-                                                                       self._x0, self._Q, self._Qd, self._R, self._xd)
-        self.elite_idx, u_mean, u_std = self._dm.cem_refit_drawn(mean, std, self.device_seed, it, self.cost_array,
-                                                                 self.n_elite)
-        x_mean, _ = self._dm.rollout_cost(self._x0, u_mean, self._Q, self._R, self._xd)
-        self.std_trj = u_std.cpu().numpy()
-        return x_mean.cpu().numpy(), u_mean.cpu().numpy()
+        return self._cem_descent(u_trj, self.current_iter, Qd=self._Qd)
 
     def iterate(self, max_iterations):
         """QuasistaticOptimizerBase.iterate; with device_seed set, through ONE irs_cem_iterate call: every descent
@@ -72,18 +52,14 @@ class CrossEntropyMethodQuasistatic(QuasistaticOptimizerBase):
         descent logged but not adopted)."""
         if self.device_seed is None:
             return super().iterate(max_iterations)
-        k = max(1, max_iterations - self.current_iter + 2)  # descents the host loop would run from current_iter
-        o = self._dm.cem_iterate(dev.to_dev(np.asarray(self.u_trj, float)), dev.to_dev(np.asarray(self.std_trj, float)),
-                                 self._x0, self._Q, self._Qd, self._R, self._xd, self.batch_size, self.n_elite, k,
-                                 self.device_seed, self.current_iter, quasistatic=True)
-        x_hist, u_hist, std_hist = (o[key].cpu().numpy() for key in ("x_hist", "u_hist", "std_hist"))
+        k, h = self._cem_iterate_histories(max_iterations, self.current_iter, Qd=self._Qd)
         for i in range(k):
             if self.verbose:
                 print("Iter {:02d}, cost: {:0.4f}. time: {:0.2f}.".format(self.current_iter, self.cost,
                                                                         time.time() - self.start_time))
-            x_new, u_new = x_hist[i], u_hist[i]
+            x_new, u_new = h["x_hist"][i], h["u_hist"][i]
             cost_new = self._log(x_new, u_new)
-            self.std_trj = std_hist[i]
+            self.std_trj = h["std_hist"][i]
             if self.publish_every_iteration:
                 self.q_dynamics.publish_trajectory(x_new)
             if i == k - 1:

@@ -22,7 +22,11 @@
 // Model-free form (irs_cem_values_stage[_drawn]): for a system that is a torch callable, step 1 is T + 1 launches of
 // cem_values_stage_kernel -- the time-loop body of cem_rollout_kernel without the dynamics -- with the callable
 // stepping all B states between them; steps 2-3 are the kernels above, which never see a Model.
+//
+// This file holds the kernels and, at its end, the launches cem.hpp declares; the extern "C" entries and their checks
+// are cem_api.hip.
 #include "boxqp.hpp"      // has_u_into_x
+#include "cem.hpp"
 #include "philox.hpp"
 
 namespace {
@@ -200,7 +204,6 @@ __global__ __launch_bounds__(64) void cem_rollout_quasistatic_kernel(ModelParams
 // Eight bytes a lane, not sixteen: the range starts at row b0 of a tensor the C ABI only knows to be 8-byte aligned,
 // and the stage is bound by its launch, not its loads (B (n + m + 2) doubles: 1.6 MB at B = 50 000, n = 2, m = 1).
 constexpr int kStageBlock = 128;
-constexpr int kStageMaxN = 32, kStageMaxM = 16;      // torch_system.MAX_DIM_X / MAX_DIM_U
 
 __host__ __device__ constexpr int stage_pitch(int w) { return w | 1; }
 
@@ -481,17 +484,16 @@ __global__ __launch_bounds__(256) void cem_candidates_kernel(CemDrawn src, int m
     u_cand[i] = src.at(m, b, q / m, q % m);
 }
 
-// [a, a + len) and [b, b + len) share an element
-bool overlap(const double* a, const double* b, size_t len) { return a < b + len && b < a + len; }
+// ---- the launches of cem.hpp: a CemSource becomes the Src its kernels are compiled for, here and nowhere else ----
+CemDrawn drawn(const CemSource& s) { return {s.mean, s.std, s.seed, s.sample_offset, s.iter}; }
 
-constexpr size_t round256(size_t v) { return (v + 255) / 256 * 256; }
+// f(CemSupplied) or f(CemDrawn)
+template <class F>
+auto with_source(const CemSource& s, F f) {
+    if (!s.drawn) return f(CemSupplied{s.u_cand});
+    return f(drawn(s));
+}
 
-// Which cost a rollout prices its candidates with: CrossEntropyMethod's (cem_rollout_kernel) or IrsLqrQuasistatic's
-// (cem_rollout_quasistatic_kernel: needs Qd and a position-controlled model).
-enum class CemCost { Plain, Quasistatic };
-
-// Src = CemSupplied or CemDrawn.  Qd is read by the quasistatic cost only.  IRS_ERR_UNSUPPORTED (nothing launched) when
-// the quasistatic cost is asked of a model that is not position controlled.
 template <CemCost COST, class Src>
 int launch_rollout(int model, const ModelParams& p, int T, int B, const Src& src, const double* x0, const double* Q,
                    const double* Qd, const double* R, const double* xd_trj, double* costs, hipStream_t st) {
@@ -511,238 +513,41 @@ int launch_rollout(int model, const ModelParams& p, int T, int B, const Src& src
     return rc;
 }
 
-// IRS_OK for a position-controlled model, else IRS_ERR_UNSUPPORTED
-int position_controlled(int model) {
-    int rc = IRS_ERR_UNSUPPORTED;
-    IRS_DISPATCH_MODEL(model, {
-        if (has_u_into_x<Model>::value) rc = IRS_OK;
-    });
-    return rc;
-}
-
-// What both stage entries refuse, before any HIP call; nullptr if the sizes and the shared pointers are fine.
-const char* stage_argument_error(int n, int m, int T, int B, int t, const double* x, const double* Q, const double* R,
-                                 const double* xd_trj, const double* u_t, const double* costs) {
-    if (n < 1 || n > kStageMaxN) return "n must be in 1..32";
-    if (m < 1 || m > kStageMaxM) return "m must be in 1..16";
-    if (T <= 0 || B <= 0) return "T and B must be positive";
-    if (t < 0 || t > T) return "t must be in 0..T";
-    if (!x || !Q || !R || !xd_trj || !costs) return "null pointer";
-    if (t < T && !u_t) return "u_t is null at a stage t < T";
-    return nullptr;
-}
-
-template <class Src>
-void launch_stage(int n, int m, int T, int B, int t, const Src& src, const double* x, const double* Q, const double* R,
-                  const double* xd_trj, double* u_t, double* costs, hipStream_t st) {
-    hipLaunchKernelGGL((cem_values_stage_kernel<Src>), dim3((B + kStageBlock - 1) / kStageBlock), dim3(kStageBlock),
-                       stage_lds_bytes(n, m), st, n, m, T, B, t, src, x, Q, R, xd_trj, u_t, costs);
-}
-
-void launch_refit_drawn(int T, int m, int B, int n_elite, const CemDrawn& src, const double* costs, int* elite_idx,
-                        double* u_new, double* std_new, hipStream_t st) {
-    hipLaunchKernelGGL(cem_select_kernel, dim3(1), dim3(kSelBlock), 0, st, costs, B, n_elite, elite_idx);
-    const int Tm = T * m;
-    hipLaunchKernelGGL(cem_refit_drawn_kernel, dim3((Tm + 63) / 64), dim3(64 * kRefitWaves), 0, st, src, m, elite_idx,
-                       n_elite, Tm, u_new, std_new);
-}
-
 }  // namespace
 
-extern "C" {
-
-int irs_cem_rollout_costs(int model, const double* params, int n_params, int T, int B,
-                          const double* u_cand, const double* x0, const double* Q, const double* R,
-                          const double* xd_trj, double* costs, void* stream) {
-    IRS_CHECK_ARG(T > 0 && B > 0 && u_cand && x0 && Q && R && xd_trj && costs, "bad argument");
-    ModelParams p;
-    int rc = irs_load_params(model, params, n_params, &p);
-    if (rc != IRS_OK) return rc;
-    rc = launch_rollout<CemCost::Plain>(model, p, T, B, CemSupplied{u_cand}, x0, Q, nullptr, R, xd_trj, costs,
-                                        static_cast<hipStream_t>(stream));
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
+int irs_cem_launch_rollout(CemCost cost, int model, const ModelParams& p, int T, int B, const CemSource& src,
+                           const double* x0, const double* Q, const double* Qd, const double* R, const double* xd_trj,
+                           double* costs, hipStream_t st) {
+    return with_source(src, [&](const auto& s) {
+        return cost == CemCost::Plain
+                   ? launch_rollout<CemCost::Plain>(model, p, T, B, s, x0, Q, nullptr, R, xd_trj, costs, st)
+                   : launch_rollout<CemCost::Quasistatic>(model, p, T, B, s, x0, Q, Qd, R, xd_trj, costs, st);
+    });
 }
 
-int irs_cem_rollout_costs_quasistatic(int model, const double* params, int n_params, int T, int B,
-                                      const double* u_cand, const double* x0, const double* Q,
-                                      const double* Qd, const double* R, const double* xd_trj, double* costs,
-                                      void* stream) {
-    IRS_CHECK_ARG(T > 0 && B > 0 && u_cand && x0 && Q && Qd && R && xd_trj && costs, "bad argument");
-    ModelParams p;
-    int rc = irs_load_params(model, params, n_params, &p);
-    if (rc != IRS_OK) return rc;
-    rc = launch_rollout<CemCost::Quasistatic>(model, p, T, B, CemSupplied{u_cand}, x0, Q, Qd, R, xd_trj, costs,
-                                              static_cast<hipStream_t>(stream));
-    if (rc != IRS_OK) {
-        irs_set_error("irs_cem_rollout_costs_quasistatic: model %d is not position controlled", model);
-        return rc;
-    }
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-int irs_cem_refit(int T, int m, int B, int n_elite, const double* u_cand, const double* costs,
-                  int* elite_idx, double* u_new, double* std_new, void* stream) {
-    IRS_CHECK_ARG(T > 0 && m > 0 && B > 0 && n_elite > 0 && n_elite <= B, "need 0 < n_elite <= B");
-    IRS_CHECK_ARG(u_cand && costs && elite_idx && u_new && std_new, "null pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+void irs_cem_launch_refit(int T, int m, int B, int n_elite, const CemSource& src, const double* costs, int* elite_idx,
+                          double* u_new, double* std_new, hipStream_t st) {
     hipLaunchKernelGGL(cem_select_kernel, dim3(1), dim3(kSelBlock), 0, st, costs, B, n_elite, elite_idx);
-    IRS_CHECK_LAUNCH();
     const int Tm = T * m;
-    hipLaunchKernelGGL(cem_refit_kernel, dim3((Tm + 63) / 64), dim3(64 * kRefitWaves), 0, st, u_cand, elite_idx, n_elite,
-                       Tm, u_new, std_new);
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
+    const dim3 grid((Tm + 63) / 64), block(64 * kRefitWaves);
+    if (src.drawn)
+        hipLaunchKernelGGL(cem_refit_drawn_kernel, grid, block, 0, st, drawn(src), m, elite_idx, n_elite, Tm, u_new,
+                           std_new);
+    else
+        hipLaunchKernelGGL(cem_refit_kernel, grid, block, 0, st, src.u_cand, elite_idx, n_elite, Tm, u_new, std_new);
 }
 
-// ---- device-resident form: candidates drawn in the kernels ---------------------------------------------------
-
-int irs_cem_candidates(int T, int m, int B, const double* u_mean, const double* std, uint64_t seed, uint32_t iter,
-                       uint64_t sample_offset, double* u_cand, void* stream) {
-    IRS_CHECK_ARG(T > 0 && m > 0 && B > 0, "sizes must be positive");
-    IRS_CHECK_ARG(u_mean && std && u_cand, "null pointer");
-    const size_t total = (size_t)B * T * m;
-    IRS_CHECK_ARG((total + 255) / 256 <= 0x7fffffffull, "B T m too large for one launch");
-    const CemDrawn src{u_mean, std, seed, sample_offset, iter};
-    hipLaunchKernelGGL(cem_candidates_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), src, m, T * m, total, u_cand);
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
+void irs_cem_launch_stage(int n, int m, int T, int B, int t, const CemSource& src, const double* x, const double* Q,
+                          const double* R, const double* xd_trj, double* u_t, double* costs, hipStream_t st) {
+    with_source(src, [&](const auto& s) {
+        using Src = std::decay_t<decltype(s)>;
+        hipLaunchKernelGGL((cem_values_stage_kernel<Src>), dim3((B + kStageBlock - 1) / kStageBlock), dim3(kStageBlock),
+                           stage_lds_bytes(n, m), st, n, m, T, B, t, s, x, Q, R, xd_trj, u_t, costs);
+    });
 }
 
-int irs_cem_rollout_costs_drawn(int model, const double* params, int n_params, int T, int B, const double* u_mean,
-                                const double* std, uint64_t seed, uint32_t iter, uint64_t sample_offset,
-                                const double* x0, const double* Q, const double* R, const double* xd_trj,
-                                double* costs, void* stream) {
-    IRS_CHECK_ARG(T > 0 && B > 0 && u_mean && std && x0 && Q && R && xd_trj && costs, "bad argument");
-    ModelParams p;
-    int rc = irs_load_params(model, params, n_params, &p);
-    if (rc != IRS_OK) return rc;
-    rc = launch_rollout<CemCost::Plain>(model, p, T, B, CemDrawn{u_mean, std, seed, sample_offset, iter}, x0, Q, nullptr, R,
-                                        xd_trj, costs, static_cast<hipStream_t>(stream));
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
+void irs_cem_launch_candidates(int T, int m, size_t total, const CemSource& src, double* u_cand, hipStream_t st) {
+    hipLaunchKernelGGL(cem_candidates_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, drawn(src), m,
+                       T * m, total, u_cand);
 }
 
-int irs_cem_rollout_costs_quasistatic_drawn(int model, const double* params, int n_params, int T, int B,
-                                            const double* u_mean, const double* std, uint64_t seed, uint32_t iter,
-                                            uint64_t sample_offset, const double* x0, const double* Q,
-                                            const double* Qd, const double* R, const double* xd_trj, double* costs,
-                                            void* stream) {
-    IRS_CHECK_ARG(T > 0 && B > 0 && u_mean && std && x0 && Q && Qd && R && xd_trj && costs, "bad argument");
-    ModelParams p;
-    int rc = irs_load_params(model, params, n_params, &p);
-    if (rc != IRS_OK) return rc;
-    rc = launch_rollout<CemCost::Quasistatic>(model, p, T, B, CemDrawn{u_mean, std, seed, sample_offset, iter}, x0, Q, Qd,
-                                              R, xd_trj, costs, static_cast<hipStream_t>(stream));
-    if (rc != IRS_OK) {
-        irs_set_error("irs_cem_rollout_costs_quasistatic_drawn: model %d is not position controlled", model);
-        return rc;
-    }
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-int irs_cem_refit_drawn(int T, int m, int B, int n_elite, const double* u_mean, const double* std, uint64_t seed,
-                        uint32_t iter, uint64_t sample_offset, const double* costs, int* elite_idx, double* u_new,
-                        double* std_new, void* stream) {
-    IRS_CHECK_ARG(T > 0 && m > 0 && B > 0 && n_elite > 0 && n_elite <= B, "need 0 < n_elite <= B");
-    IRS_CHECK_ARG(u_mean && std && costs && elite_idx && u_new && std_new, "null pointer");
-    const size_t len = (size_t)T * m;
-    IRS_CHECK_ARG(!overlap(u_new, u_mean, len) && !overlap(u_new, std, len) && !overlap(std_new, u_mean, len) &&
-                      !overlap(std_new, std, len) && !overlap(u_new, std_new, len),
-                  "u_new / std_new must not alias u_mean / std (the refit reads the old ones while it writes)");
-    launch_refit_drawn(T, m, B, n_elite, CemDrawn{u_mean, std, seed, sample_offset, iter}, costs, elite_idx, u_new,
-                       std_new, static_cast<hipStream_t>(stream));
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-// ---- model-free rollout: one stage per call, the caller steps the plant between calls ---------------------------
-
-int irs_cem_values_stage(int n, int m, int T, int B, int t, const double* x, const double* u_cand, const double* Q,
-                         const double* R, const double* xd_trj, double* u_t, double* costs, void* stream) {
-    const char* bad = stage_argument_error(n, m, T, B, t, x, Q, R, xd_trj, u_t, costs);
-    IRS_CHECK_ARG(bad == nullptr, bad);
-    IRS_CHECK_ARG(u_cand != nullptr, "null pointer");
-    launch_stage(n, m, T, B, t, CemSupplied{u_cand}, x, Q, R, xd_trj, u_t, costs, static_cast<hipStream_t>(stream));
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-int irs_cem_values_stage_drawn(int n, int m, int T, int B, int t, const double* x, const double* u_mean,
-                               const double* std, uint64_t seed, uint32_t iter, uint64_t sample_offset, const double* Q,
-                               const double* R, const double* xd_trj, double* u_t, double* costs, void* stream) {
-    const char* bad = stage_argument_error(n, m, T, B, t, x, Q, R, xd_trj, u_t, costs);
-    IRS_CHECK_ARG(bad == nullptr, bad);
-    IRS_CHECK_ARG(u_mean != nullptr && std != nullptr, "null pointer");
-    launch_stage(n, m, T, B, t, CemDrawn{u_mean, std, seed, sample_offset, iter}, x, Q, R, xd_trj, u_t, costs,
-                 static_cast<hipStream_t>(stream));
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-// costs (B) | elite_idx (n_elite) | the plain cost of the mean's rollout where the quasistatic one is reported
-size_t irs_cem_iterate_scratch_bytes(int T, int m, int B, int n_elite) {
-    if (T <= 0 || m <= 0 || B <= 0 || n_elite <= 0) return 0;
-    return round256((size_t)B * sizeof(double)) + round256((size_t)n_elite * sizeof(int)) + 256;
-}
-
-int irs_cem_iterate(const irs_cem_iterate_call* c, void* stream) {
-    IRS_CHECK_ARG(c != nullptr, "null call struct");
-    IRS_CHECK_ARG(c->T > 0 && c->B > 0 && c->n_descents > 0, "T, B and n_descents must be positive");
-    IRS_CHECK_ARG(c->n_elite > 0 && c->n_elite <= c->B, "need 0 < n_elite <= B");
-    IRS_CHECK_ARG(c->Q && c->R && c->xd_trj && c->x0 && c->u_trj0 && c->std0, "null problem pointer");
-    IRS_CHECK_ARG(!c->quasistatic || c->Qd, "the quasistatic cost needs Qd");
-    IRS_CHECK_ARG(c->u_hist && c->std_hist && c->x_hist && c->cost_hist && c->scratch, "null output / scratch pointer");
-    int n, m, np;
-    int rc = irs_model_info(c->model, &n, &m, &np);
-    if (rc != IRS_OK) return rc;
-    ModelParams p;
-    rc = irs_load_params(c->model, c->params, c->n_params, &p);
-    if (rc != IRS_OK) return rc;
-    if (c->quasistatic && position_controlled(c->model) != IRS_OK) {
-        irs_set_error("irs_cem_iterate: model %d is not position controlled", c->model);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    const int T = c->T, B = c->B;
-    const size_t need = irs_cem_iterate_scratch_bytes(T, m, B, c->n_elite);
-    if (c->scratch_bytes < need) {
-        irs_set_error("irs_cem_iterate: scratch %zu < %zu bytes", c->scratch_bytes, need);
-        return IRS_ERR_INVALID_ARG;
-    }
-    char* sp = static_cast<char*>(c->scratch);
-    double* costs = reinterpret_cast<double*>(sp);
-    int* elite_idx = reinterpret_cast<int*>(sp + round256((size_t)B * sizeof(double)));
-    double* plain_cost = reinterpret_cast<double*>(sp + need - 256);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t us = (size_t)T * m, xs = (size_t)(T + 1) * n;
-    for (int i = 0; i < c->n_descents; ++i) {
-        // draw around the previous descent's refit (std is always carried; the caller decides what "adopted" means)
-        const CemDrawn src{i == 0 ? c->u_trj0 : c->u_hist + (size_t)(i - 1) * us,
-                           i == 0 ? c->std0 : c->std_hist + (size_t)(i - 1) * us, c->seed, 0, c->iter0 + (uint32_t)i};
-        double* u_new = c->u_hist + (size_t)i * us;
-        rc = c->quasistatic ? launch_rollout<CemCost::Quasistatic>(c->model, p, T, B, src, c->x0, c->Q, c->Qd, c->R,
-                                                                   c->xd_trj, costs, st)
-                            : launch_rollout<CemCost::Plain>(c->model, p, T, B, src, c->x0, c->Q, nullptr, c->R,
-                                                             c->xd_trj, costs, st);
-        if (rc != IRS_OK) return rc;
-        launch_refit_drawn(T, m, B, c->n_elite, src, costs, elite_idx, u_new, c->std_hist + (size_t)i * us, st);
-        // the mean's rollout (cem.py:182), priced like the candidates
-        rc = irs_rollout_cost(c->model, c->params, c->n_params, T, c->x0, u_new, c->Q, c->R, c->xd_trj,
-                              c->x_hist + (size_t)i * xs, c->quasistatic ? plain_cost : c->cost_hist + i, stream);
-        if (rc != IRS_OK) return rc;
-        if (c->quasistatic) {
-            rc = launch_rollout<CemCost::Quasistatic>(c->model, p, T, 1, CemSupplied{u_new}, c->x0, c->Q, c->Qd, c->R,
-                                                      c->xd_trj, c->cost_hist + i, st);
-            if (rc != IRS_OK) return rc;
-        }
-    }
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-}  // extern "C"

@@ -56,40 +56,96 @@ def smooth_geometry(model_id, mode, T, N, rng=False):
                 wg0_rr=out[5], branch=_lib.SMOOTH_PLANS[out[6]])
 
 
+class CemSource:
+    """Where the B candidate sequences of a CEM operation come from (csrc/cem.hpp): `supplied` as a tensor, or `drawn`
+    inside the kernels, never stored.  Knows B, T, m and the device; `args` is the run of C arguments that stands for
+    the source in an entry -- every irs_cem_* entry comes as `name` taking the tensor and `name`_drawn taking the
+    stream in the same place (`suffix` tells which) -- built once; the source keeps its tensors alive."""
+    __slots__ = ("suffix", "B", "T", "m", "args", "tensors", "device")
+
+    def __init__(self, suffix, B, T, m, args, tensors):
+        self.suffix, self.B, self.T, self.m, self.args, self.tensors = suffix, B, T, m, args, tensors
+        self.device = tensors[0].device
+
+    @classmethod
+    def supplied(cls, u_cand):
+        """The candidates u_cand (B,T,m)."""
+        B, T, m = u_cand.shape
+        return cls("", B, T, m, (_ptr(u_cand, F64),), (u_cand,))
+
+    @classmethod
+    def drawn(cls, u_mean, std, B, seed, it, sample_offset=0):
+        """Candidates sample_offset .. sample_offset + B of the stream of (seed, it), scaled by std (T,m) around
+        u_mean (T,m) (include/irs_hip.h: irs_cem_candidates writes them out)."""
+        T, m = u_mean.shape
+        return cls("_drawn", int(B), T, m, (_ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it), int(sample_offset)),
+                   (u_mean, std))
+
+
+def _quasistatic_weight(Qd):
+    if Qd is None:
+        raise ValueError("the quasistatic CEM cost needs Qd")
+    return Qd
+
+
 class CemModelFree:
-    """The CEM calls that never see the plant -- selection + refit, the candidate writer -- for every class with a
-    `lib`: DeviceModel and torch_system.TorchDeviceModel."""
+    """The CEM surface of every class with a `lib` -- DeviceModel and torch_system.TorchDeviceModel -- over two
+    primitives on a CemSource: cem_refit_from (selection + refit, which never see the plant) and the subclass's
+    cem_costs(src, x0, Q, R, xd_trj, Qd=None) -> costs (B) of the candidates of `src`, rollout + evaluate_cost each
+    or, with Qd, the quasistatic eval_cost (du input cost, terminal Qd)."""
+
+    def cem_refit_from(self, src, costs, n_elite):
+        """Elite selection + mean/std refit (a drawn source: the elites regenerated from their indices): returns
+        elite_idx (n_elite), u_new (T,m), std_new (T,m), fresh tensors."""
+        idx = torch.empty((n_elite,), dtype=torch.int32, device=src.device)
+        u_new = torch.empty((src.T, src.m), dtype=F64, device=src.device)
+        std_new = torch.empty((src.T, src.m), dtype=F64, device=src.device)
+        name = "irs_cem_refit" + src.suffix
+        check(getattr(self.lib, name)(src.T, src.m, src.B, int(n_elite), *src.args, _ptr(costs, F64), idx.data_ptr(),
+                                      _ptr(u_new, F64), _ptr(std_new, F64), _stream()), name)
+        return idx, u_new, std_new
+
+    def cem_rollout_costs(self, u_cand, x0, Q, R, xd_trj):
+        """costs (B) of the B candidate sequences u_cand (B,T,m): rollout + evaluate_cost each."""
+        return self.cem_costs(CemSource.supplied(u_cand), x0, Q, R, xd_trj)
+
+    def cem_rollout_costs_quasistatic(self, u_cand, x0, Q, Qd, R, xd_trj):
+        """costs (B) with the quasistatic eval_cost (du input cost, terminal Qd)."""
+        return self.cem_costs(CemSource.supplied(u_cand), x0, Q, R, xd_trj, Qd=_quasistatic_weight(Qd))
+
+    # device-resident form: the candidates are drawn inside the kernels (include/irs_hip.h), never stored
+    def cem_rollout_costs_drawn(self, u_mean, std, B, seed, it, x0, Q, R, xd_trj, sample_offset=0):
+        """cem_rollout_costs of B candidates drawn around u_mean (T,m) with std (T,m): no (B,T,m) tensor."""
+        return self.cem_costs(CemSource.drawn(u_mean, std, B, seed, it, sample_offset), x0, Q, R, xd_trj)
+
+    def cem_rollout_costs_quasistatic_drawn(self, u_mean, std, B, seed, it, x0, Q, Qd, R, xd_trj, sample_offset=0):
+        """cem_rollout_costs_quasistatic of B drawn candidates."""
+        return self.cem_costs(CemSource.drawn(u_mean, std, B, seed, it, sample_offset), x0, Q, R, xd_trj,
+                              Qd=_quasistatic_weight(Qd))
 
     def cem_refit(self, u_cand, costs, n_elite):
-        """Elite selection + mean/std refit: returns elite_idx (n_elite), u_new (T,m), std_new (T,m)."""
-        B, T, m = u_cand.shape
-        dev = u_cand.device
-        idx = torch.empty((n_elite,), dtype=torch.int32, device=dev)
-        u_new = torch.empty((T, m), dtype=F64, device=dev)
-        std_new = torch.empty((T, m), dtype=F64, device=dev)
-        check(self.lib.irs_cem_refit(T, m, B, int(n_elite), _ptr(u_cand, F64), _ptr(costs, F64), idx.data_ptr(),
-                                     _ptr(u_new, F64), _ptr(std_new, F64), _stream()), "irs_cem_refit")
-        return idx, u_new, std_new
+        """cem_refit_from on the candidates u_cand (B,T,m)."""
+        return self.cem_refit_from(CemSource.supplied(u_cand), costs, n_elite)
+
+    def cem_refit_drawn(self, u_mean, std, seed, it, costs, n_elite, sample_offset=0):
+        """cem_refit_from on the costs.shape[0] candidates drawn around u_mean with std."""
+        return self.cem_refit_from(CemSource.drawn(u_mean, std, costs.shape[0], seed, it, sample_offset), costs, n_elite)
 
     def cem_candidates(self, u_mean, std, B, seed, it, sample_offset=0):
         """The (B,T,m) candidates the drawn kernels see (verification only)."""
-        T, m = u_mean.shape
-        u_cand = torch.empty((B, T, m), dtype=F64, device=u_mean.device)
-        check(self.lib.irs_cem_candidates(T, m, int(B), _ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it),
-                                          int(sample_offset), _ptr(u_cand, F64), _stream()), "irs_cem_candidates")
+        src = CemSource.drawn(u_mean, std, B, seed, it, sample_offset)
+        u_cand = torch.empty((src.B, src.T, src.m), dtype=F64, device=src.device)
+        check(self.lib.irs_cem_candidates(src.T, src.m, src.B, *src.args, _ptr(u_cand, F64), _stream()),
+              "irs_cem_candidates")
         return u_cand
 
-    def cem_refit_drawn(self, u_mean, std, seed, it, costs, n_elite, sample_offset=0):
-        """cem_refit with the elites regenerated from their indices: elite_idx, u_new, std_new (fresh tensors)."""
-        T, m = u_mean.shape
-        dev = u_mean.device
-        idx = torch.empty((n_elite,), dtype=torch.int32, device=dev)
-        u_new = torch.empty((T, m), dtype=F64, device=dev)
-        std_new = torch.empty((T, m), dtype=F64, device=dev)
-        check(self.lib.irs_cem_refit_drawn(T, m, costs.shape[0], int(n_elite), _ptr(u_mean, F64), _ptr(std, F64),
-                                           int(seed), int(it), int(sample_offset), _ptr(costs, F64), idx.data_ptr(),
-                                           _ptr(u_new, F64), _ptr(std_new, F64), _stream()), "irs_cem_refit_drawn")
-        return idx, u_new, std_new
+    def _cem_histories(self, u_trj0, n_descents):
+        """What cem_iterate returns: u_hist, std_hist (n_descents,T,m), x_hist (n_descents,T+1,n), cost_hist
+        (n_descents), on the device of u_trj0 (T,m)."""
+        k, (T, m) = int(n_descents), u_trj0.shape
+        return {key: torch.empty(shape, dtype=F64, device=u_trj0.device)
+                for key, shape in (("u_hist", (k, T, m)), ("std_hist", (k, T, m)), ("x_hist", (k, T + 1, self.n)),
+                                   ("cost_hist", (k,)))}
 
 
 class DeviceModel(CemModelFree):
@@ -506,63 +562,26 @@ class DeviceModel(CemModelFree):
               "irs_quasistatic_bound_rows_batch")
         return lo, hi
 
-    # ---- CEM baseline -------------------------------------------------------
-    def cem_rollout_costs(self, u_cand, x0, Q, R, xd_trj):
-        """costs (B) of the B candidate sequences u_cand (B,T,m): rollout + evaluate_cost each."""
-        B, T = u_cand.shape[0], u_cand.shape[1]
-        costs = torch.empty((B,), dtype=F64, device=u_cand.device)
-        check(self.lib.irs_cem_rollout_costs(self.model_id, self._p, self._np, T, B, _ptr(u_cand, F64),
-                                             _ptr(x0, F64), _ptr(Q, F64), _ptr(R, F64), _ptr(xd_trj, F64),
-                                             _ptr(costs, F64), _stream()), "irs_cem_rollout_costs")
+    # ---- CEM baseline (the public names: CemModelFree) ------------------------
+    def cem_costs(self, src, x0, Q, R, xd_trj, Qd=None):
+        """CemModelFree.cem_costs in one launch; the entry is picked by (quasistatic, drawn)."""
+        costs = torch.empty((src.B,), dtype=F64, device=src.device)
+        name = ("irs_cem_rollout_costs" if Qd is None else "irs_cem_rollout_costs_quasistatic") + src.suffix
+        weights = (_ptr(Q, F64), _ptr(R, F64)) if Qd is None else (_ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64))
+        check(getattr(self.lib, name)(self.model_id, self._p, self._np, src.T, src.B, *src.args, _ptr(x0, F64), *weights,
+                                      _ptr(xd_trj, F64), _ptr(costs, F64), _stream()), name)
         return costs
-
-    def cem_rollout_costs_quasistatic(self, u_cand, x0, Q, Qd, R, xd_trj):
-        """costs (B) with the quasistatic eval_cost (du input cost, terminal Qd)."""
-        B, T = u_cand.shape[0], u_cand.shape[1]
-        costs = torch.empty((B,), dtype=F64, device=u_cand.device)
-        check(self.lib.irs_cem_rollout_costs_quasistatic(self.model_id, self._p, self._np, T, B, _ptr(u_cand, F64),
-                                                         _ptr(x0, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
-                                                         _ptr(xd_trj, F64), _ptr(costs, F64), _stream()),
-              "irs_cem_rollout_costs_quasistatic")
-        return costs
-
-    # device-resident form: the candidates are drawn inside the kernels (include/irs_hip.h), never stored
-    def cem_rollout_costs_drawn(self, u_mean, std, B, seed, it, x0, Q, R, xd_trj, sample_offset=0):
-        """cem_rollout_costs of B candidates drawn around u_mean (T,m) with std (T,m)."""
-        costs = torch.empty((int(B),), dtype=F64, device=u_mean.device)
-        check(self.lib.irs_cem_rollout_costs_drawn(self.model_id, self._p, self._np, u_mean.shape[0], int(B),
-                                                   _ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it),
-                                                   int(sample_offset), _ptr(x0, F64), _ptr(Q, F64), _ptr(R, F64),
-                                                   _ptr(xd_trj, F64), _ptr(costs, F64), _stream()),
-              "irs_cem_rollout_costs_drawn")
-        return costs
-
-    def cem_rollout_costs_quasistatic_drawn(self, u_mean, std, B, seed, it, x0, Q, Qd, R, xd_trj, sample_offset=0):
-        """cem_rollout_costs_quasistatic of B drawn candidates."""
-        costs = torch.empty((int(B),), dtype=F64, device=u_mean.device)
-        check(self.lib.irs_cem_rollout_costs_quasistatic_drawn(self.model_id, self._p, self._np, u_mean.shape[0], int(B),
-                                                               _ptr(u_mean, F64), _ptr(std, F64), int(seed), int(it),
-                                                               int(sample_offset), _ptr(x0, F64), _ptr(Q, F64),
-                                                               _ptr(Qd, F64), _ptr(R, F64), _ptr(xd_trj, F64),
-                                                               _ptr(costs, F64), _stream()),
-              "irs_cem_rollout_costs_quasistatic_drawn")
-        return costs
-
     def cem_iterate(self, u_trj0, std0, x0, Q, Qd, R, xd_trj, B, n_elite, n_descents, seed, iter0=1,
                     quasistatic=False):
         """n_descents CEM descents in ONE library call (irs_cem_iterate), nothing read back: a dict of the device
         histories u_hist, std_hist (n_descents,T,m), x_hist (n_descents,T+1,n), cost_hist (n_descents)."""
         T, m = u_trj0.shape
-        dev, k = u_trj0.device, int(n_descents)
-        o = {"u_hist": torch.empty((k, T, m), dtype=F64, device=dev),
-             "std_hist": torch.empty((k, T, m), dtype=F64, device=dev),
-             "x_hist": torch.empty((k, T + 1, self.n), dtype=F64, device=dev),
-             "cost_hist": torch.empty((k,), dtype=F64, device=dev)}
+        o = self._cem_histories(u_trj0, n_descents)
         need = self.lib.irs_cem_iterate_scratch_bytes(T, m, int(B), int(n_elite))
-        scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev)
+        scratch = torch.empty((max(need, 8),), dtype=torch.uint8, device=u_trj0.device)
         c = _lib.CemIterateCall()
         self.fill_call(c)
-        c.T, c.B, c.n_elite, c.n_descents, c.quasistatic = T, int(B), int(n_elite), k, int(bool(quasistatic))
+        c.T, c.B, c.n_elite, c.n_descents, c.quasistatic = T, int(B), int(n_elite), int(n_descents), int(bool(quasistatic))
         c.seed, c.iter0 = int(seed), int(iter0)
         c.Q, c.Qd, c.R, c.xd_trj, c.x0 = (_ptr(a, F64) for a in (Q, Qd, R, xd_trj, x0))
         c.u_trj0, c.std0 = _ptr(u_trj0, F64), _ptr(std0, F64)
@@ -925,21 +944,18 @@ def box_values_solve(At, Bt, ct, Q, Qd, R, xd_trj, x0, x_lo=None, x_hi=None, u_l
 
 
 # ---- model-free CEM rollout (csrc/cem.hip, cem_values_stage_kernel): the caller steps the plant between the stages ----
-def cem_values_stage(t, x, u_cand, Q, R, xd_trj, u_t, costs):
-    """Stage t of B candidate rollouts on the supplied candidates u_cand (B,T,m) (irs_cem_values_stage): x (B,n) are
-    the states at step t; costs (B) gets this stage's cost terms (written at t = 0, added after), u_t (B,m) the
-    controls of step t (None at t = T).  One launch."""
-    B, T, m = u_cand.shape
-    check(_lib.load().irs_cem_values_stage(x.shape[1], m, T, B, int(t), _ptr(x, F64), _ptr(u_cand, F64), _ptr(Q, F64),
-                                           _ptr(R, F64), _ptr(xd_trj, F64), _ptr(u_t, F64), _ptr(costs, F64),
-                                           _stream()), "irs_cem_values_stage")
+def cem_values_stage(t, x, src, Q, R, xd_trj, u_t, costs):
+    """Stage t of the B candidate rollouts of `src` -- a CemSource, or the supplied candidates u_cand (B,T,m)
+    themselves (irs_cem_values_stage[_drawn]): x (B,n) are the states at step t; costs (B) gets this stage's cost terms
+    (written at t = 0, added after), u_t (B,m) the controls of step t (None at t = T).  One launch."""
+    if not isinstance(src, CemSource):
+        src = CemSource.supplied(src)
+    name = "irs_cem_values_stage" + src.suffix
+    check(getattr(_lib.load(), name)(x.shape[1], src.m, src.T, src.B, int(t), _ptr(x, F64), *src.args, _ptr(Q, F64),
+                                     _ptr(R, F64), _ptr(xd_trj, F64), _ptr(u_t, F64), _ptr(costs, F64), _stream()), name)
 
 
 def cem_values_stage_drawn(t, x, u_mean, std, seed, it, sample_offset, Q, R, xd_trj, u_t, costs):
     """cem_values_stage with the controls drawn around u_mean (T,m) with std (T,m) -- the stream of cem_candidates --
-    for the B = x.shape[0] candidates sample_offset .. sample_offset + B (irs_cem_values_stage_drawn)."""
-    T, m = u_mean.shape
-    check(_lib.load().irs_cem_values_stage_drawn(x.shape[1], m, T, x.shape[0], int(t), _ptr(x, F64), _ptr(u_mean, F64),
-                                                 _ptr(std, F64), int(seed), int(it), int(sample_offset), _ptr(Q, F64),
-                                                 _ptr(R, F64), _ptr(xd_trj, F64), _ptr(u_t, F64), _ptr(costs, F64),
-                                                 _stream()), "irs_cem_values_stage_drawn")
+    for the B = x.shape[0] candidates sample_offset .. sample_offset + B."""
+    cem_values_stage(t, x, CemSource.drawn(u_mean, std, x.shape[0], seed, it, sample_offset), Q, R, xd_trj, u_t, costs)

@@ -276,29 +276,27 @@ class TorchDeviceModel(dev.CemModelFree):
             x_new[t + 1] = self._step(x_new[t], u_new[t])
         return dict(x_new=x_new, u_new=u_new, info=h["info"])
 
-    # ---- CEM baseline: DeviceModel's surface (cem_refit, cem_refit_drawn, cem_candidates: dev.CemModelFree) ---------
-    def _cem_rollout(self, B, T, x0, xd_trj, stage):
-        """The time loop of B rollouts: stage(t, x, u_t, costs) for t = 0..T with one float64 call of the callable
-        between two stages -- T + 1 launches and T torch steps on the current stream, nothing read on the host."""
-        x = x0.expand(B, self.n).contiguous()
-        u_t = torch.empty((B, self.m), dtype=dev.F64, device=x0.device)
-        costs = torch.empty((B,), dtype=dev.F64, device=x0.device)
-        for t in range(T):
-            stage(t, x, u_t, costs)
+    # ---- CEM baseline: DeviceModel's surface (the public names, selection and refit: dev.CemModelFree) -------------
+    _NO_QUASISTATIC_CEM = ("the quasistatic CEM cost needs a compiled position-controlled model; a "
+                           "TorchDynamicalSystem runs CrossEntropyMethod only")
+
+    def _cem_rollout(self, src, x0, Q, R, xd_trj):
+        """The time loop of the B rollouts of `src`: dev.cem_values_stage for t = 0..T with one float64 call of the
+        callable between two stages -- T + 1 launches and T torch steps on the current stream, nothing read on the
+        host."""
+        x = x0.expand(src.B, self.n).contiguous()
+        u_t = torch.empty((src.B, self.m), dtype=dev.F64, device=x0.device)
+        costs = torch.empty((src.B,), dtype=dev.F64, device=x0.device)
+        for t in range(src.T):
+            dev.cem_values_stage(t, x, src, Q, R, xd_trj, u_t, costs)
             x = self._f(x, u_t)
-        stage(T, x, None, costs)
+        dev.cem_values_stage(src.T, x, src, Q, R, xd_trj, None, costs)
         return costs
 
-    def cem_rollout_costs(self, u_cand, x0, Q, R, xd_trj):
-        """costs (B) of the B candidate sequences u_cand (B,T,m): rollout + evaluate_cost each."""
-        return self._cem_rollout(u_cand.shape[0], u_cand.shape[1], x0, xd_trj, lambda t, x, u_t, costs:
-                                 dev.cem_values_stage(t, x, u_cand, Q, R, xd_trj, u_t, costs))
-
-    def cem_rollout_costs_drawn(self, u_mean, std, B, seed, it, x0, Q, R, xd_trj, sample_offset=0):
-        """cem_rollout_costs of B candidates drawn around u_mean (T,m) with std (T,m): no (B,T,m) tensor."""
-        return self._cem_rollout(int(B), u_mean.shape[0], x0, xd_trj, lambda t, x, u_t, costs:
-                                 dev.cem_values_stage_drawn(t, x, u_mean, std, seed, it, sample_offset, Q, R, xd_trj,
-                                                            u_t, costs))
+    def cem_costs(self, src, x0, Q, R, xd_trj, Qd=None):
+        if Qd is not None:
+            raise NotImplementedError(self._NO_QUASISTATIC_CEM)
+        return self._cem_rollout(src, x0, Q, R, xd_trj)
 
     def cem_iterate(self, u_trj0, std0, x0, Q, Qd, R, xd_trj, B, n_elite, n_descents, seed, iter0=1,
                     quasistatic=False):
@@ -307,18 +305,12 @@ class TorchDeviceModel(dev.CemModelFree):
         (n_descents).  Descent i draws around descent i - 1's refit with generator iteration iter0 + i, as
         irs_cem_iterate does; here the loop is the host's and only enqueues."""
         if quasistatic:
-            raise NotImplementedError("the quasistatic CEM cost needs a compiled position-controlled model; a "
-                                      "TorchDynamicalSystem runs CrossEntropyMethod only")
-        T, m = u_trj0.shape
-        device, k = u_trj0.device, int(n_descents)
-        o = {"u_hist": torch.empty((k, T, m), dtype=dev.F64, device=device),
-             "std_hist": torch.empty((k, T, m), dtype=dev.F64, device=device),
-             "x_hist": torch.empty((k, T + 1, self.n), dtype=dev.F64, device=device),
-             "cost_hist": torch.empty((k,), dtype=dev.F64, device=device)}
+            raise NotImplementedError(self._NO_QUASISTATIC_CEM)
+        o = self._cem_histories(u_trj0, n_descents)
         mean, std = u_trj0, std0
-        for i in range(k):
-            costs = self.cem_rollout_costs_drawn(mean, std, B, seed, int(iter0) + i, x0, Q, R, xd_trj)
-            _, mean, std = self.cem_refit_drawn(mean, std, seed, int(iter0) + i, costs, n_elite)
+        for i in range(int(n_descents)):
+            src = dev.CemSource.drawn(mean, std, B, seed, int(iter0) + i)
+            _, mean, std = self.cem_refit_from(src, self.cem_costs(src, x0, Q, R, xd_trj), n_elite)
             x_new, cost = self.rollout_cost(x0, mean, Q, R, xd_trj)        # the mean's rollout (cem.py:182)
             for key, v in (("u_hist", mean), ("std_hist", std), ("x_hist", x_new)):
                 o[key][i].copy_(v)

@@ -414,3 +414,39 @@ def test_example_runners_take_device_rng_for_cem(amd, module, argv, monkeypatch,
     run.main()
     hist = [float(v) for v in capsys.readouterr().out.split("cost history:")[1].split()]
     assert len(hist) == 4 and all(np.isfinite(hist))
+
+
+# ---------------------------------------------------------------- 6. one candidate source under both device models
+def test_candidate_source_primitives_on_a_torch_system(amd):
+    """cem_costs / cem_refit_from on a TorchDeviceModel with a CemSource of a non-zero sample_offset, which the public
+    classes never pass.  The drawn source against the supplied source on the materialised stream: costs and elite_idx
+    under torch.equal (one candidate stream, one cost body, as test_drawn_stage_equals_supplied_stage holds stage by
+    stage), the refit to the bounds of test_drawn_refit_equals_refit_on_materialised_candidates.  The public names are
+    the primitives; the quasistatic cost is refused as cem_iterate(quasistatic=True) refuses it.  B = 300: the third
+    128-lane stage workgroup is ragged."""
+    from examples.torch_systems import TorchPendulum
+    from irs_mpc_amd import device as dev
+    T, B, n_elite, it = 3, 300, 7, 4
+    dm = TorchPendulum(0.05).dm()
+    mean, std = mean_std(T, 1, 3)
+    mean_d, std_d = dev.to_dev(mean), dev.to_dev(std)
+    x0, Q, R = dev.to_dev(np.zeros(2)), dev.to_dev(np.diag([1., 2.])), dev.to_dev(np.eye(1))
+    xd = dev.to_dev(np.tile(np.array([np.pi, 0.]), (T + 1, 1)))
+    drawn = dev.CemSource.drawn(mean_d, std_d, B, SEED, it, OFFSET)
+    supplied = dev.CemSource.supplied(dm.cem_candidates(mean_d, std_d, B, SEED, it, OFFSET))
+    assert (drawn.B, drawn.T, drawn.m) == (supplied.B, supplied.T, supplied.m) == (B, T, 1)
+    c_drawn, c_sup = dm.cem_costs(drawn, x0, Q, R, xd), dm.cem_costs(supplied, x0, Q, R, xd)
+    assert np.isfinite(npy(c_sup)).all() and float(c_sup.std()) > 0
+    assert torch.equal(c_drawn, c_sup)
+    assert torch.equal(dm.cem_rollout_costs_drawn(mean_d, std_d, B, SEED, it, x0, Q, R, xd, OFFSET), c_drawn)
+    assert not torch.equal(dm.cem_rollout_costs_drawn(mean_d, std_d, B, SEED, it, x0, Q, R, xd), c_drawn)   # offset 0
+    assert torch.equal(dm.cem_rollout_costs(supplied.tensors[0], x0, Q, R, xd), c_sup)
+    idx1, u1, s1 = dm.cem_refit_from(drawn, c_drawn, n_elite)
+    idx0, u0, s0 = dm.cem_refit_from(supplied, c_sup, n_elite)
+    assert torch.equal(idx1, idx0)
+    np.testing.assert_allclose(npy(u1), npy(u0), rtol=1e-12, atol=1e-13)
+    np.testing.assert_allclose(npy(s1), npy(s0), rtol=1e-9, atol=1e-12)
+    for call in (lambda: dm.cem_costs(drawn, x0, Q, R, xd, Qd=Q),
+                 lambda: dm.cem_rollout_costs_quasistatic(supplied.tensors[0], x0, Q, Q, R, xd)):
+        with pytest.raises(NotImplementedError, match="compiled position-controlled model"):
+            call()

@@ -3,7 +3,7 @@ build a tuning library with -DIRS_RIC_STAMPS and point IRS_HIP_LIB at it, on the
 
     cd irs_mpc_amd/csrc && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=fast -DIRS_RIC_STAMPS \
         -c tvlqr.hip -o /tmp/tvlqr_st.o && hipcc --offload-arch=gfx950 -shared -fPIC -o variants/libirs_hip_ricst.so \
-        plugin.o smooth.o smooth_api.o smooth_ug.o /tmp/tvlqr_st.o cem.o boxqp.o boxqp_api.o ctrlbox.o ctrlbox_mfma.o collective.o iterate.o -ldl
+        plugin.o smooth.o smooth_api.o smooth_ug.o /tmp/tvlqr_st.o cem.o cem_api.o boxqp.o boxqp_api.o ctrlbox.o ctrlbox_mfma.o collective.o iterate.o -ldl
     IRS_HIP_LIB=$PWD/variants/libirs_hip_ricst.so python tools/riccati_stamps.py
 
 Prints s_memtime cycles per step: head + 14 products, gain solve, the ten products of the Joseph update, and how long a

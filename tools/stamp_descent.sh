@@ -9,7 +9,7 @@ LIB=${TMPDIR:-/tmp}/libirs_hip_stamps.so
 cd $R/irs_mpc_amd/csrc
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=fast -mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -fno-signed-zeros \
     -DIRS_CBM_STAMPS -c ctrlbox_mfma.hip -o /tmp/ctrlbox_mfma_stamps.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $LIB plugin.o smooth.o smooth_api.o smooth_ug.o tvlqr.o cem.o boxqp.o boxqp_api.o ctrlbox.o collective.o iterate.o /tmp/ctrlbox_mfma_stamps.o -ldl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $LIB plugin.o smooth.o smooth_api.o smooth_ug.o tvlqr.o cem.o cem_api.o boxqp.o boxqp_api.o ctrlbox.o collective.o iterate.o /tmp/ctrlbox_mfma_stamps.o -ldl
 cd $R
 IRS_HIP_LIB=$LIB python tools/time_quasistatic.py "$@" --stamps
 # ... and the LAST descent of the benchmark's iLQR loop (a warm-started one, late in an episode)
