@@ -23,6 +23,28 @@ import irs_mpc_amd as amd  # noqa: E402
 from examples.problems import PROBLEMS  # noqa: E402
 
 
+def run_batch(sysd, params, sm, N, iters, a):
+    """--batch B: B copies of the script's problem that differ in the initial guess (u_trj_initial + a fixed
+    perturbation drawn with seed + b; problem 0 keeps the script's) and in the seed of their sample draws."""
+    import copy
+    plist, smps = [], []
+    for b in range(a.batch):
+        p = copy.copy(params)
+        if b > 0:
+            p.u_trj_initial = params.u_trj_initial + 0.01 * np.random.default_rng(a.seed + b).normal(
+                size=params.u_trj_initial.shape)
+        plist.append(p)
+        smps.append(amd.GaussianSmoothing(sm["std_x"], sm["std_u"], N, power=sm["power"], seed=a.seed + b))
+    solver = amd.IrsLqrBatch(sysd, plist, a.method, None if a.method == "exact" else smps)
+    t0 = time.time()
+    solver.iterate(iters)
+    for b in range(a.batch):
+        print("problem %d final cost: %.6f  %s" % (b, solver.cost[b], solver.status[b] or "ok"))
+    print("Elapsed time: " + str(time.time() - t0))
+    if a.csv:
+        np.savetxt(a.csv, np.array([c for c, s in zip(solver.cost_lst, solver.status) if s is None]).T)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("system", choices=sorted(PROBLEMS))
@@ -37,6 +59,9 @@ def main():
     ap.add_argument("--lazy-bounds", action="store_true",
                     help="irs-lqr methods: params.qp_lazy_bounds = True -- the bounded QPs put their penalty only on the "
                          "bounds a plan would break (the scripts' +-1e4 / +-1e5 'no bound' entries then cost nothing)")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="irs-lqr methods: B problems in one IrsLqrBatch -- problem b starts from the script's "
+                         "u_trj_initial plus a fixed, seeded perturbation and draws with seed + b (device RNG)")
     a = ap.parse_args()
 
     sysd, params, sm, cem, iters = PROBLEMS[a.system](*([a.T] if a.T else []))
@@ -45,6 +70,10 @@ def main():
     if a.lazy_bounds:
         params.qp_lazy_bounds = True
     np.random.seed(a.seed)
+    if a.batch > 0:
+        if a.method == "cem":
+            ap.error("--batch runs the irs-lqr methods")
+        return run_batch(sysd, params, sm, N, iters, a)
     if a.method == "cem":
         cp = amd.CemParameters()
         for k in ("Q", "Qd", "R", "x0", "xd_trj", "u_trj_initial"):

@@ -216,7 +216,8 @@ int irs_smooth_rng(int model, const double *params, int n_params, int mode, int 
  * IRS_SMOOTH_ZERO_ORDER_B and IRS_SMOOTH_FIRST_ORDER, the u-only modes (std_x does not exist), while IRS_UG is not 0.
  * The general kernel (csrc/smooth.hip: the other contact models, and the planar hand under IRS_UG=0) has no batched
  * form: its translation unit is SLP-vectorised under -ffp-contract=fast, and a problem index in front of its body
- * changed which products the compiler fuses, i.e. the last bits of the f32 sums.
+ * changed which products the compiler fuses, i.e. the last bits of the f32 sums.  (The analytic models
+ * have a batched form of that kernel under another contract: irs_smooth_rng_general_batch below.)
  * In:  x_trj DEV f64, problem b's nominal states from x_trj + b x_stride (ELEMENTS), T rows of n read: x_stride =
  *      (T+1) n takes a (B,T+1,n) trajectory tensor as it is, T n stacked nominal points; u_trj likewise with u_stride
  *      >= T m; std_u (B,m) DEV f64; seed (B) DEV; iter shared by the problems.
@@ -241,6 +242,33 @@ int irs_smooth_rng_batch(int model, const double *params, int n_params, int mode
                          const double *std_u, const uint64_t *seed, uint32_t iter,
                          double *sums, double *At, double *Bt, double *ct, int *info,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same for the ANALYTIC models (pendulum, quadrotor, bicycle, three cart) in IRS_SMOOTH_ZERO_ORDER_AB and
+ * IRS_SMOOTH_FIRST_ORDER: the general kernel (csrc/smooth.hip) over B T rows, grid (nblk, B T), device-drawn samples
+ * and the fused solve.  Row (b, t) gets the geometry irs_smooth_geometry(model, mode, T, N, 1) plans for the
+ * per-problem (T, N); its Philox counters take t within the problem, problem b's seed, the shared `iter` and
+ * sample_offset 0, so problem b's DRAWS are those of irs_smooth_rng(model, ..., x_trj_b, u_trj_b, std_x_b, std_u_b,
+ * seed_b, iter, ...); std_x (B,n) and std_u (B,m) DEV f64 are converted to f32 as the single entry converts them.
+ * The contract is NOT bit equality with the single call: that translation unit is SLP-vectorised under
+ * -ffp-contract=fast and a problem index in front of the body may change which f32 products fuse.  Problem b's sums,
+ * At, Bt and ct equal the single call's up to f32 rounding and meet the tolerance against the f64 oracle on identical
+ * samples that the single entry meets (tests/test_irs_lqr_batch_gpu.py).
+ * Strides, outputs, workspace (B slices of the single layout, 256-byte aligned, zeroed once per allocation by
+ * irs_smooth_general_batch_workspace_init; every call leaves all counters zero again) and the order of the checks:
+ * as irs_smooth_rng_batch.  irs_smooth_general_batch_workspace_bytes = B * round256(irs_smooth_workspace_bytes(model,
+ * mode, T, N)); 0: model / mode not served, or B <= 0.  Every argument error is decided before the first HIP call:
+ *   IRS_ERR_INVALID_ARG  B, T or N <= 0; T > 1024; B T > 65535; a null pointer (std_x included); short strides; wrong
+ *                        n_params
+ *   IRS_ERR_UNSUPPORTED  a contact model (irs_smooth_rng_batch serves the planar hand), an unknown model,
+ *                        IRS_SMOOTH_ZERO_ORDER_B
+ *   IRS_ERR_WORKSPACE    workspace null, too small or not 256-byte aligned                                        */
+size_t irs_smooth_general_batch_workspace_bytes(int model, int mode, int T, int N, int B);   /* no GPU is touched */
+int irs_smooth_general_batch_workspace_init(void *workspace, size_t workspace_bytes, void *stream);
+int irs_smooth_rng_general_batch(int model, const double *params, int n_params, int mode, int T, int N, int B,
+                                 const double *x_trj, long long x_stride, const double *u_trj, long long u_stride,
+                                 const double *std_x, const double *std_u, const uint64_t *seed, uint32_t iter,
+                                 double *sums, double *At, double *Bt, double *ct, int *info,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* Sample pass, samples SUPPLIED (parity mode; "identical seeds" = the host draws
  * them exactly as the reference's `sampling(x_t,u_t,iter)` closure does, e.g.
@@ -330,6 +358,21 @@ int irs_tvlqr_descent(int model, const double *params, int n_params, int T,
                       const double *Q, const double *Qd, const double *R, double alpha_R,
                       const double *xd_trj, const double *x0, double *K, double *k,
                       double *x_new, double *u_new, double *cost, int *info, void *stream);
+
+/* B descents of the analytic models in ONE launch: irs_tvlqr_descent with a problem index, grid B, one 64-lane
+ * workgroup per problem.  Problem b's outputs are, bit for bit, those of irs_tvlqr_descent on problem b's inputs, on
+ * every Riccati path (the model and T choose it as in the single call).
+ * In (DEV f64, B contiguous blocks): At (B,T,n,n), Bt (B,T,n,m), ct (B,T,n), xd_trj (B,T+1,n), x0 (B,n); shared by
+ *      the problems: the model and its params, T, Q, Qd, R, alpha_R.
+ * Out: K (B,T,m,n), k (B,T,m), x_new (B,T+1,n), u_new (B,T,m), cost (B) DEV f64, info (B) DEV int.
+ * Every argument error is decided before the first HIP call:
+ *   IRS_ERR_INVALID_ARG  B <= 0, T <= 0, a null pointer, wrong n_params
+ *   IRS_ERR_UNSUPPORTED  an unknown model; a contact model (irs_quasistatic_box_descent_batch is its batched descent) */
+int irs_tvlqr_descent_batch(int model, const double *params, int n_params, int T, int B,
+                            const double *At, const double *Bt, const double *ct,
+                            const double *Q, const double *Qd, const double *R, double alpha_R,
+                            const double *xd_trj, const double *x0, double *K, double *k,
+                            double *x_new, double *u_new, double *cost, int *info, void *stream);
 
 /* IrsLqr.local_descent (irs_lqr/irs_lqr.py:148-186) with ACTIVE absolute box bounds
  * (solve_tvlqr's x_bound_abs / u_bound_abs, irs_lqr/tv_lqr.py:112-123): T tail QPs, each
@@ -939,6 +982,15 @@ int irs_tvlqr_plan_within_bounds(int n, int m, int T, const double *At, const do
                                  const double *K, const double *k, const double *x_new,
                                  const double *xlo, const double *xhi, const double *ulo, const double *uhi,
                                  int *flag, void *stream);
+
+/* The same test for B problems in one launch (one workgroup per problem): flag (B) DEV int32, flag[b] = the single
+ * entry's decision on problem b's blocks of irs_tvlqr_descent_batch -- At (B,T,n,n), Bt (B,T,n,m), ct (B,T,n),
+ * K (B,T,m,n), k (B,T,m), x_new (B,T+1,n) -- and ITS box: xlo, xhi (B,n), ulo, uhi (B,m) DEV f64, +-inf allowed.
+ * IRS_ERR_INVALID_ARG: sizes out of range, B <= 0, a null pointer.                                              */
+int irs_tvlqr_plan_within_bounds_batch(int n, int m, int T, int B, const double *At, const double *Bt, const double *ct,
+                                       const double *K, const double *k, const double *x_new,
+                                       const double *xlo, const double *xhi, const double *ulo, const double *uhi,
+                                       int *flag, void *stream);
 
 /* irs_tvlqr_box_descent that (a) also returns evaluate_cost of its result (cost, may be NULL) and (b) returns at
  * once, writing nothing, when *run_flag (DEV int32, may be NULL = always run) is 0.                            */

@@ -6,6 +6,7 @@ from .cem_quasistatic import (CemQuasistaticParameters,            # noqa: F401
 from .dynamical_system import DynamicalSystem                       # noqa: F401
 from .irs_lqr import (IrsLqr, IrsLqrExact, IrsLqrFirstOrder,        # noqa: F401
                       IrsLqrParameters, IrsLqrZeroOrder)
+from .irs_lqr_batch import IrsLqrBatch                              # noqa: F401
 from .irs_lqr_quasistatic import (IrsLqrQuasistatic,               # noqa: F401
                                    IrsLqrQuasistaticParameters)
 from .irs_lqr_quasistatic_batch import IrsLqrQuasistaticBatch       # noqa: F401

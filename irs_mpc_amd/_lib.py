@@ -192,6 +192,16 @@ SIGNATURES["irs_smooth_batch_workspace_init"] = (c_int, [_dp, c_size_t, c_void_p
 SIGNATURES["irs_smooth_rng_batch"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, c_int, c_int, _dp, c_longlong,
                                               _dp, c_longlong, _dp, _dp, c_uint32, _dp, _dp, _dp, _dp, _dp, _dp, c_size_t,
                                               c_void_p])
+# B problems of the analytic models per launch: the general sample pass (+ std_x before std_u), the descent, the plan test
+SIGNATURES["irs_smooth_general_batch_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int, c_int, c_int])
+SIGNATURES["irs_smooth_general_batch_workspace_init"] = (c_int, [_dp, c_size_t, c_void_p])
+SIGNATURES["irs_smooth_rng_general_batch"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, c_int, c_int, _dp,
+                                                      c_longlong, _dp, c_longlong, _dp, _dp, _dp, c_uint32, _dp, _dp, _dp,
+                                                      _dp, _dp, _dp, c_size_t, c_void_p])
+SIGNATURES["irs_tvlqr_descent_batch"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                 c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, c_void_p])
+SIGNATURES["irs_tvlqr_plan_within_bounds_batch"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                            _dp, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_quasistatic_bound_rows_batch"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, c_int, c_int, _dp, _dp,
                                                           c_void_p])
 SIGNATURES["irs_tvlqr_box_solve"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_double,

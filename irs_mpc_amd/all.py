@@ -7,5 +7,6 @@ from .sampling import *           # noqa: F401,F403
 from .cem import *                # noqa: F401,F403
 from .irs_lqr_quasistatic import *   # noqa: F401,F403
 from .irs_lqr_quasistatic_batch import IrsLqrQuasistaticBatch   # noqa: F401
+from .irs_lqr_batch import IrsLqrBatch   # noqa: F401
 from .cem_quasistatic import *       # noqa: F401,F403
 from .torch_system import TorchDynamicalSystem   # noqa: F401

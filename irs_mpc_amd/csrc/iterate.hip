@@ -18,12 +18,13 @@ namespace {
 // QPs too (tv_lqr.py:112-123); otherwise *flag = 1 and the bounded descent must run.  One thread per tail; all
 // tails advance together (thread t is idle until s = t), so the coefficient rows of step s are read by every
 // active thread at once.  (irs_mpc_amd/irs_lqr.py:_tail_plans_within_bounds is the host statement of the same.)
-__global__ void plan_check_kernel(int n, int m, int T, const double* __restrict__ At, const double* __restrict__ Bt,
-                                  const double* __restrict__ ct, const double* __restrict__ K,
-                                  const double* __restrict__ k, const double* __restrict__ x_new,
-                                  const double* __restrict__ xlo, const double* __restrict__ xhi,
-                                  const double* __restrict__ ulo, const double* __restrict__ uhi, int* flag,
-                                  const int* descent_info, const int* smooth_info, int box_unsupported, int* row) {
+__device__ __forceinline__ void plan_check_body(int n, int m, int T, const double* __restrict__ At,
+                                                const double* __restrict__ Bt, const double* __restrict__ ct,
+                                                const double* __restrict__ K, const double* __restrict__ k,
+                                                const double* __restrict__ x_new, const double* __restrict__ xlo,
+                                                const double* __restrict__ xhi, const double* __restrict__ ulo,
+                                                const double* __restrict__ uhi, int* flag, const int* descent_info,
+                                                const int* smooth_info, int box_unsupported, int* row) {
     constexpr int NMAX = 32, MMAX = 16;
     __shared__ int viol;
     if (threadIdx.x == 0) viol = 0;
@@ -81,6 +82,29 @@ __global__ void plan_check_kernel(int n, int m, int T, const double* __restrict_
     }
 }
 
+__global__ void plan_check_kernel(int n, int m, int T, const double* __restrict__ At, const double* __restrict__ Bt,
+                                  const double* __restrict__ ct, const double* __restrict__ K,
+                                  const double* __restrict__ k, const double* __restrict__ x_new,
+                                  const double* __restrict__ xlo, const double* __restrict__ xhi,
+                                  const double* __restrict__ ulo, const double* __restrict__ uhi, int* flag,
+                                  const int* descent_info, const int* smooth_info, int box_unsupported, int* row) {
+    plan_check_body(n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, descent_info, smooth_info, box_unsupported,
+                    row);
+}
+
+// B problems, one workgroup each: problem b's contiguous blocks, its box, its flag (no info row: the fused iterate is
+// a single-problem loop)
+__global__ void plan_check_batch_kernel(int n, int m, int T, const double* __restrict__ At, const double* __restrict__ Bt,
+                                        const double* __restrict__ ct, const double* __restrict__ K,
+                                        const double* __restrict__ k, const double* __restrict__ x_new,
+                                        const double* __restrict__ xlo, const double* __restrict__ xhi,
+                                        const double* __restrict__ ulo, const double* __restrict__ uhi, int* flag) {
+    const size_t b = blockIdx.x, Ts = (size_t)T;
+    plan_check_body(n, m, T, At + b * Ts * n * n, Bt + b * Ts * n * m, ct + b * Ts * n, K + b * Ts * m * n, k + b * Ts * m,
+                    x_new + b * (Ts + 1) * n, xlo + b * n, xhi + b * n, ulo + b * m, uhi + b * m, flag + b, nullptr, nullptr,
+                    0, nullptr);
+}
+
 // one unrolled step of the walk: x_l to its 16-lane group by DPP, two partial sums per output (half the FMA chain)
 template <int NN, int l = 0>
 struct PcWalk {
@@ -101,14 +125,13 @@ struct PcWalk {
 // through LDS is ~200 cycles of latency: twelve in a row per step made this 55 us), the state size is a template
 // parameter (every loop unrolled, no predication).
 template <int NN>
-__global__ __launch_bounds__(1024) void plan_check16_kernel(int m, int T, const double* __restrict__ At,
-                                                            const double* __restrict__ Bt, const double* __restrict__ ct,
-                                                            const double* __restrict__ K, const double* __restrict__ k,
-                                                            const double* __restrict__ x_new,
-                                                            const double* __restrict__ xlo, const double* __restrict__ xhi,
-                                                            const double* __restrict__ ulo, const double* __restrict__ uhi,
-                                                            int* flag, const int* descent_info, const int* smooth_info,
-                                                            int box_unsupported, int* row) {
+__device__ __forceinline__ void plan_check16_body(int m, int T, const double* __restrict__ At,
+                                                  const double* __restrict__ Bt, const double* __restrict__ ct,
+                                                  const double* __restrict__ K, const double* __restrict__ k,
+                                                  const double* __restrict__ x_new, const double* __restrict__ xlo,
+                                                  const double* __restrict__ xhi, const double* __restrict__ ulo,
+                                                  const double* __restrict__ uhi, int* flag, const int* descent_info,
+                                                  const int* smooth_info, int box_unsupported, int* row) {
     constexpr int n = NN, L = 16;
     extern __shared__ double psh[];
     double* AclT = psh;                          // [s][l][i]
@@ -192,6 +215,36 @@ __global__ __launch_bounds__(1024) void plan_check16_kernel(int m, int T, const 
 }
 
 template <int NN>
+__global__ __launch_bounds__(1024) void plan_check16_kernel(int m, int T, const double* __restrict__ At,
+                                                            const double* __restrict__ Bt, const double* __restrict__ ct,
+                                                            const double* __restrict__ K, const double* __restrict__ k,
+                                                            const double* __restrict__ x_new,
+                                                            const double* __restrict__ xlo, const double* __restrict__ xhi,
+                                                            const double* __restrict__ ulo, const double* __restrict__ uhi,
+                                                            int* flag, const int* descent_info, const int* smooth_info,
+                                                            int box_unsupported, int* row) {
+    plan_check16_body<NN>(m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, descent_info, smooth_info,
+                          box_unsupported, row);
+}
+
+template <int NN>
+__global__ __launch_bounds__(1024) void plan_check16_batch_kernel(int m, int T, const double* __restrict__ At,
+                                                                  const double* __restrict__ Bt,
+                                                                  const double* __restrict__ ct,
+                                                                  const double* __restrict__ K,
+                                                                  const double* __restrict__ k,
+                                                                  const double* __restrict__ x_new,
+                                                                  const double* __restrict__ xlo,
+                                                                  const double* __restrict__ xhi,
+                                                                  const double* __restrict__ ulo,
+                                                                  const double* __restrict__ uhi, int* flag) {
+    const size_t b = blockIdx.x, Ts = (size_t)T, n = NN;
+    plan_check16_body<NN>(m, T, At + b * Ts * n * n, Bt + b * Ts * n * m, ct + b * Ts * n, K + b * Ts * m * n,
+                          k + b * Ts * m, x_new + b * (Ts + 1) * n, xlo + b * n, xhi + b * n, ulo + b * m, uhi + b * m,
+                          flag + b, nullptr, nullptr, 0, nullptr);
+}
+
+template <int NN>
 static int plan_check16_launch(int m, int T, size_t bytes, const double* At, const double* Bt, const double* ct,
                                const double* K, const double* k, const double* x_new, const double* xlo,
                                const double* xhi, const double* ulo, const double* uhi, int* flag,
@@ -227,6 +280,39 @@ static int plan_check_launch(int n, int m, int T, const double* At, const double
     const int block = T < 256 ? ((T + 63) / 64 * 64) : 256;
     hipLaunchKernelGGL(plan_check_kernel, dim3(1), dim3(block), 0, st, n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi,
                        flag, descent_info, smooth_info, box_unsupported, row);
+    return IRS_OK;
+}
+
+// the same choice of kernel per problem, B workgroups
+template <int NN>
+static int plan_check16_batch_launch(int m, int T, int B, size_t bytes, const double* At, const double* Bt, const double* ct,
+                                     const double* K, const double* k, const double* x_new, const double* xlo,
+                                     const double* xhi, const double* ulo, const double* uhi, int* flag, hipStream_t st) {
+    constexpr auto kern = plan_check16_batch_kernel<NN>;
+    const int rc = irs_raise_lds_limit<kern>(150 * 1024, "plan check");
+    if (rc != IRS_OK) return rc;
+    const int waves = (T + 3) / 4 < 16 ? (T + 3) / 4 : 16;
+    hipLaunchKernelGGL(kern, dim3(B), dim3(64 * waves), bytes, st, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag);
+    return IRS_OK;
+}
+
+static int plan_check_batch_launch(int n, int m, int T, int B, const double* At, const double* Bt, const double* ct,
+                                   const double* K, const double* k, const double* x_new, const double* xlo,
+                                   const double* xhi, const double* ulo, const double* uhi, int* flag, hipStream_t st) {
+    const size_t bytes = (size_t)T * ((size_t)n * n + n + (size_t)n * m + m) * sizeof(double);
+    if (n >= 1 && n <= 16 && m <= 16 && bytes <= (size_t)(150 * 1024)) {
+#define PC_CASE(NN_)                                                                                                    \
+    case NN_:                                                                                                           \
+        return plan_check16_batch_launch<NN_>(m, T, B, bytes, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, st);
+        switch (n) {
+            PC_CASE(1) PC_CASE(2) PC_CASE(3) PC_CASE(4) PC_CASE(5) PC_CASE(6) PC_CASE(7) PC_CASE(8)
+            PC_CASE(9) PC_CASE(10) PC_CASE(11) PC_CASE(12) PC_CASE(13) PC_CASE(14) PC_CASE(15) PC_CASE(16)
+        }
+#undef PC_CASE
+    }
+    const int block = T < 256 ? ((T + 63) / 64 * 64) : 256;
+    hipLaunchKernelGGL(plan_check_batch_kernel, dim3(B), dim3(block), 0, st, n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo,
+                       uhi, flag);
     return IRS_OK;
 }
 
@@ -277,6 +363,19 @@ int irs_tvlqr_plan_within_bounds(int n, int m, int T, const double* At, const do
     IRS_CHECK_ARG(At && Bt && ct && K && k && x_new && xlo && xhi && ulo && uhi && flag, "null pointer");
     const int rc = plan_check_launch(n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, nullptr, nullptr, 0, nullptr,
                                      static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) return rc;
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+int irs_tvlqr_plan_within_bounds_batch(int n, int m, int T, int B, const double* At, const double* Bt, const double* ct,
+                                       const double* K, const double* k, const double* x_new, const double* xlo,
+                                       const double* xhi, const double* ulo, const double* uhi, int* flag, void* stream) {
+    IRS_CHECK_ARG(n > 0 && n <= 32 && m > 0 && m <= 16 && T > 0, "sizes out of range (n <= 32, m <= 16)");
+    IRS_CHECK_ARG(B > 0, "B must be positive");
+    IRS_CHECK_ARG(At && Bt && ct && K && k && x_new && xlo && xhi && ulo && uhi && flag, "null pointer");
+    const int rc = plan_check_batch_launch(n, m, T, B, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag,
+                                           static_cast<hipStream_t>(stream));
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;

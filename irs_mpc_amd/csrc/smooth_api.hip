@@ -304,6 +304,15 @@ int smooth_batch_supported(int model, int mode, int* n, int* m, int* np) {
     return irs_smooth_ug_supported(model, mode) ? IRS_OK : IRS_ERR_UNSUPPORTED;
 }
 
+// what the general kernel's batched form serves: the analytic models (those with a Jacobian) in the modes that perturb
+// x and u
+int smooth_general_batch_supported(int model, int mode, int* n, int* m, int* np) {
+    const int rc = irs_model_info(model, n, m, np);
+    if (rc != IRS_OK) return rc;
+    const bool analytic = !has_nominal_in_wg0(model, mode);
+    return analytic && (mode == IRS_SMOOTH_ZERO_ORDER_AB || mode == IRS_SMOOTH_FIRST_ORDER) ? IRS_OK : IRS_ERR_UNSUPPORTED;
+}
+
 }  // namespace
 
 extern "C" {
@@ -374,9 +383,87 @@ int irs_smooth_rng_batch(int model, const double* params, int n_params, int mode
     c.At = At; c.Bt = Bt; c.ct = ct; c.info = info;
     fill_args(a, c, g, true);
     a.iter = iter;
-    const SmoothBatch bat{x_stride, u_stride, (long long)stride, reinterpret_cast<const unsigned long long*>(seed), std_u};
+    const SmoothBatch bat{x_stride, u_stride, (long long)stride, reinterpret_cast<const unsigned long long*>(seed), std_u,
+                          nullptr};
     rc = irs_smooth_ug_launch_batch(model, mode, a, bat, B, static_cast<hipStream_t>(stream));
     if (rc != IRS_OK) return rc;
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
+}
+
+size_t irs_smooth_general_batch_workspace_bytes(int model, int mode, int T, int N, int B) {
+    int n, m, np;
+    if (B <= 0 || smooth_general_batch_supported(model, mode, &n, &m, &np) != IRS_OK) return 0;
+    return (size_t)B * round256(irs_smooth_workspace_bytes(model, mode, T, N));
+}
+
+int irs_smooth_general_batch_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(workspace != nullptr && workspace_bytes > 0, "no workspace");
+    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) {
+        irs_set_error("irs_smooth_general_batch_workspace_init: %s", hipGetErrorString(e));
+        return IRS_ERR_HIP;
+    }
+    return IRS_OK;
+}
+
+int irs_smooth_rng_general_batch(int model, const double* params, int n_params, int mode, int T, int N, int B,
+                                 const double* x_trj, long long x_stride, const double* u_trj, long long u_stride,
+                                 const double* std_x, const double* std_u, const uint64_t* seed, uint32_t iter,
+                                 double* sums, double* At, double* Bt, double* ct, int* info,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    // every argument error is decided before the first HIP call
+    IRS_CHECK_ARG(B > 0 && T > 0 && N > 0, "B, T and N must be positive");
+    IRS_CHECK_ARG(T <= kMaxT, "T too large for the arrival counters (max 1024)");
+    IRS_CHECK_ARG((long long)B * T <= 65535, "B * T beyond the grid's 65535 rows");
+    IRS_CHECK_ARG(x_trj && u_trj && std_x && std_u && seed && sums && At && Bt && ct && info, "null pointer");
+    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
+    int n = 0, m = 0, np = 0;
+    int rc = smooth_general_batch_supported(model, mode, &n, &m, &np);
+    if (rc != IRS_OK) {
+        irs_set_error("irs_smooth_rng_general_batch: model %d, mode %d: the general batched sample pass serves the analytic "
+                      "models (pendulum, quadrotor, bicycle, three cart) in IRS_SMOOTH_ZERO_ORDER_AB and "
+                      "IRS_SMOOTH_FIRST_ORDER", model, mode);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (params == nullptr || n_params != np) {
+        irs_set_error("irs_smooth_rng_general_batch: model %d expects %d params, got %d", model, np, n_params);
+        return IRS_ERR_INVALID_ARG;
+    }
+    IRS_CHECK_ARG(x_stride >= (long long)T * n && u_stride >= (long long)T * m,
+                  "x_stride / u_stride shorter than a problem's T rows");
+    SmoothArgs a;
+    memset(&a, 0, sizeof(a));
+    rc = irs_load_params(model, params, n_params, &a.p);
+    if (rc != IRS_OK) return rc;
+    SmoothGeometry g;
+    rc = smooth_geometry(model, mode, T, N, true, &g);
+    if (rc != IRS_OK) return rc;
+    IRS_CHECK_ARG(partial_bytes(T, g.nblk, irs_sums_len(model, mode)) <= 0xffffffffull,
+                  "a problem's partial sums exceed the hand-off's 32-bit buffer size");
+    // B slices of the single-problem layout, 256-byte aligned
+    const size_t stride = round256(irs_smooth_workspace_bytes(model, mode, T, N)), need = (size_t)B * stride;
+    if (workspace == nullptr || workspace_bytes < need) {
+        irs_set_error("irs_smooth_rng_general_batch: workspace %zu < %zu bytes (%d slices of %zu)", workspace_bytes, need, B,
+                      stride);
+        return IRS_ERR_WORKSPACE;
+    }
+    if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
+        irs_set_error("irs_smooth_rng_general_batch: the workspace must be 256-byte aligned");
+        return IRS_ERR_WORKSPACE;
+    }
+    // problem 0's call; the kernel's entry moves its arguments to the row's problem (SmoothRow)
+    irs_smooth_call c = positional_call(model, n_params, mode, T, N, x_trj, u_trj, sums, workspace, workspace_bytes);
+    c.At = At; c.Bt = Bt; c.ct = ct; c.info = info;
+    fill_args(a, c, g, true);
+    a.iter = iter;
+    const SmoothBatch bat{x_stride, u_stride, (long long)stride, reinterpret_cast<const unsigned long long*>(seed), std_u,
+                          std_x};
+    rc = irs_smooth_launch_batch(model, mode, a, bat, B, static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) {
+        irs_set_error("irs_smooth_rng_general_batch: no batched kernel for model %d, mode %d", model, mode);
+        return rc;
+    }
     IRS_CHECK_LAUNCH();
     return IRS_OK;
 }

@@ -46,6 +46,7 @@ struct SmoothBatch {
     long long ws_stride;                 // BYTES between the workspace slices (counters, fnom and partial move together)
     const unsigned long long* seed;      // DEV (B)
     const double* std_u;                 // DEV (B, m)
+    const double* std_x;                 // DEV (B, n): read by the modes that perturb the state too (null in the others)
 };
 struct SmoothSolo {};
 
@@ -56,6 +57,9 @@ int irs_smooth_finalize_launch(int model, int mode, const SmoothArgs& a, hipStre
 int irs_rng_samples_launch(int n, int m, float* dx, float* du, const SmoothArgs& a, hipStream_t st);
 int irs_exact_linearize_launch(int model, const ModelParams& p, const double* x_trj, const double* u_trj, double* At,
                                double* Bt, double* ct, int T, hipStream_t st);
+// the general sample pass over B problems (analytic models, the modes that perturb x and u; device-drawn samples,
+// fused solve)
+int irs_smooth_launch_batch(int model, int mode, const SmoothArgs& a, const SmoothBatch& bat, int B, hipStream_t st);
 
 // smooth_ug.hip: the uniform-geometry sample pass (exact 8-row contact models, u-only modes)
 bool irs_smooth_ug_supported(int model, int mode);
@@ -462,7 +466,8 @@ __device__ __forceinline__ void finalize_timestep(const ModelParams& p, const do
 // smooth_ug.hip (built without SLP vectorisation; certified by tests/test_smooth_batch_gpu.py).  The same entry in
 // front of smooth.hip's kernel did not give it: that unit is SLP-vectorised under -ffp-contract=fast, any change in
 // front of the body -- even this view holding unchanged copies -- moved which products the compiler fuses with which
-// sums deep inside the contact solve, and the f32 sums differed in their last bits.
+// sums deep inside the contact solve, and the f32 sums differed in their last bits.  The general kernel's
+// batched form (smooth_batch.hip: the analytic models) therefore promises equality up to f32 rounding only.
 struct SmoothRow {
     const ModelParams& p;
     const double* x_trj;
@@ -511,6 +516,11 @@ __device__ __forceinline__ SmoothRow smooth_batch_row(const SmoothArgs& a, const
 #pragma unroll
     for (int j = 0; j < m; ++j)
         r.std[n + j] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)bat.std_u[(size_t)b * m + j])));
+    if constexpr (TR::Z0 == 0) {         // the state is perturbed too (the u-only kernels compile nothing here)
+#pragma unroll
+        for (int i = 0; i < n; ++i)
+            r.std[i] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)bat.std_x[(size_t)b * n + i])));
+    }
     return r;
 }
 

@@ -1106,6 +1106,29 @@ __global__ __launch_bounds__(64) void descent_kernel(ModelParams p, RiccatiArgs 
     }
 }
 
+// descent_kernel with a problem index: grid B, workgroup b runs the same program -- backward pass, fence, closed-loop
+// rollout -- on problem b's blocks.  `a`, x0 and the outputs describe problem 0; Q, Qd, R, the model and T are shared.
+template <class Model>
+__global__ __launch_bounds__(64) void descent_batch_kernel(ModelParams p, RiccatiArgs a, const double* x0,
+                                                           double* x_new, double* u_new, double* cost_out) {
+    constexpr size_t n = Model::NX, m = Model::NU;
+    __shared__ RiccatiLds<Model::NX, Model::NU> S;
+    __shared__ RolloutLds<Model> S2;
+    const int lane = threadIdx.x;
+    __shared__ double qx[(Model::NX > 4 && Model::NX + 1 <= 16 && Model::NU <= 4) ? kQxMax : 1];
+    const size_t b = blockIdx.x, T = (size_t)a.T;
+    a.At += b * T * n * n; a.Bt += b * T * n * m; a.ct += b * T * n;
+    a.xd += b * (T + 1) * n;
+    a.K += b * T * m * n; a.k += b * T * m;
+    a.info += b;
+    riccati_backward_any<Model::NX, Model::NU>(a, lane, S, qx);
+    // the gains were stored by this very wave: drain the stores, then re-read them
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    rollout_device<Model>(p, a.T, a.K, a.k, nullptr, x0 + b * n, a.Q, a.R, a.xd, x_new + b * (T + 1) * n,
+                          u_new + b * T * m, cost_out + b, lane, S2);
+}
+
 // evaluate_cost of a given trajectory pair: lanes stride over t, f64 wave reduction.
 __global__ __launch_bounds__(64) void evaluate_cost_kernel(int n, int m, int T, const double* x_trj,
                                                            const double* u_trj, const double* Q,
@@ -1318,6 +1341,51 @@ int irs_tvlqr_descent(int model, const double* params, int n_params, int T, cons
                       void* stream) {
     return irs_tvlqr_descent_row(model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R, xd_trj, x0, K, k, x_new,
                                  u_new, cost, info, nullptr, nullptr, stream);
+}
+
+int irs_tvlqr_descent_batch(int model, const double* params, int n_params, int T, int B, const double* At,
+                            const double* Bt, const double* ct, const double* Q, const double* Qd,
+                            const double* R, double alpha_R, const double* xd_trj, const double* x0,
+                            double* K, double* k, double* x_new, double* u_new, double* cost, int* info,
+                            void* stream) {
+    // every argument error is decided before the first HIP call
+    IRS_CHECK_ARG(B > 0 && T > 0, "B and T must be positive");
+    IRS_CHECK_ARG(At && Bt && ct && Q && Qd && R && xd_trj && x0 && K && k && x_new && u_new && cost && info,
+                  "null pointer");
+    int n, m, np;
+    int rc = irs_model_info(model, &n, &m, &np);
+    if (rc != IRS_OK) {
+        irs_set_error("irs_tvlqr_descent_batch: unknown model id %d", model);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (model != IRS_MODEL_PENDULUM && model != IRS_MODEL_QUADROTOR && model != IRS_MODEL_BICYCLE &&
+        model != IRS_MODEL_THREE_CART) {
+        irs_set_error("irs_tvlqr_descent_batch: model %d is a contact model: its batched descent is "
+                      "irs_quasistatic_box_descent_batch", model);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (params == nullptr || n_params != np) {
+        irs_set_error("irs_tvlqr_descent_batch: model %d expects %d params, got %d", model, np, n_params);
+        return IRS_ERR_INVALID_ARG;
+    }
+    ModelParams p;
+    rc = irs_load_params(model, params, n_params, &p);
+    if (rc != IRS_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define IRS_DESCENT_BATCH(Model_)                                                                                       \
+    {                                                                                                                   \
+        RiccatiArgs a{At, Bt, ct, Q, Qd, R, xd_trj, K, k, info, alpha_R, Model_::NX, Model_::NU, T};                    \
+        hipLaunchKernelGGL((descent_batch_kernel<Model_>), dim3(B), dim3(64), 0, st, p, a, x0, x_new, u_new, cost);    \
+    }
+    switch (model) {
+        case IRS_MODEL_PENDULUM: IRS_DESCENT_BATCH(PendulumModel) break;
+        case IRS_MODEL_QUADROTOR: IRS_DESCENT_BATCH(QuadrotorModel) break;
+        case IRS_MODEL_BICYCLE: IRS_DESCENT_BATCH(BicycleModel) break;
+        default: IRS_DESCENT_BATCH(ThreeCartModel) break;
+    }
+#undef IRS_DESCENT_BATCH
+    IRS_CHECK_LAUNCH();
+    return IRS_OK;
 }
 
 }  // extern "C"

@@ -346,6 +346,90 @@ class DeviceModel(CemModelFree):
               "irs_tvlqr_descent")
         return o
 
+    # ---- B problems of an analytic model per launch ---------------------------------
+    def tvlqr_descent_batch(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, alpha_R=0.5, out=None):
+        """B descents in one launch (irs_tvlqr_descent_batch): problem b's outputs are, bit for bit, those of
+        tvlqr_descent on At[b], Bt[b], ct[b], xd_trj[b], x0[b] with the shared Q, Qd, R.  At (B,T,n,n), Bt (B,T,n,m),
+        ct (B,T,n), xd_trj (B,T+1,n), x0 (B,n).  Returns dict(K (B,T,m,n), k (B,T,m), x_new (B,T+1,n), u_new (B,T,m),
+        cost (B), info (B)); pass `out` to write into tensors of those shapes."""
+        B, T = At.shape[0], At.shape[1]
+        dev = At.device
+        n, m = self.n, self.m
+        for name, t, shape in (("At", At, (B, T, n, n)), ("Bt", Bt, (B, T, n, m)), ("ct", ct, (B, T, n)),
+                               ("xd_trj", xd_trj, (B, T + 1, n)), ("x0", x0, (B, n))):
+            assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+        shapes = dict(K=(B, T, m, n), k=(B, T, m), x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B,))
+        o = out if out is not None else self._tv_alloc(shapes, dev)
+        for name, shape in shapes.items():
+            assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
+        check(self.lib.irs_tvlqr_descent_batch(self.model_id, self._p, self._np, T, B, _ptr(At, F64), _ptr(Bt, F64),
+                                               _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
+                                               float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(o["K"], F64),
+                                               _ptr(o["k"], F64), _ptr(o["x_new"], F64), _ptr(o["u_new"], F64),
+                                               _ptr(o["cost"], F64), _ptr(o["info"], torch.int32), _stream()),
+              "irs_tvlqr_descent_batch")
+        return o
+
+    def plan_within_bounds_batch(self, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag=None):
+        """flag (B) int32: 1 where some tail plan of problem b leaves ITS box xlo, xhi (B,n), ulo, uhi (B,m) -- one
+        launch (irs_tvlqr_plan_within_bounds_batch), the single entry's decision per problem."""
+        B, T = At.shape[0], At.shape[1]
+        for name, t, shape in (("xlo", xlo, (B, self.n)), ("xhi", xhi, (B, self.n)), ("ulo", ulo, (B, self.m)),
+                               ("uhi", uhi, (B, self.m)), ("x_new", x_new, (B, T + 1, self.n)),
+                               ("K", K, (B, T, self.m, self.n)), ("k", k, (B, T, self.m))):
+            assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+        if flag is None:
+            flag = torch.empty((B,), dtype=torch.int32, device=At.device)
+        check(self.lib.irs_tvlqr_plan_within_bounds_batch(self.n, self.m, T, B, _ptr(At, F64), _ptr(Bt, F64),
+                                                          _ptr(ct, F64), _ptr(K, F64), _ptr(k, F64), _ptr(x_new, F64),
+                                                          _ptr(xlo, F64), _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64),
+                                                          _ptr(flag, torch.int32), _stream()),
+              "irs_tvlqr_plan_within_bounds_batch")
+        return flag
+
+    def smooth_general_batch_supported(self, mode):
+        """Whether smooth_rng_general_batch serves this model in `mode`: the analytic models in the modes that perturb
+        x and u (zero-order AB, first order)."""
+        return self.lib.irs_smooth_general_batch_workspace_bytes(self.model_id, int(mode), 1, 1, 1) > 0
+
+    def smooth_rng_general_batch(self, mode, X, U, N, std_x_dev, std_u_dev, seed_dev, it, out=None):
+        """The sample passes of B problems of an analytic model in one launch (irs_smooth_rng_general_batch): problem b
+        sees the draws of smooth_rng(mode, X[b], U[b], N, std_x[b], std_u[b], seed[b], it) and its results agree with
+        that call's up to f32 rounding (not bit for bit).  Arguments and result as smooth_rng_batch, plus std_x_dev
+        (B,n) f64 on the device."""
+        B = U.shape[0]
+        T = out["info"].shape[1] if out is not None else U.shape[1]
+        dev = U.device
+        for name, t, cols in (("X", X, self.n), ("U", U, self.m)):
+            assert t.is_cuda and t.dtype == F64 and t.dim() == 3 and t.shape[0] == B and t.shape[1] >= T, name
+            assert t.shape[2] == cols and t.stride(2) == 1 and t.stride(1) == cols, (name, t.shape, t.stride())
+            assert B == 1 or t.stride(0) >= T * cols, (name, t.stride())
+        assert tuple(std_x_dev.shape) == (B, self.n) and tuple(std_u_dev.shape) == (B, self.m)
+        assert tuple(seed_dev.shape) == (B,) and seed_dev.dtype == torch.int64 and seed_dev.is_cuda and seed_dev.is_contiguous()
+        shapes = self._tv_shapes((B, T), mode)
+        o = out if out is not None else self._tv_alloc(shapes, dev)
+        for name, shape in shapes.items():
+            assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
+        assert o["info"].dtype == torch.int32 and o["info"].is_contiguous()
+        need = self.lib.irs_smooth_general_batch_workspace_bytes(self.model_id, int(mode), T, int(N), B)
+        if need == 0:
+            raise NotImplementedError("smooth_rng_general_batch: model %d, mode %d is not served" % (self.model_id, mode))
+        key = ("smooth_general_batch", int(mode), T, int(N))  # one slice layout per buffer: the counters stay where they are
+        before = self._ws.get((key, dev))
+        ws = self._cached_workspace(key, need, dev)
+        if ws is not before:                                 # a fresh allocation: its counters are zeroed once
+            check(self.lib.irs_smooth_general_batch_workspace_init(ws.data_ptr(), ws.numel(), _stream()),
+                  "irs_smooth_general_batch_workspace_init")
+        xs = X.stride(0) if B > 1 else X.shape[1] * self.n
+        us = U.stride(0) if B > 1 else U.shape[1] * self.m
+        check(self.lib.irs_smooth_rng_general_batch(self.model_id, self._p, self._np, int(mode), T, int(N), B,
+                                                    X.data_ptr(), xs, U.data_ptr(), us, _ptr(std_x_dev, F64),
+                                                    _ptr(std_u_dev, F64), seed_dev.data_ptr(), int(it),
+                                                    _ptr(o["sums"], F64), _ptr(o["At"], F64), _ptr(o["Bt"], F64),
+                                                    _ptr(o["ct"], F64), o["info"].data_ptr(), ws.data_ptr(), ws.numel(),
+                                                    _stream()), "irs_smooth_rng_general_batch")
+        return o
+
     # ---- box-constrained descent ----------------------------------------------
     # the dynamic-LDS budget of the bounded-descent kernels (IRS_LDS_BUDGET in csrc/irs_common.hpp), for callers that
     # compare the size queries with it; every placement decision reads irs_box_horizon_limit instead

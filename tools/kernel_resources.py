@@ -13,9 +13,10 @@ import subprocess
 import sys
 
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=fast"
-SMOOTH_EXTRA = "-ffinite-math-only -fno-signed-zeros"       # csrc/Makefile: smooth.o, smooth_ug.o
+SMOOTH_EXTRA = "-ffinite-math-only -fno-signed-zeros"       # csrc/Makefile: smooth.o, smooth_batch.o, smooth_ug.o
 EXTRA = {                                                    # the per-unit flags of csrc/Makefile
     "smooth.hip": SMOOTH_EXTRA,
+    "smooth_batch.hip": SMOOTH_EXTRA,
     "smooth_ug.hip": SMOOTH_EXTRA + " -fno-slp-vectorize",
     "ctrlbox_mfma.hip": "-mllvm -amdgpu-mfma-vgpr-form=1 -fno-honor-nans -fno-signed-zeros",
 }
