@@ -24,8 +24,10 @@ template <typename T, int K> struct scalar_of<Dual<T, K>> { using type = T; };
 // f32 sine/cosine for the sample pass: branch-free (no large-argument slow path, so the
 // compiler can batch the sample loads around it), ~20 VALU instructions for the pair.
 // Quadrant reduction r = x - q*pi/2 by two FMAs against a hi/lo split of pi/2, then
-// the minimax polynomials on [-pi/4, pi/4].  Absolute error <= ~1.5e-7 for |x| < 1e3
-// (grows like 6e-8*|x|/1e3 beyond); the sample pass is held to an f32 tolerance.
+// the minimax polynomials on [-pi/4, pi/4].  Absolute error <= 1.5e-7 for |x| < 1e3 (asserted by
+// tests/test_functors_*.py; measured against long double: 9.3e-8 up to 1e5, 1.1e-7 up to 1e6).  NOT usable beyond: the
+// two-term split of pi/2 runs out (9.6e-5 by 1e7), and once r leaves the polynomials' interval the result is not even
+// bounded (|sin| = 87 by 1e8, inf further out).  The sample pass is held to an f32 tolerance.
 // sin/cos of q*pi/2 + r for |r| <= pi/4 (+ rounding), q an integer quadrant count.
 IRS_HD void irs_sincos_quadrant(float r, int qi, float& s, float& c);
 
@@ -53,7 +55,9 @@ IRS_HD void irs_sincos_quadrant(float r, int qi, float& s, float& c) {
 // reduction with a hi/lo split of pi/2 and the fdlibm kernel polynomials (k_sin.c /
 // k_cos.c coefficients, < 1 ulp on [-pi/4, pi/4]).  ~35 dependent f64 operations instead
 // of two ocml calls with large-argument paths: the rollout chain is latency-bound on this.
-// Accurate to ~1 ulp for |x| < 1e6.
+// Within 2 ulp for |x| < 1e6 (asserted by tests/test_functors_*.py; measured against long double: 1.57 ulp up to
+// 3e9).  The domain ends where the quadrant count leaves `int`: |x| >= 2^31 pi/2 ~ 3.37e9 converts out of range -- the
+// error is 2.0 absolute there, unbounded further out, and host and device convert differently.
 IRS_HD void irs_sincos(double x, double& s, double& c) {
     const double q = rint(x * 0.63661977236758134308);
     double r = fma(q, -1.57079632679489655800, x);              // pi/2 hi
