@@ -35,7 +35,8 @@ def run_batch(sysd, params, sm, N, iters, a):
                 size=params.u_trj_initial.shape)
         plist.append(p)
         smps.append(amd.GaussianSmoothing(sm["std_x"], sm["std_u"], N, power=sm["power"], seed=a.seed + b))
-    solver = amd.IrsLqrBatch(sysd, plist, a.method, None if a.method == "exact" else smps)
+    # bounded=True: a problem whose box bound binds takes the bounded descent, as the single class does
+    solver = amd.IrsLqrBatch(sysd, plist, a.method, None if a.method == "exact" else smps, bounded=True)
     t0 = time.time()
     solver.iterate(iters)
     for b in range(a.batch):

@@ -1003,6 +1003,37 @@ int irs_tvlqr_box_descent_if(int model, const double *params, int n_params, int 
                              double *x_new, double *u_new, double *cost, int *info, const int *run_flag,
                              void *stream);
 
+/* B bounded descents of the analytic models (pendulum, quadrotor, bicycle, three cart) in ONE launch: the kernel of
+ * irs_tvlqr_box_descent_if with a problem index, grid B, one 64-lane workgroup per problem (fixed penalty, every
+ * finite bound enforced).  Problem b's x_new, u_new, cost and info are, bit for bit, those of irs_tvlqr_box_descent_if
+ * (records on chip) / irs_tvlqr_box_descent_wsx (records in the workspace) on problem b's inputs.
+ * In (DEV f64, B contiguous blocks): At (B,T,n,n), Bt (B,T,n,m), ct (B,T,n), xd_trj (B,T+1,n), x0 (B,n), and each
+ *      problem's box xlo, xhi (B,n), ulo, uhi (B,m) (+-inf allowed: the shapes of irs_tvlqr_plan_within_bounds_batch);
+ *      shared: the model and its params, T, Q, Qd, R, alpha_R, rho, relax, max_iter, eps.
+ * Out: x_new (B,T+1,n), u_new (B,T,m), cost (B, may be NULL) DEV f64, info (B,3) DEV int32.
+ * run_flag (B) DEV int32, may be NULL = all run: workgroup b returns at once when run_flag[b] == 0, and nothing of
+ *      problem b is read or written.  A problem that fails (info[0] or info[2]) leaves its neighbours' bits alone.
+ * workspace: NULL = records on chip (the horizon must fit LDS, as for irs_tvlqr_box_descent); given (DEV, 256-byte
+ *      aligned), it is used at any horizon, as irs_tvlqr_box_descent_wsx does: problem b's records at
+ *      workspace + b * stride, stride = irs_box_records_bytes(model, T, IRS_BOX_ADMM) rounded up to 256.
+ * irs_tvlqr_box_descent_batch_workspace_bytes: B * stride; 0 for B <= 0, T <= 0, a model the batch does not serve,
+ *      and a horizon beyond irs_box_horizon_limit(model, IRS_BOX_ADMM).  No GPU.
+ * Every argument error is decided before the first HIP call:
+ *   IRS_ERR_INVALID_ARG  B <= 0, T <= 0, a null pointer (all but cost, run_flag, workspace), a bad ADMM parameter,
+ *                        wrong n_params
+ *   IRS_ERR_WORKSPACE    the workspace is smaller than B slices, or not 256-byte aligned
+ *   IRS_ERR_UNSUPPORTED  any other model; no workspace at a horizon whose records do not fit LDS; a horizon beyond
+ *                        the limit (the single entry's texts)                                                     */
+size_t irs_tvlqr_box_descent_batch_workspace_bytes(int model, int T, int B);
+int irs_tvlqr_box_descent_batch(int model, const double *params, int n_params, int T, int B,
+                                const double *At, const double *Bt, const double *ct,
+                                const double *Q, const double *Qd, const double *R, double alpha_R,
+                                const double *xd_trj, const double *x0,
+                                const double *xlo, const double *xhi, const double *ulo, const double *uhi,
+                                double rho, double relax, int max_iter, double eps,
+                                double *x_new, double *u_new, double *cost, int *info, const int *run_flag,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- the multi-GPU smoothing step inside the library (csrc/collective.hip) ------------------------------
  * One process per GPU; samples sharded over the ranks; per step: sample pass -> ONE all-reduce of the
  * (T,P) f64 statistics (RCCL over xGMI) -> solve (every rank, redundantly).  Replaces the reference's ZeroMQ

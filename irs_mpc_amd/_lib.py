@@ -202,6 +202,10 @@ SIGNATURES["irs_tvlqr_descent_batch"] = (c_int, [c_int, POINTER(c_double), c_int
                                                  c_double, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, c_void_p])
 SIGNATURES["irs_tvlqr_plan_within_bounds_batch"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                                             _dp, _dp, _dp, _dp, c_void_p])
+SIGNATURES["irs_tvlqr_box_descent_batch_workspace_bytes"] = (c_size_t, [c_int, c_int, c_int])
+SIGNATURES["irs_tvlqr_box_descent_batch"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, c_int, _dp, _dp, _dp, _dp, _dp,
+                                                     _dp, c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_double, c_double, c_int,
+                                                     c_double, _dp, _dp, _dp, _dp, _dp, _dp, c_size_t, c_void_p])
 SIGNATURES["irs_quasistatic_bound_rows_batch"] = (c_int, [c_int, c_int, c_int, c_int, _dp, _dp, _dp, c_int, c_int, _dp, _dp,
                                                           c_void_p])
 SIGNATURES["irs_tvlqr_box_solve"] = (c_int, [c_int, POINTER(c_double), c_int, c_int, _dp, _dp, _dp, _dp, _dp, _dp, c_double,

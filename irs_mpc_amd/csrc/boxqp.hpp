@@ -91,8 +91,22 @@ struct BoxAdaptLazy : BoxAdapt {
 // The caller has checked the ADMM settings (irs_admm_settings_ok), as every entry does before anything else.
 // adapt: null = fixed rho; else the adaptive form of the kernel (checked by the caller: irs_admm_adapt_ok).
 // lazy: null = every finite bound enforced; else the lazy form (adapt must be given: max_refactor = 0 for a fixed rho).
+// batch_B = 0: the single problem `a`, one workgroup.  batch_B >= 1: the batched kernel over that many problems, one
+// workgroup each (the plain fixed-penalty form of an analytic model only: du false, adapt and lazy null) -- every
+// per-problem array of `a` is B contiguous blocks, the bound rows (B,n) / (B,m) and run_flag (B) included; Q / Qd / R
+// and the scalars are shared; records in HBM: problem b's at ws + b * round256(records).  Its workspace errors are
+// worded with `fn` and are IRS_ERR_WORKSPACE.
 int irs_box_admm_launch(const char* fn, int model, bool du, const BoxArgs& a, void* ws, size_t ws_bytes, BoxWs policy,
-                        hipStream_t st, const BoxAdapt* adapt = nullptr, const BoxLazy* lazy = nullptr);
+                        hipStream_t st, const BoxAdapt* adapt = nullptr, const BoxLazy* lazy = nullptr, int batch_B = 0);
+// boxqp_batch.hip: the batched instantiations of the kernel (boxqp_kernel.inc with a problem index), launched as planned
+// -- AdmmLds, or AdmmHbm with problem b's records at ws + b * ws_stride bytes.  Called by irs_box_admm_launch alone.
+int irs_box_admm_launch_batch(int model, const BoxArgs& a, const BoxPlan& p, double* ws, int B, size_t ws_stride,
+                              hipStream_t st);
+// the models the batched ADMM kernel is instantiated for: the analytic ones (IrsLqrBatch's)
+inline bool irs_box_batch_model(int model) {
+    return model == IRS_MODEL_PENDULUM || model == IRS_MODEL_QUADROTOR || model == IRS_MODEL_BICYCLE ||
+           model == IRS_MODEL_THREE_CART;
+}
 
 // ctrlbox.hip: active-set solver for the quasistatic descent with ONE control box.
 // kind 0: bounds on u_t (a.ulo/a.uhi), kind 1: bounds on u_t - u_{t-1} (a.dlo/a.dhi); a bound pair

@@ -31,6 +31,7 @@ struct BoxCall {
     const int* run_flag;
     double* act_io;
     const BoxLazy* lazy;             // null: every finite bound enforced
+    int batch;                       // 0: one problem; B > 0: that many, every per-problem array B contiguous blocks
     const char* solver_error;        // non-null: the entry's solver argument is refused, in these words
     void* stream;
 };
@@ -60,13 +61,14 @@ irs_admm_settings fixed_rho(double rho, double relax, int max_iter, double eps) 
 }
 
 // a workspace the records must go to (the _wsx entries of the ADMM kernel): 256-byte aligned, large enough
-int check_box_workspace(const char* fn, int model, int T, int du, const void* ws, size_t ws_bytes) {
+// batch > 0: one slice per problem, and both complaints are IRS_ERR_WORKSPACE
+int check_box_workspace(const char* fn, int model, int T, int du, const void* ws, size_t ws_bytes, int batch) {
     if (ws == nullptr) return IRS_OK;
     const BoxPlan p = irs_box_plan(model, T, du ? IRS_BOX_ADMM_DU : IRS_BOX_ADMM, BoxWs::Always);
-    const WsFit f = ws_fit(p, 1, ws, ws_bytes);
+    const WsFit f = ws_fit(p, batch > 0 ? (size_t)batch : 1, ws, ws_bytes);
     if (f.misaligned) {
         irs_set_error("%s: the workspace must be 256-byte aligned", fn);
-        return IRS_ERR_INVALID_ARG;
+        return batch > 0 ? IRS_ERR_WORKSPACE : IRS_ERR_INVALID_ARG;
     }
     if (p.max_T == 0) {
         irs_set_error("%s: model %d has no %s form", fn, model, du ? "position-controlled" : "plain");
@@ -162,8 +164,18 @@ int box_call_args(const BoxCall& c, BoxArgs* a, BoxAdapt* ad, const BoxAdapt** a
     if (!(c.du || c.dlo == nullptr)) return refuse("du bounds need the position-controlled form");
     int rc = read_admm_settings(c.fn, c.settings, c.adapt_out, ad, adapt);
     if (rc != IRS_OK) return rc;
+    if (c.batch > 0 && !irs_box_batch_model(c.model)) {
+        irs_set_error("%s: model %d has no batched bounded descent (served: the pendulum, the quadrotor, the bicycle and "
+                      "the three carts; a contact model's is irs_quasistatic_box_descent_batch)", c.fn, c.model);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    int np = 0;
+    if (c.batch > 0 && (irs_model_info(c.model, nullptr, nullptr, &np) != IRS_OK || c.params == nullptr || c.n_params != np)) {
+        irs_set_error("%s: model %d expects %d params, got %d", c.fn, c.model, np, c.n_params);
+        return IRS_ERR_INVALID_ARG;
+    }
     if (c.policy == BoxWs::Always) {
-        rc = check_box_workspace(c.fn, c.model, c.T, c.du ? 1 : 0, c.ws, c.ws_bytes);
+        rc = check_box_workspace(c.fn, c.model, c.T, c.du ? 1 : 0, c.ws, c.ws_bytes, c.batch);
         if (rc != IRS_OK) return rc;
     }
     rc = box_fill(c, a);
@@ -173,8 +185,9 @@ int box_call_args(const BoxCall& c, BoxArgs* a, BoxAdapt* ad, const BoxAdapt** a
 }
 
 int box_call_launch(const BoxCall& c, const BoxArgs& a, const BoxAdapt* adapt) {
-    return irs_box_admm_launch(kFormName[(int)c.form], c.model, c.du, a, c.ws, c.ws_bytes, c.policy,
-                               static_cast<hipStream_t>(c.stream), adapt, c.lazy);
+    // (a batch words the launch's errors with its own name: its workspace is B slices)
+    return irs_box_admm_launch(c.batch > 0 ? c.fn : kFormName[(int)c.form], c.model, c.du, a, c.ws, c.ws_bytes, c.policy,
+                               static_cast<hipStream_t>(c.stream), adapt, c.lazy, c.batch);
 }
 
 int box_call(const BoxCall& c) {
@@ -271,6 +284,29 @@ int irs_tvlqr_box_descent_set(int model, const double* params, int n_params, int
                             xd_trj, x0, xlo, xhi, ulo, uhi, nullptr, nullptr, settings, x_new, u_new, nullptr, info,
                             workspace, workspace_bytes, BoxWs::Always, stream);
     c.adapt_out = adapt_out;
+    return box_call(c);
+}
+
+// B descents of an analytic model in one launch: the call record of irs_tvlqr_box_descent_if / _wsx plus a batch count
+size_t irs_tvlqr_box_descent_batch_workspace_bytes(int model, int T, int B) {
+    if (T <= 0 || B <= 0 || !irs_box_batch_model(model)) return 0;
+    const BoxPlan p = irs_box_plan(model, T, IRS_BOX_ADMM, BoxWs::Always);
+    return p.place == BoxPlace::AdmmHbm ? (size_t)B * round256(p.records) : 0;      // (None: beyond the horizon limit)
+}
+
+int irs_tvlqr_box_descent_batch(int model, const double* params, int n_params, int T, int B, const double* At,
+                                const double* Bt, const double* ct, const double* Q, const double* Qd, const double* R,
+                                double alpha_R, const double* xd_trj, const double* x0, const double* xlo,
+                                const double* xhi, const double* ulo, const double* uhi, double rho, double relax,
+                                int max_iter, double eps, double* x_new, double* u_new, double* cost, int* info,
+                                const int* run_flag, void* workspace, size_t workspace_bytes, void* stream) {
+    IRS_CHECK_ARG(B > 0, "B must be positive");
+    const irs_admm_settings s = fixed_rho(rho, relax, max_iter, eps);
+    BoxCall c = box_problem(__func__, BoxForm::Descent, false, model, params, n_params, T, At, Bt, ct, Q, Qd, R, alpha_R,
+                            xd_trj, x0, xlo, xhi, ulo, uhi, nullptr, nullptr, &s, x_new, u_new, cost, info, workspace,
+                            workspace_bytes, BoxWs::Always, stream);
+    c.run_flag = run_flag;
+    c.batch = B;
     return box_call(c);
 }
 

@@ -387,6 +387,41 @@ class DeviceModel(CemModelFree):
               "irs_tvlqr_plan_within_bounds_batch")
         return flag
 
+    def tvlqr_box_descent_batch(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, xlo, xhi, ulo, uhi, alpha_R=0.5, rho=10.0,
+                                relax=1.6, max_iter=5000, eps=1e-8, run_flag=None, records_in_hbm=False, out=None):
+        """B bounded descents in one launch (irs_tvlqr_box_descent_batch): problem b's outputs are, bit for bit, those
+        of irs_tvlqr_box_descent_if on problem b's blocks and ITS box xlo, xhi (B,n), ulo, uhi (B,m), with the shared
+        Q, Qd, R and ADMM settings.  run_flag (B) int32 or None: problem b is neither read nor written where
+        run_flag[b] == 0.  Beyond the LDS horizon the factor records go to a cached workspace, one slice per problem;
+        records_in_hbm=True puts them there at any horizon (same bits).  Returns dict(x_new (B,T+1,n), u_new (B,T,m),
+        cost (B), info (B,3)); pass `out` to write into tensors of those shapes."""
+        B, T = At.shape[0], At.shape[1]
+        dev = At.device
+        n, m = self.n, self.m
+        for name, t, shape in (("At", At, (B, T, n, n)), ("Bt", Bt, (B, T, n, m)), ("ct", ct, (B, T, n)),
+                               ("xd_trj", xd_trj, (B, T + 1, n)), ("x0", x0, (B, n)), ("xlo", xlo, (B, n)),
+                               ("xhi", xhi, (B, n)), ("ulo", ulo, (B, m)), ("uhi", uhi, (B, m))):
+            assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+        assert run_flag is None or tuple(run_flag.shape) == (B,), tuple(run_flag.shape)
+        shapes = dict(x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B, 3))
+        o = out if out is not None else self._tv_alloc(shapes, dev)
+        for name, shape in shapes.items():
+            assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
+        ws = None
+        if records_in_hbm or self.lib.irs_tvlqr_box_workspace_bytes(self.model_id, T, 0) > 0:
+            need = self.lib.irs_tvlqr_box_descent_batch_workspace_bytes(self.model_id, T, B)
+            ws = self._cached_workspace("box_batch", need, dev)
+        check(self.lib.irs_tvlqr_box_descent_batch(self.model_id, self._p, self._np, T, B, _ptr(At, F64), _ptr(Bt, F64),
+                                                   _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
+                                                   float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(xlo, F64),
+                                                   _ptr(xhi, F64), _ptr(ulo, F64), _ptr(uhi, F64), float(rho),
+                                                   float(relax), int(max_iter), float(eps), _ptr(o["x_new"], F64),
+                                                   _ptr(o["u_new"], F64), _ptr(o["cost"], F64),
+                                                   _ptr(o["info"], torch.int32), _ptr(run_flag, torch.int32),
+                                                   *_ws_args(ws), _stream()),
+              "irs_tvlqr_box_descent_batch")
+        return o
+
     def smooth_general_batch_supported(self, mode):
         """Whether smooth_rng_general_batch serves this model in `mode`: the analytic models in the modes that perturb
         x and u (zero-order AB, first order)."""

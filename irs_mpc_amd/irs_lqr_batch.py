@@ -9,15 +9,22 @@ those descents queue on a single wave.  Here an iteration of all B problems is
                          `irs_exact_linearize` on the stacked (B T) nominal points,
     one descent launch   `irs_tvlqr_descent_batch` (the descent kernel with a problem index, one workgroup each),
     one plan-test launch `irs_tvlqr_plan_within_bounds_batch`, when any problem has a finite bound,
+    (bounded=True)       one bounded-descent launch `irs_tvlqr_box_descent_batch` behind the plan test's flags: the
+                         ADMM kernel of the single classes with a problem index, one workgroup each; a problem whose
+                         plan stays inside its box, or that has stopped, returns at once,
     and the adoption     a masked copy,
 
 enqueued back to back without a device synchronisation; the histories are read back once at the end.
 
 The problems share the system, `T`, `Q`, `Qd`, `R`, and the sampling's `num_samples` and `power`; they may differ in
-`x0`, `xd_trj`, `u_trj_initial`, the bounds, and their `GaussianSmoothing`'s seed, `std_x` and `std_u`.  Descents are
-the unbounded ones (Riccati): a problem whose plan leaves its box at some descent -- a bound that is genuinely active
--- stops adopting there and `status[b]` says how to run it; so does one whose Riccati pass or smoothing solve failed,
-with the message the single class raises.  The other problems finish.
+`x0`, `xd_trj`, `u_trj_initial`, the bounds, and their `GaussianSmoothing`'s seed, `std_x` and `std_u`.
+
+bounded=False (the default): descents are the unbounded ones (Riccati): a problem whose plan leaves its box at some
+descent -- a bound that is genuinely active -- stops adopting there and `status[b]` says how to run it.
+bounded=True: that problem's descent is the single class's bounded one (T warm-started tail QPs by ADMM, fixed penalty;
+`qp_rho`, `qp_max_iter`, `qp_eps` shared by the problems), it keeps `status[b] is None` and runs to the end; it stops
+only where a bounded QP is not solved, with the single class's message.  Either way a problem whose Riccati pass or
+smoothing solve failed stops with the message the single class raises, and the other problems finish.
 """
 import numpy as np
 import torch
@@ -42,8 +49,19 @@ def _bound_active(single):
             "with %s, whose bounded descent (irs_tvlqr_box_descent) enforces it" % single)
 
 
+def _horizon_beyond_limit(T, limit):
+    # IrsLqr.local_descent's text (irs_lqr.py)
+    return ("a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
+            "(factor records in HBM, ADMM vectors in LDS; tv_lqr.py:112-123)" % (T, limit))
+
+
+# the bounded QPs' ADMM settings, shared by the problems of a launch: the field and the single class's default
+QP_SETTINGS = (("qp_rho", 10.0), ("qp_max_iter", 5000), ("qp_eps", 1e-8))
+QP_RELAX = 1.6
+
+
 class IrsLqrBatch:
-    def __init__(self, system, params_list, order, sampling_list=None):
+    def __init__(self, system, params_list, order, sampling_list=None, bounded=False):
         ps = list(params_list)
         if not ps:
             raise ValueError("params_list is empty")
@@ -68,6 +86,14 @@ class IrsLqrBatch:
             for field in ("Q", "Qd", "R"):
                 if not np.array_equal(np.asarray(getattr(p, field), float), np.asarray(getattr(p0, field), float)):
                     raise ValueError("params_list[%d].%s differs from params_list[0].%s" % (b, field, field))
+        self.bounded = bool(bounded)
+        self._qp = {field: getattr(p0, field, default) for field, default in QP_SETTINGS}
+        if self.bounded:
+            for b, p in enumerate(ps[1:], 1):
+                for field, default in QP_SETTINGS:
+                    if getattr(p, field, default) != self._qp[field]:
+                        raise ValueError("params_list[%d].%s differs from params_list[0].%s: the bounded descents of a "
+                                         "launch share their ADMM settings" % (b, field, field))
         self.mode, self._single = ORDERS[order]
         if self.mode is None:
             if sampling_list is not None:
@@ -109,6 +135,8 @@ class IrsLqrBatch:
             boxes.append(pr._box_host)
         self._box = None
         if any(np.isfinite(v).any() for box in boxes for v in box):
+            if self.bounded and not self._dm.box_descent_supported(T):
+                raise NotImplementedError(_horizon_beyond_limit(T, self._dm.box_horizon_limit()))
             self._box = tuple(dev.to_dev(np.stack([box[i] for box in boxes])) for i in range(4))
         if smps is not None:
             seeds = np.array([int(s.seed) & 0xFFFFFFFFFFFFFFFF for s in smps], dtype=np.uint64)
@@ -173,6 +201,8 @@ class IrsLqrBatch:
         dinfo = torch.empty((D, B), dtype=torch.int32, device=device)
         flags = torch.zeros((D, B), dtype=torch.int32, device=device)
         sinfo = torch.zeros((D, B, T), dtype=torch.int32, device=device)
+        bounded = self.bounded and self._box is not None     # no finite bound anywhere: nothing more than the Riccati loop
+        binfo = torch.zeros((D, B, 3), dtype=torch.int32, device=device)       # rows a bounded descent did not write: 0
         K = torch.empty((B, T, m, n), dtype=dev.F64, device=device)
         k = torch.empty((B, T, m), dtype=dev.F64, device=device)
         lin = {}
@@ -189,14 +219,30 @@ class IrsLqrBatch:
                                    out=dict(K=K, k=k, x_new=xs[d], u_new=us[d], cost=costs[d], info=dinfo[d]))
             if self._box is not None:
                 dm.plan_within_bounds_batch(lin["At"], lin["Bt"], lin["ct"], K, k, xs[d], *self._box, flag=flags[d])
+            if not bounded and d + 1 == D:
+                break                                        # the last descent is logged, not adopted
+            # go: alive, and this descent's Riccati pass and smoothing solve succeeded
+            go = alive & (dinfo[d] == 0) & ~(sinfo[d] != 0).any(dim=1)
+            solved = flags[d] == 0
+            if bounded:
+                # the bounded descents of the problems whose plan leaves its box, behind their flags: they overwrite
+                # this descent's rows of the histories; a stopped problem's workgroup returns at once
+                dm.tvlqr_box_descent_batch(lin["At"], lin["Bt"], lin["ct"], self._Q, self._Qd, self._R, self._xd, x0,
+                                           *self._box, alpha_R=0.5, rho=self._qp["qp_rho"], relax=QP_RELAX,
+                                           max_iter=self._qp["qp_max_iter"], eps=self._qp["qp_eps"],
+                                           run_flag=flags[d] * go.to(torch.int32),
+                                           out=dict(x_new=xs[d], u_new=us[d], cost=costs[d], info=binfo[d]))
+                solved = solved | ((binfo[d, :, 0] == 0) & (binfo[d, :, 2] == 0))
             if d + 1 < D:
                 # adoption: a problem goes on from its new trajectory unless this descent, or an earlier one, stopped it
-                alive = alive & (dinfo[d] == 0) & (flags[d] == 0) & ~(sinfo[d] != 0).any(dim=1)
+                alive = go & solved
                 keep = alive[:, None, None]
                 X, U = torch.where(keep, xs[d], X), torch.where(keep, us[d], U)
         xs_h, us_h, cs_h = xs.cpu().numpy(), us.cpu().numpy(), costs.cpu().numpy()        # the one read-back
         dinfo_h, flags_h, sbad_h = dinfo.cpu().numpy(), flags.cpu().numpy(), (sinfo != 0).any(dim=2).cpu().numpy()
-        self._last = dict(At=lin["At"], Bt=lin["Bt"], ct=lin["ct"], K=K, k=k, info=dinfo[D - 1], flag=flags[D - 1])
+        binfo_h = binfo.cpu().numpy()
+        self._last = dict(At=lin["At"], Bt=lin["Bt"], ct=lin["ct"], K=K, k=k, info=dinfo[D - 1], flag=flags[D - 1],
+                          box_info=binfo[D - 1])
         for b, pr in enumerate(self.problems):
             if self.status[b] is not None:
                 continue                                     # stopped in an earlier call: frozen at its last adopted state
@@ -206,8 +252,10 @@ class IrsLqrBatch:
                     self.status[b] = RICCATI_FAILED
                 elif sbad_h[i, b]:
                     self.status[b] = SMOOTHING_FAILED
-                elif flags_h[i, b] != 0:
+                elif flags_h[i, b] != 0 and not bounded:
                     self.status[b] = _bound_active(self._single)
+                elif flags_h[i, b] != 0 and (binfo_h[i, b, 0] != 0 or binfo_h[i, b, 2] != 0):
+                    self.status[b] = RICCATI_FAILED          # the single class's message for an unsolved bounded QP
                 if self.status[b] is not None:
                     break
                 pr.x_trj_lst.append(xs_h[i, b])

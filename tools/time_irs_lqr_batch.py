@@ -4,6 +4,10 @@ B = 1 ... 512 beside B x the single-problem calls measured in the same run, at t
 N=1e4, quadrotor T=50 N=1e4.
 
     python tools/time_irs_lqr_batch.py [pendulum|quadrotor] [--B 1,8,64,256,512] [--order zero_order|first_order]
+    python tools/time_irs_lqr_batch.py bounded [--B 1,8,64,256,512] [--max-singles K] [--reps 3]
+
+`bounded`: B bounded descents in one launch (irs_tvlqr_box_descent_batch, records on chip and forced to HBM) beside
+the single entry (irs_tvlqr_box_descent_if) on the same inputs, on the example script's bicycle problem (T = 100).
 
 What is timed: a window of back-to-back enqueues between two device events, long enough to last some tens of
 milliseconds (the count comes from a pilot window), after a warm-up of the same calls; the figure is the median of 5
@@ -121,12 +125,84 @@ class Batch:
             self.flag.data_ptr(), dev._stream()), "irs_tvlqr_plan_within_bounds")
 
 
+class Bounded:
+    """B copies of the example script's bicycle problem (T = 100, steer bound; examples/run.py --batch: problem b starts
+    from u_trj_initial + 0.01 N(0,1) drawn with seed b, problem 0 from the script's), linearised exactly along the
+    rollout of their guesses: the inputs of the first bounded descent of `examples/run.py bicycle exact --batch B`."""
+
+    def __init__(self, B, T=100):
+        system, p, _, _, _ = PROBLEMS["bicycle"](T)
+        self.dm, self.B, self.T = system.dm(), B, T
+        dm, n, m = self.dm, system.dim_x, system.dim_u
+        U = np.stack([np.asarray(p.u_trj_initial, float)
+                      + (0.01 * np.random.default_rng(b).normal(size=(T, m)) if b > 0 else 0.0) for b in range(B)])
+        self.Q, self.Qd, self.R = (dev.to_dev(np.asarray(a, float)) for a in (p.Q, p.Qd, p.R))
+        self.xd = dev.to_dev(np.tile(np.asarray(p.xd_trj, float), (B, 1, 1)))
+        self.x0 = dev.to_dev(np.tile(np.asarray(p.x0, float), (B, 1)))
+        Ud = dev.to_dev(U)
+        X = torch.stack([dm.rollout_cost(self.x0[b], Ud[b], self.Q, self.R, self.xd[b])[0] for b in range(B)])
+        At, Bt, ct = dm.exact_linearize(X[:, :T].reshape(B * T, n), Ud.reshape(B * T, m))
+        self.lin = (At.view(B, T, n, n).contiguous(), Bt.view(B, T, n, m).contiguous(), ct.view(B, T, n).contiguous())
+        self.box = [dev.to_dev(np.broadcast_to(np.asarray(v, float), (B, d)).copy())
+                    for v, d in ((p.xbound[0], n), (p.xbound[1], n), (p.ubound[0], m), (p.ubound[1], m))]
+        self.out = dm._tv_alloc(dict(x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B, 3)), "cuda")
+
+    def batch(self, hbm):
+        self.dm.tvlqr_box_descent_batch(*self.lin, self.Q, self.Qd, self.R, self.xd, self.x0, *self.box,
+                                        records_in_hbm=hbm, out=self.out)
+
+    def single(self, b):
+        """irs_tvlqr_box_descent_if on problem b's blocks, into problem b's rows of the outputs."""
+        dm, o = self.dm, self.out
+        ptr = [t[b].data_ptr() for t in self.lin] + [t.data_ptr() for t in (self.Q, self.Qd, self.R)]
+        _lib.check(dm.lib.irs_tvlqr_box_descent_if(
+            dm.model_id, dm._p, dm._np, self.T, *ptr, 0.5, self.xd[b].data_ptr(), self.x0[b].data_ptr(),
+            *[t[b].data_ptr() for t in self.box], 10.0, 1.6, 5000, 1e-8, o["x_new"][b].data_ptr(), o["u_new"][b].data_ptr(),
+            o["cost"][b:b + 1].data_ptr(), o["info"][b].data_ptr(), None, dev._stream()), "irs_tvlqr_box_descent_if")
+
+
+def launch_us(fn, reps=3):
+    """[us] of one fn() between two device events: median, min, max of `reps` after one warm-up.  A bounded descent lasts
+    milliseconds to seconds, far above the event resolution, so every launch is a window of its own."""
+    fn()
+    torch.cuda.synchronize()
+    us = [1e3 * window_ms(fn, 1) for _ in range(reps)]
+    return float(np.median(us)), min(us), max(us)
+
+
+def bounded_rows(Bs, max_singles, reps=3):
+    """Per B: the batched launch with its records on chip and forced to HBM, beside the single entry on the same inputs
+    -- every problem alone, once, between its own events after a warm-up (`singles`: their sum, i.e. the calls back to
+    back without the launch gaps; the slowest one is what the batch has to wait for).  Beyond max_singles problems only
+    the first max_singles are run alone, and the row says so."""
+    print("bicycle T=100 bounded descent (steer bound); us per launch as median [min .. max] of %d launches" % reps,
+          flush=True)
+    for B in Bs:
+        b = Bounded(B)
+        K = min(B, max_singles)
+        b.single(0)
+        each = [1e3 * window_ms(lambda q=q: b.single(q), 1) for q in range(K)]
+        info1 = b.out["info"].cpu().numpy()[:K].copy()
+        lds, hbm = launch_us(lambda: b.batch(False), reps), launch_us(lambda: b.batch(True), reps)
+        info = b.out["info"].cpu().numpy()
+        assert np.array_equal(info[:K], info1), "the batch and the singles disagree on info"
+        print("B=%-4d on chip %s   in HBM %s   %d singles: sum %11.1f  slowest %9.1f  fastest %9.1f"
+              "   most ADMM iterations %d   unsolved %d"
+              % (B, fmt(lds), fmt(hbm), K, sum(each), max(each), min(each), int(info[:, 1].max()),
+                 int(((info[:, 2] != 0) | (info[:, 0] != 0)).sum())), flush=True)
+        del b
+        torch.cuda.empty_cache()
+
+
 def main():
     argv = sys.argv[1:]
 
     def option(name, default):
         return argv[argv.index(name) + 1] if name in argv else default
 
+    if "bounded" in argv:
+        return bounded_rows([int(v) for v in option("--B", "1,8,64,256,512").split(",")],
+                            int(option("--max-singles", "512")), int(option("--reps", "3")))
     names = [v for v in argv if v in SIZES] or list(SIZES)
     Bs = [int(v) for v in option("--B", "1,8,64,256,512").split(",")]
     order = option("--order", "zero_order")
