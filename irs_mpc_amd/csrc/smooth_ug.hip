@@ -35,6 +35,7 @@
 // (lane c owns contact row c; an 8x8 masked LDL' spread over the 64 lanes), from the f32 pipeline's active set,
 // re-checked against the KKT conditions in f64.
 #include "smooth_common.hpp"
+#include "ug_geometry.hpp"
 
 namespace {
 
@@ -603,34 +604,34 @@ struct UgNomLds {
 
 // (a) the f64 geometry: independent of the f32 prologue and of the table, so the nominal wave runs it BEFORE the
 // workgroup's first barrier, beside wave 0's f32 assembly.  Leaves J, q, D^-1, b in LDS and returns r_c on lane c.
+// The assembly is spread over the lanes (ug_geometry.hpp): lane c holds row c of J and element c of q, D^-1, b.
 template <class Model, class Args>
 __device__ __forceinline__ double ug_nominal_geometry(const Args& a, UgNomLds& L, int t, int lane) {
     constexpr int NC = Model::NC, n = Model::NX, m = Model::NU;
-    double x64[n], u64[m], q[n], Dinv[n], b[n], J[NC][n], phi[NC];
+    static_assert(std::is_base_of<PlanarHandModel, Model>::value && NC == 8, "ug_hand_geometry is the planar hand's assembly");
+    double x64[n], u64[m];
 #pragma unroll
     for (int i = 0; i < n; ++i) x64[i] = a.x_trj[(size_t)t * n + i];
 #pragma unroll
     for (int j = 0; j < m; ++j) u64[j] = a.u_trj[(size_t)t * m + j];
-    Model::template assemble<double>(a.p, x64, u64, q, Dinv, b, J, phi);
-    if (lane == 0) {
+    UgHandLane<double> g;
+    ug_hand_geometry<double>(a.p, x64, u64, lane, g);
+    if (lane < NC) {
 #pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int k = 0; k < n; ++k) L.J[c][k] = J[c][k];
-#pragma unroll
-        for (int k = 0; k < n; ++k) { L.q[k] = q[k]; L.Dinv[k] = Dinv[k]; L.b[k] = b[k]; }
+        for (int k = 0; k < n; ++k) L.J[lane][k] = g.J[k];
     }
-    // r_c on lane c (phi is the only per-row quantity not in LDS)
-    double rr = 0.0;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        double s = phi[c];
-#pragma unroll
-        for (int k = 0; k < n; ++k) s -= J[c][k] * (b[k] * Dinv[k]);
-        rr = (lane == c) ? s : rr;
-    }
+    if (lane < n) { L.q[lane] = g.q; L.Dinv[lane] = g.Dinv; L.b[lane] = g.b; }
+    // r_c = phi_c - sum_k J[c][k] (b_k D^-1_k) on lane c, over the k whose b is not zero, in ascending order: the
+    // object's weight (k = 1) and the two joints of the row's arm (a row of link 0 has a zero at the second)
+    const double bD = g.b * g.Dinv;
+    const double bD1 = __shfl(bD, 1, 64), bD3 = __shfl(bD, 3, 64), bD4 = __shfl(bD, 4, 64), bD5 = __shfl(bD, 5, 64),
+                 bD6 = __shfl(bD, 6, 64);
+    const bool arm1 = (lane & 4) != 0;
+    double s = fma(-bD1, g.J[1], g.phi);
+    s = fma(-(arm1 ? bD5 : bD3), arm1 ? g.J[5] : g.J[3], s);
+    s = fma(-(arm1 ? bD6 : bD4), arm1 ? g.J[6] : g.J[4], s);
     wave_sync();
-    return rr;
+    return lane < NC ? s : 0.0;
 }
 
 // (b) after the table exists: the f32 pipeline's active set at du = 0, then the cooperative f64 solve and its check
@@ -728,7 +729,8 @@ __device__ __forceinline__ void ug_nominal(const Args& a, const UgUni<Model::NC>
 }
 
 // -DIRS_UG_STAMPS (tuning builds only): s_memtime at the phase boundaries of every workgroup -> a device buffer that
-// irs_debug_ug_stamps copies out (tests/tools/ug_stamps.py)
+// irs_debug_ug_stamps copies out (tests/tools/ug_stamps.py; tools/ug_prologue_stamps.py prints the prologue's slots:
+// 6 = wave 0's first fresh trip done, 10 = the nominal wave's f64 geometry done)
 #ifdef IRS_UG_STAMPS
 constexpr int kUgStampSlots = 12, kUgStampWgs = 2048;
 __device__ unsigned long long ug_stamps[kUgStampWgs * kUgStampSlots];
@@ -761,31 +763,39 @@ __device__ unsigned ug_counts[3];
 
 // The workgroup's prologue: the f32 geometry of the step QP at (x, u) (wave 0), what follows from it (W, r0, J D^-1, C:
 // one quantity per thread) and the table (everyone; `build` false skips it: timing experiments).  Ends on a barrier.
-template <class Model, bool UCOL>
+// `early` runs in every thread once wave 0 has issued its loads of x and u: the place for memory requests of the
+// caller's that should be in flight during the prologue without standing in front of those loads.
+template <class Model, bool UCOL, class Early>
 __device__ __forceinline__ void ug_prologue(const ModelParams& p, const double* x, const double* u, bool build,
-                                            UgLds<Model>& S, int tid) {
+                                            UgLds<Model>& S, int tid, Early early) {
     constexpr int n = Model::NX, m = Model::NU, NC = Model::NC;
+    static_assert(std::is_base_of<PlanarHandModel, Model>::value && NC == 8, "ug_hand_geometry is the planar hand's assembly");
     const int lane = tid & 63, wave = tid >> 6;
     if (wave == 0) {
-        // the model's QP assembly (trigonometry, closest points): one wave, every lane the same; lane 0 stores
-        float xb[n], ub[m], q[n], Dinv[n], b0[n], J[NC][n], phi[NC];
+        // the model's QP assembly (trigonometry, closest points), spread over the lanes (ug_geometry.hpp): lane c < NC
+        // holds and stores row c of J and phi_c, lane k < n element k of q, D^-1, b
+        double xd[n], ud[m];
 #pragma unroll
-        for (int i = 0; i < n; ++i) xb[i] = (float)x[i];
+        for (int i = 0; i < n; ++i) xd[i] = x[i];
 #pragma unroll
-        for (int j = 0; j < m; ++j) ub[j] = (float)u[j];
-        Model::template assemble<float>(p, xb, ub, q, Dinv, b0, J, phi);
-        if (lane == 0) {
+        for (int j = 0; j < m; ++j) ud[j] = u[j];
+        early();
+        float xb[n], ub[m];
 #pragma unroll
-            for (int i = 0; i < NC; ++i) {
-                S.phi[i] = phi[i];
+        for (int i = 0; i < n; ++i) xb[i] = (float)xd[i];
 #pragma unroll
-                for (int k = 0; k < n; ++k) S.Jc[i][k] = J[i][k];
-            }
+        for (int j = 0; j < m; ++j) ub[j] = (float)ud[j];
+        UgHandLane<float> g;
+        ug_hand_geometry<float>(p, xb, ub, lane, g);
+        if (lane < NC) {
+            S.phi[lane] = g.phi;
 #pragma unroll
-            for (int k = 0; k < n; ++k) { S.Db0[k] = b0[k] * Dinv[k]; S.q[k] = q[k]; S.Dinv[k] = Dinv[k]; }
-#pragma unroll
-            for (int j = 0; j < m; ++j) S.DK[j] = Dinv[Model::act(j)] * Model::template stiffness<float>(p, j);
+            for (int k = 0; k < n; ++k) S.Jc[lane][k] = g.J[k];
         }
+        if (lane < n) { S.Db0[lane] = g.b * g.Dinv; S.q[lane] = g.q; S.Dinv[lane] = g.Dinv; }
+        if (lane >= Model::act(0) && lane < Model::act(0) + m) S.DK[lane - Model::act(0)] = g.Dinv * g.kp;
+    } else {
+        early();
     }
     __syncthreads();
     // what follows from it, one quantity per thread (the expressions of irs_contact_qp_dual_exact_try):
@@ -831,7 +841,7 @@ template <class Model, bool UCOL>
 __global__ __launch_bounds__(kUgBlock) void ug_table_kernel(ModelParams p, const double* x, const double* u, float* out) {
     __shared__ UgLds<Model> S;
     const int tid = threadIdx.x;
-    ug_prologue<Model, UCOL>(p, x, u, true, S, tid);
+    ug_prologue<Model, UCOL>(p, x, u, true, S, tid, [] {});
     constexpr int NE = 1 << Model::NC;
     for (int q = tid; q < NE * kUgTabStride; q += kUgBlock) {
         const int c = q % kUgTabStride;
@@ -873,10 +883,35 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
     const bool nominal_wave = blk == 0 && wave == NW - 1;
     double nom_r = 0.0;
     if (nominal_wave && !(a.diag & 2)) nom_r = ug_nominal_geometry<Model>(a, nomL, t, lane);
+    if (nominal_wave) UG_STAMP(10);
     if constexpr (TR::FIRST_B) {
         for (int q = tid; q < (1 << NC); q += BLOCK) hist[q] = 0u;
     }
-    ug_prologue<Model, UCOL>(a.p, a.x_trj + (size_t)t * n, a.u_trj + (size_t)t * m, !(a.diag & 4), S, tid);
+    // 64-sample blocks are dealt round robin to the waves of the timestep: rounds 0 .. kUgNomRounds - 1 to all but
+    // the nominal wave (which is busy with the f64 step for about that long), later rounds to all of them
+    const int V = a.nblk * NW;
+    const int me = nominal_wave ? V - 1 : (blk == 0 ? wave : blk * NW - 1 + wave);
+    const int nblocks = (a.N + 63) / 64;
+    const int round0 = nominal_wave ? kUgNomRounds : 0;
+    auto block_of = [&](int k) { return k < kUgNomRounds ? k * (V - 1) + me : kUgNomRounds * (V - 1) + (k - kUgNomRounds) * V + me; };
+    // the perturbations of the NEXT fresh trip are requested while this one computes: a trip is ~1.5 us of
+    // arithmetic, an HBM round trip ~0.5-1 us, and a SIMD holds two waves -- nothing else would hide it.  (No
+    // other vector-memory operation sits inside a trip, so the wait lands where the sample is consumed.)  Those of
+    // the FIRST trip are requested from inside the prologue and are in flight during the geometry and the table build.
+    float du_next[m];
+#pragma unroll
+    for (int j = 0; j < m; ++j) du_next[j] = 0.f;
+    auto request = [&](int block) {
+        if constexpr (!RNG) {
+            if (block < nblocks) {
+                const int sidx = block * 64 + lane;
+                const size_t row = (size_t)t * a.N + (sidx < a.N ? sidx : a.N - 1);
+                load_row<m>(a.du + row * m, du_next);
+            }
+        }
+    };
+    ug_prologue<Model, UCOL>(a.p, a.x_trj + (size_t)t * n, a.u_trj + (size_t)t * m, !(a.diag & 4), S, tid,
+                             [&] { if (!(a.diag & 8)) request(block_of(round0)); });
 
     UG_STAMP(2);
     // the uniform operands of the sweeps, in VECTOR registers (one copy per lane).  Measured on gfx950
@@ -902,32 +937,10 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
     if (nominal_wave) UG_STAMP(8);
     UG_COUNT_DECL;
     if (!(a.diag & 8)) {
-        // 64-sample blocks are dealt round robin to the waves of the timestep: rounds 0 .. kUgNomRounds - 1 to all but
-        // the nominal wave (which is busy with the f64 step for about that long), later rounds to all of them
-        const int V = a.nblk * NW;
-        const int me = nominal_wave ? V - 1 : (blk == 0 ? wave : blk * NW - 1 + wave);
-        const int nblocks = (a.N + 63) / 64;
-        int round = nominal_wave ? kUgNomRounds : 0;
-        auto block_of = [&](int k) { return k < kUgNomRounds ? k * (V - 1) + me : kUgNomRounds * (V - 1) + (k - kUgNomRounds) * V + me; };
+        int round = round0;
         float* ring = ring_all + wave * (kUgRing * QE);
         int qhead = 0, qtail = 0;                           // wave-uniform
-        int bk = block_of(round);
-        // the perturbations of the NEXT fresh trip are requested while this one computes: a trip is ~1.5 us of
-        // arithmetic, an HBM round trip ~0.5-1 us, and a SIMD holds two waves -- nothing else would hide it.  (No
-        // other vector-memory operation sits inside a trip, so the wait lands where the sample is consumed.)
-        float du_next[m];
-#pragma unroll
-        for (int j = 0; j < m; ++j) du_next[j] = 0.f;
-        auto request = [&](int block) {
-            if constexpr (!RNG) {
-                if (block < nblocks) {
-                    const int sidx = block * 64 + lane;
-                    const size_t row = (size_t)t * a.N + (sidx < a.N ? sidx : a.N - 1);
-                    load_row<m>(a.du + row * m, du_next);
-                }
-            }
-        };
-        request(bk);
+        int bk = block_of(round);                           // (its perturbations: requested in the prologue)
         while (true) {
             const bool fresh = bk < nblocks;
             const int pending = qtail - qhead;
@@ -1023,6 +1036,7 @@ __global__ __launch_bounds__(kUgBlock) void smooth_ug_kernel(SmoothArgs args, st
                 for (int i = 0; i < m; ++i) { acc[q] += zz[i]; ++q; }
                 if (on && nonfinite) acc[0] = irs_poison();
             }
+            if (!flush && round == round0 + 1) UG_STAMP(6);     // wave 0: its first fresh trip done
         }
     }
 
