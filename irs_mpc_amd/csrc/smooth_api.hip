@@ -4,9 +4,10 @@
 //
 // Every single-problem entry -- by struct (irs_smooth_run) or positional -- states its call as a SmoothEntry and
 // goes through smooth_common: the checks in one order, the model constants, the plan (smooth_geometry), the
-// workspace carve and SmoothArgs (fill_args), one launch.  irs_smooth_rng_batch shares fill_args and keeps the checks
-// that only B problems have.  The refusal texts carry the names of the functions here (IRS_CHECK_ARG prints
-// __func__): tests/test_smooth_entries_cpu.py pins them, call by call.
+// workspace carve and SmoothArgs (fill_args), one launch.  The two batched entries state theirs as a SmoothBatchCall and
+// go through smooth_batch_common: the checks only B problems have, what tells the two apart as data (SmoothBatchKind),
+// fill_args for problem 0, one launch.  The refusal texts carry the names of the entries -- IRS_CHECK_ARG prints
+// __func__, the batched path the record's fn: tests/test_smooth_entries_cpu.py pins them, call by call.
 #include "smooth_common.hpp"
 
 namespace {
@@ -297,20 +298,130 @@ irs_smooth_call positional_call(int model, int n_params, int mode, int T, int N,
 // ---- B problems per launch --------------------------------------------------------------------------------
 size_t round256(size_t bytes) { return (bytes + 255) / 256 * 256; }
 
-// what the batched sample pass serves: what the uniform-geometry kernel serves (IRS_UG is read per call)
-int smooth_batch_supported(int model, int mode, int* n, int* m, int* np) {
-    const int rc = irs_model_info(model, n, m, np);
-    if (rc != IRS_OK) return rc;
-    return irs_smooth_ug_supported(model, mode) ? IRS_OK : IRS_ERR_UNSUPPORTED;
+// what the general kernel's batched form serves of a registered model: the analytic ones (those with a Jacobian) in
+// the modes that perturb x and u
+bool smooth_general_batch_serves(int model, int mode) {
+    return !has_nominal_in_wg0(model, mode) && (mode == IRS_SMOOTH_ZERO_ORDER_AB || mode == IRS_SMOOTH_FIRST_ORDER);
 }
 
-// what the general kernel's batched form serves: the analytic models (those with a Jacobian) in the modes that perturb
-// x and u
-int smooth_general_batch_supported(int model, int mode, int* n, int* m, int* np) {
+// What tells the two batched passes apart, as data: the rest of smooth_batch_common is the same for both.
+struct SmoothBatchKind {
+    bool (*serves_model)(int model, int mode);       // of a registered model (the uniform-geometry one reads IRS_UG per call)
+    const char* serves;              // the refusal of a (model, mode) that is not served, after "<fn>: model %d, mode %d: "
+    bool takes_std_x;                // std_x is an argument, and a null one is refused (else: the entry has none)
+    bool uniform_geometry_only;      // the planned family must be IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY, refused by number
+    int (*launch)(int model, int mode, const SmoothArgs& a, const SmoothBatch& bat, int B, hipStream_t st);
+    const char* launch_refusal;      // what a launcher's refusal is reworded to (fn, model, mode); null: its own text stands
+};
+
+const SmoothBatchKind kUniformGeometryBatch{
+    irs_smooth_ug_supported,
+    "the batched sample pass serves the uniform-geometry kernel (IRS_MODEL_PLANAR_HAND_EXACT in IRS_SMOOTH_ZERO_ORDER_B and "
+    "IRS_SMOOTH_FIRST_ORDER, IRS_UG not 0)",
+    false, true, irs_smooth_ug_launch_batch, nullptr};
+const SmoothBatchKind kGeneralBatch{
+    smooth_general_batch_serves,
+    "the general batched sample pass serves the analytic models (pendulum, quadrotor, bicycle, three cart) in "
+    "IRS_SMOOTH_ZERO_ORDER_AB and IRS_SMOOTH_FIRST_ORDER",
+    true, false, irs_smooth_launch_batch, "%s: no batched kernel for model %d, mode %d"};
+
+// One batched sample pass as its entry states it: the kind, and the entry's arguments in the order it takes them.
+struct SmoothBatchCall {
+    const char* fn;                  // the name the checks word their errors with
+    const SmoothBatchKind& kind;
+    int model; const double* params; int n_params, mode, T, N, B;
+    const double* x_trj; long long x_stride; const double* u_trj; long long u_stride;
+    const double* std_x;             // DEV (B, n); null for the uniform-geometry form
+    const double* std_u; const uint64_t* seed; uint32_t iter;      // DEV (B, m), DEV (B)
+    double *sums, *At, *Bt, *ct; int* info;
+    void* workspace; size_t workspace_bytes;
+};
+
+// whether the kind serves (model, mode), and then the model's sizes
+int smooth_batch_supported(const SmoothBatchKind& k, int model, int mode, int* n, int* m, int* np) {
     const int rc = irs_model_info(model, n, m, np);
     if (rc != IRS_OK) return rc;
-    const bool analytic = !has_nominal_in_wg0(model, mode);
-    return analytic && (mode == IRS_SMOOTH_ZERO_ORDER_AB || mode == IRS_SMOOTH_FIRST_ORDER) ? IRS_OK : IRS_ERR_UNSUPPORTED;
+    return k.serves_model(model, mode) ? IRS_OK : IRS_ERR_UNSUPPORTED;
+}
+
+// B slices of the single-problem workspace, 256-byte aligned; 0 where the kind does not serve (model, mode)
+size_t smooth_batch_workspace_size(const SmoothBatchKind& k, int model, int mode, int T, int N, int B) {
+    int n, m, np;
+    if (B <= 0 || smooth_batch_supported(k, model, mode, &n, &m, &np) != IRS_OK) return 0;
+    return (size_t)B * round256(irs_smooth_workspace_bytes(model, mode, T, N));
+}
+
+// zeroes a batch workspace: every slice's arrival counters, once per allocation
+int smooth_batch_workspace_init(const char* fn, void* workspace, size_t workspace_bytes, void* stream) {
+    if (workspace == nullptr || workspace_bytes == 0) { irs_set_error("%s: no workspace", fn); return IRS_ERR_INVALID_ARG; }
+    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) { irs_set_error("%s: %s", fn, hipGetErrorString(e)); return IRS_ERR_HIP; }
+    return IRS_OK;
+}
+
+// The one path of both batched entries: the checks in one order, worded with the entry's name, then SmoothArgs for
+// problem 0 (fill_args), the strides and per-problem arrays (SmoothBatch), one launch.
+int smooth_batch_common(const SmoothBatchCall& c, void* stream) {
+    const SmoothBatchKind& k = c.kind;
+    const auto refuse = [&c](const char* msg) { irs_set_error("%s: %s", c.fn, msg); return IRS_ERR_INVALID_ARG; };
+    // every argument error is decided before the first HIP call
+    if (!(c.B > 0 && c.T > 0 && c.N > 0)) return refuse("B, T and N must be positive");
+    if (c.T > kMaxT) return refuse("T too large for the arrival counters (max 1024)");
+    if ((long long)c.B * c.T > 65535) return refuse("B * T beyond the grid's 65535 rows");
+    if (!(c.x_trj && c.u_trj && (c.std_x || !k.takes_std_x) && c.std_u && c.seed && c.sums && c.At && c.Bt && c.ct &&
+          c.info))
+        return refuse("null pointer");
+    if (c.mode < 0 || c.mode > 2) return refuse("unknown smoothing mode");
+    int n = 0, m = 0, np = 0;
+    int rc = smooth_batch_supported(k, c.model, c.mode, &n, &m, &np);
+    if (rc != IRS_OK) {
+        irs_set_error("%s: model %d, mode %d: %s", c.fn, c.model, c.mode, k.serves);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    if (c.params == nullptr || c.n_params != np) {
+        irs_set_error("%s: model %d expects %d params, got %d", c.fn, c.model, np, c.n_params);
+        return IRS_ERR_INVALID_ARG;
+    }
+    if (c.x_stride < (long long)c.T * n || c.u_stride < (long long)c.T * m)
+        return refuse("x_stride / u_stride shorter than a problem's T rows");
+    SmoothArgs a;
+    memset(&a, 0, sizeof(a));
+    rc = irs_load_params(c.model, c.params, c.n_params, &a.p);
+    if (rc != IRS_OK) return rc;
+    SmoothGeometry g;
+    rc = smooth_geometry(c.model, c.mode, c.T, c.N, true, &g);
+    if (rc != IRS_OK) return rc;
+    if (partial_bytes(c.T, g.nblk, irs_sums_len(c.model, c.mode)) > 0xffffffffull)
+        return refuse("a problem's partial sums exceed the hand-off's 32-bit buffer size");
+    if (k.uniform_geometry_only && g.family != IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY) {
+        irs_set_error("%s: no batched kernel for the planned kernel family %d", c.fn, g.family);
+        return IRS_ERR_UNSUPPORTED;
+    }
+    const size_t stride = round256(irs_smooth_workspace_bytes(c.model, c.mode, c.T, c.N)), need = (size_t)c.B * stride;
+    if (c.workspace == nullptr || c.workspace_bytes < need) {
+        irs_set_error("%s: workspace %zu < %zu bytes (%d slices of %zu)", c.fn, c.workspace_bytes, need, c.B, stride);
+        return IRS_ERR_WORKSPACE;
+    }
+    if ((reinterpret_cast<uintptr_t>(c.workspace) & 255) != 0) {
+        irs_set_error("%s: the workspace must be 256-byte aligned", c.fn);
+        return IRS_ERR_WORKSPACE;
+    }
+    // problem 0's call; the kernel's entry moves its arguments to the row's problem (SmoothRow)
+    irs_smooth_call p0 = positional_call(c.model, c.n_params, c.mode, c.T, c.N, c.x_trj, c.u_trj, c.sums, c.workspace,
+                                         c.workspace_bytes);
+    p0.At = c.At; p0.Bt = c.Bt; p0.ct = c.ct; p0.info = c.info;
+    fill_args(a, p0, g, true);
+    a.iter = c.iter;
+    const SmoothBatch bat{c.x_stride, c.u_stride, (long long)stride, reinterpret_cast<const unsigned long long*>(c.seed),
+                          c.std_u, c.std_x};
+    rc = k.launch(c.model, c.mode, a, bat, c.B, static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) {
+        if (k.launch_refusal) irs_set_error(k.launch_refusal, c.fn, c.model, c.mode);
+        return rc;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { irs_set_error("%s: HIP error %s", c.fn, hipGetErrorString(e)); return IRS_ERR_HIP; }
+    return IRS_OK;
 }
 
 }  // namespace
@@ -318,16 +429,19 @@ int smooth_general_batch_supported(int model, int mode, int* n, int* m, int* np)
 extern "C" {
 
 size_t irs_smooth_batch_workspace_bytes(int model, int mode, int T, int N, int B) {
-    int n, m, np;
-    if (B <= 0 || smooth_batch_supported(model, mode, &n, &m, &np) != IRS_OK) return 0;
-    return (size_t)B * round256(irs_smooth_workspace_bytes(model, mode, T, N));
+    return smooth_batch_workspace_size(kUniformGeometryBatch, model, mode, T, N, B);
+}
+
+size_t irs_smooth_general_batch_workspace_bytes(int model, int mode, int T, int N, int B) {
+    return smooth_batch_workspace_size(kGeneralBatch, model, mode, T, N, B);
 }
 
 int irs_smooth_batch_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(workspace != nullptr && workspace_bytes > 0, "no workspace");
-    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) { irs_set_error("irs_smooth_batch_workspace_init: %s", hipGetErrorString(e)); return IRS_ERR_HIP; }
-    return IRS_OK;
+    return smooth_batch_workspace_init(__func__, workspace, workspace_bytes, stream);
+}
+
+int irs_smooth_general_batch_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
+    return smooth_batch_workspace_init(__func__, workspace, workspace_bytes, stream);
 }
 
 int irs_smooth_rng_batch(int model, const double* params, int n_params, int mode, int T, int N, int B,
@@ -335,76 +449,9 @@ int irs_smooth_rng_batch(int model, const double* params, int n_params, int mode
                          const double* std_u, const uint64_t* seed, uint32_t iter,
                          double* sums, double* At, double* Bt, double* ct, int* info,
                          void* workspace, size_t workspace_bytes, void* stream) {
-    // every argument error is decided before the first HIP call
-    IRS_CHECK_ARG(B > 0 && T > 0 && N > 0, "B, T and N must be positive");
-    IRS_CHECK_ARG(T <= kMaxT, "T too large for the arrival counters (max 1024)");
-    IRS_CHECK_ARG((long long)B * T <= 65535, "B * T beyond the grid's 65535 rows");
-    IRS_CHECK_ARG(x_trj && u_trj && std_u && seed && sums && At && Bt && ct && info, "null pointer");
-    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
-    int n = 0, m = 0, np = 0;
-    int rc = smooth_batch_supported(model, mode, &n, &m, &np);
-    if (rc != IRS_OK) {
-        irs_set_error("irs_smooth_rng_batch: model %d, mode %d: the batched sample pass serves the uniform-geometry kernel "
-                      "(IRS_MODEL_PLANAR_HAND_EXACT in IRS_SMOOTH_ZERO_ORDER_B and IRS_SMOOTH_FIRST_ORDER, IRS_UG not 0)",
-                      model, mode);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    if (params == nullptr || n_params != np) {
-        irs_set_error("irs_smooth_rng_batch: model %d expects %d params, got %d", model, np, n_params);
-        return IRS_ERR_INVALID_ARG;
-    }
-    IRS_CHECK_ARG(x_stride >= (long long)T * n && u_stride >= (long long)T * m,
-                  "x_stride / u_stride shorter than a problem's T rows");
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    rc = irs_load_params(model, params, n_params, &a.p);
-    if (rc != IRS_OK) return rc;
-    SmoothGeometry g;
-    rc = smooth_geometry(model, mode, T, N, true, &g);
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_ARG(partial_bytes(T, g.nblk, irs_sums_len(model, mode)) <= 0xffffffffull,
-                  "a problem's partial sums exceed the hand-off's 32-bit buffer size");
-    if (g.family != IRS_SMOOTH_FAMILY_UNIFORM_GEOMETRY) {
-        irs_set_error("irs_smooth_rng_batch: no batched kernel for the planned kernel family %d", g.family);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    // B slices of the single-problem layout, 256-byte aligned
-    const size_t stride = round256(irs_smooth_workspace_bytes(model, mode, T, N)), need = (size_t)B * stride;
-    if (workspace == nullptr || workspace_bytes < need) {
-        irs_set_error("irs_smooth_rng_batch: workspace %zu < %zu bytes (%d slices of %zu)", workspace_bytes, need, B, stride);
-        return IRS_ERR_WORKSPACE;
-    }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
-        irs_set_error("irs_smooth_rng_batch: the workspace must be 256-byte aligned");
-        return IRS_ERR_WORKSPACE;
-    }
-    // problem 0's call; the kernel's entry moves its arguments to the row's problem (SmoothRow)
-    irs_smooth_call c = positional_call(model, n_params, mode, T, N, x_trj, u_trj, sums, workspace, workspace_bytes);
-    c.At = At; c.Bt = Bt; c.ct = ct; c.info = info;
-    fill_args(a, c, g, true);
-    a.iter = iter;
-    const SmoothBatch bat{x_stride, u_stride, (long long)stride, reinterpret_cast<const unsigned long long*>(seed), std_u,
-                          nullptr};
-    rc = irs_smooth_ug_launch_batch(model, mode, a, bat, B, static_cast<hipStream_t>(stream));
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
-}
-
-size_t irs_smooth_general_batch_workspace_bytes(int model, int mode, int T, int N, int B) {
-    int n, m, np;
-    if (B <= 0 || smooth_general_batch_supported(model, mode, &n, &m, &np) != IRS_OK) return 0;
-    return (size_t)B * round256(irs_smooth_workspace_bytes(model, mode, T, N));
-}
-
-int irs_smooth_general_batch_workspace_init(void* workspace, size_t workspace_bytes, void* stream) {
-    IRS_CHECK_ARG(workspace != nullptr && workspace_bytes > 0, "no workspace");
-    hipError_t e = hipMemsetAsync(workspace, 0, workspace_bytes, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) {
-        irs_set_error("irs_smooth_general_batch_workspace_init: %s", hipGetErrorString(e));
-        return IRS_ERR_HIP;
-    }
-    return IRS_OK;
+    return smooth_batch_common({__func__, kUniformGeometryBatch, model, params, n_params, mode, T, N, B, x_trj, x_stride,
+                                u_trj, u_stride, nullptr, std_u, seed, iter, sums, At, Bt, ct, info, workspace,
+                                workspace_bytes}, stream);
 }
 
 int irs_smooth_rng_general_batch(int model, const double* params, int n_params, int mode, int T, int N, int B,
@@ -412,60 +459,9 @@ int irs_smooth_rng_general_batch(int model, const double* params, int n_params, 
                                  const double* std_x, const double* std_u, const uint64_t* seed, uint32_t iter,
                                  double* sums, double* At, double* Bt, double* ct, int* info,
                                  void* workspace, size_t workspace_bytes, void* stream) {
-    // every argument error is decided before the first HIP call
-    IRS_CHECK_ARG(B > 0 && T > 0 && N > 0, "B, T and N must be positive");
-    IRS_CHECK_ARG(T <= kMaxT, "T too large for the arrival counters (max 1024)");
-    IRS_CHECK_ARG((long long)B * T <= 65535, "B * T beyond the grid's 65535 rows");
-    IRS_CHECK_ARG(x_trj && u_trj && std_x && std_u && seed && sums && At && Bt && ct && info, "null pointer");
-    IRS_CHECK_ARG(mode >= 0 && mode <= 2, "unknown smoothing mode");
-    int n = 0, m = 0, np = 0;
-    int rc = smooth_general_batch_supported(model, mode, &n, &m, &np);
-    if (rc != IRS_OK) {
-        irs_set_error("irs_smooth_rng_general_batch: model %d, mode %d: the general batched sample pass serves the analytic "
-                      "models (pendulum, quadrotor, bicycle, three cart) in IRS_SMOOTH_ZERO_ORDER_AB and "
-                      "IRS_SMOOTH_FIRST_ORDER", model, mode);
-        return IRS_ERR_UNSUPPORTED;
-    }
-    if (params == nullptr || n_params != np) {
-        irs_set_error("irs_smooth_rng_general_batch: model %d expects %d params, got %d", model, np, n_params);
-        return IRS_ERR_INVALID_ARG;
-    }
-    IRS_CHECK_ARG(x_stride >= (long long)T * n && u_stride >= (long long)T * m,
-                  "x_stride / u_stride shorter than a problem's T rows");
-    SmoothArgs a;
-    memset(&a, 0, sizeof(a));
-    rc = irs_load_params(model, params, n_params, &a.p);
-    if (rc != IRS_OK) return rc;
-    SmoothGeometry g;
-    rc = smooth_geometry(model, mode, T, N, true, &g);
-    if (rc != IRS_OK) return rc;
-    IRS_CHECK_ARG(partial_bytes(T, g.nblk, irs_sums_len(model, mode)) <= 0xffffffffull,
-                  "a problem's partial sums exceed the hand-off's 32-bit buffer size");
-    // B slices of the single-problem layout, 256-byte aligned
-    const size_t stride = round256(irs_smooth_workspace_bytes(model, mode, T, N)), need = (size_t)B * stride;
-    if (workspace == nullptr || workspace_bytes < need) {
-        irs_set_error("irs_smooth_rng_general_batch: workspace %zu < %zu bytes (%d slices of %zu)", workspace_bytes, need, B,
-                      stride);
-        return IRS_ERR_WORKSPACE;
-    }
-    if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) {
-        irs_set_error("irs_smooth_rng_general_batch: the workspace must be 256-byte aligned");
-        return IRS_ERR_WORKSPACE;
-    }
-    // problem 0's call; the kernel's entry moves its arguments to the row's problem (SmoothRow)
-    irs_smooth_call c = positional_call(model, n_params, mode, T, N, x_trj, u_trj, sums, workspace, workspace_bytes);
-    c.At = At; c.Bt = Bt; c.ct = ct; c.info = info;
-    fill_args(a, c, g, true);
-    a.iter = iter;
-    const SmoothBatch bat{x_stride, u_stride, (long long)stride, reinterpret_cast<const unsigned long long*>(seed), std_u,
-                          std_x};
-    rc = irs_smooth_launch_batch(model, mode, a, bat, B, static_cast<hipStream_t>(stream));
-    if (rc != IRS_OK) {
-        irs_set_error("irs_smooth_rng_general_batch: no batched kernel for model %d, mode %d", model, mode);
-        return rc;
-    }
-    IRS_CHECK_LAUNCH();
-    return IRS_OK;
+    return smooth_batch_common({__func__, kGeneralBatch, model, params, n_params, mode, T, N, B, x_trj, x_stride,
+                                u_trj, u_stride, std_x, std_u, seed, iter, sums, At, Bt, ct, info, workspace,
+                                workspace_bytes}, stream);
 }
 
 int irs_sums_len(int model, int mode) {

@@ -38,6 +38,20 @@ def _ws_args(ws):
     return (ws.data_ptr(), ws.numel()) if ws is not None else (None, 0)
 
 
+def _check_shapes(named):
+    """Every (name, tensor, shape) of `named` names a tensor of that shape."""
+    for name, t, shape in named:
+        assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+
+
+def _outputs(out, shapes, device):
+    """`out`, or freshly allocated tensors (name -> shape; `info` int32, the rest f64): checked to have those shapes."""
+    o = out if out is not None else DeviceModel._tv_alloc(shapes, device)
+    for name, shape in shapes.items():         # (in place: through _check_shapes this costs a microsecond per call)
+        assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
+    return o
+
+
 def to_dev(a, dtype=F64):
     """numpy / tensor -> contiguous device tensor of `dtype`."""
     dev = require_gpu()
@@ -282,10 +296,53 @@ class DeviceModel(CemModelFree):
                                 rng=(std_x, std_u, seed, it))
 
     # ---- B sample passes per launch ------------------------------------------
+    # the two kinds, by their workspace cache key: the method, its entries of the C ABI, and whether it takes std_x_dev
+    _SMOOTH_BATCH = {
+        "smooth_batch": ("smooth_rng_batch", "irs_smooth_batch_workspace_bytes", "irs_smooth_batch_workspace_init",
+                         "irs_smooth_rng_batch", False),
+        "smooth_general_batch": ("smooth_rng_general_batch", "irs_smooth_general_batch_workspace_bytes",
+                                 "irs_smooth_general_batch_workspace_init", "irs_smooth_rng_general_batch", True)}
+
+    def _smooth_batch_served(self, kind, mode):
+        return getattr(self.lib, self._SMOOTH_BATCH[kind][1])(self.model_id, int(mode), 1, 1, 1) > 0
+
+    def _smooth_rng_batch(self, kind, mode, X, U, N, std_x_dev, std_u_dev, seed_dev, it, out):
+        """smooth_rng_batch / smooth_rng_general_batch (`kind`: a key of _SMOOTH_BATCH)."""
+        method, ws_bytes, ws_init, launch, takes_std_x = self._SMOOTH_BATCH[kind]
+        mode, N = int(mode), int(N)
+        B = U.shape[0]
+        T = out["info"].shape[1] if out is not None else U.shape[1]
+        dev = U.device
+        for name, t, cols in (("X", X, self.n), ("U", U, self.m)):
+            assert t.is_cuda and t.dtype == F64 and t.dim() == 3 and t.shape[0] == B and t.shape[1] >= T, name
+            assert t.shape[2] == cols and t.stride(2) == 1 and t.stride(1) == cols, (name, t.shape, t.stride())
+            assert B == 1 or t.stride(0) >= T * cols, (name, t.stride())
+        assert not takes_std_x or tuple(std_x_dev.shape) == (B, self.n)
+        assert tuple(std_u_dev.shape) == (B, self.m) and tuple(seed_dev.shape) == (B,) and seed_dev.dtype == torch.int64
+        assert seed_dev.is_cuda and seed_dev.is_contiguous()
+        o = _outputs(out, self._tv_shapes((B, T), mode), dev)
+        assert o["info"].dtype == torch.int32 and o["info"].is_contiguous()
+        need = getattr(self.lib, ws_bytes)(self.model_id, mode, T, N, B)
+        if need == 0:
+            raise NotImplementedError("%s: model %d, mode %d is not served" % (method, self.model_id, mode))
+        key = (kind, mode, T, N)                             # one slice layout per buffer: the counters stay put
+        before = self._ws.get((key, dev))
+        ws = self._cached_workspace(key, need, dev)
+        if ws is not before:                                 # a fresh allocation: its counters are zeroed once
+            check(getattr(self.lib, ws_init)(ws.data_ptr(), ws.numel(), _stream()), ws_init)
+        xs = X.stride(0) if B > 1 else X.shape[1] * self.n
+        us = U.stride(0) if B > 1 else U.shape[1] * self.m
+        stds = (_ptr(std_x_dev, F64), _ptr(std_u_dev, F64)) if takes_std_x else (_ptr(std_u_dev, F64),)
+        check(getattr(self.lib, launch)(self.model_id, self._p, self._np, mode, T, N, B, X.data_ptr(), xs,
+                                        U.data_ptr(), us, *stds, seed_dev.data_ptr(), int(it), _ptr(o["sums"], F64),
+                                        _ptr(o["At"], F64), _ptr(o["Bt"], F64), _ptr(o["ct"], F64),
+                                        o["info"].data_ptr(), ws.data_ptr(), ws.numel(), _stream()), launch)
+        return o
+
     def smooth_batch_supported(self, mode):
         """Whether smooth_rng_batch serves this model in `mode`: what the uniform-geometry kernel serves (the exact
         planar hand's u-only modes; IRS_UG is read per call)."""
-        return self.lib.irs_smooth_batch_workspace_bytes(self.model_id, int(mode), 1, 1, 1) > 0
+        return self._smooth_batch_served("smooth_batch", mode)
 
     def smooth_rng_batch(self, mode, X, U, N, std_u_dev, seed_dev, it, out=None):
         """The sample passes of B problems in one launch (irs_smooth_rng_batch): problem b's outputs are, bit for bit,
@@ -294,37 +351,7 @@ class DeviceModel(CemModelFree):
         taken from the tensor); T = the rows of `out`, else of U.  std_u_dev (B,m) f64, seed_dev (B) int64 holding the
         uint64 bits, both on the device.  Returns dict(sums (B,T,P), At (B,T,n,n), Bt (B,T,n,m), ct (B,T,n), info
         (B,T)); pass `out` to write into tensors of those shapes."""
-        B = U.shape[0]
-        T = out["info"].shape[1] if out is not None else U.shape[1]
-        dev = U.device
-        for name, t, cols in (("X", X, self.n), ("U", U, self.m)):
-            assert t.is_cuda and t.dtype == F64 and t.dim() == 3 and t.shape[0] == B and t.shape[1] >= T, name
-            assert t.shape[2] == cols and t.stride(2) == 1 and t.stride(1) == cols, (name, t.shape, t.stride())
-            assert B == 1 or t.stride(0) >= T * cols, (name, t.stride())
-        assert tuple(std_u_dev.shape) == (B, self.m) and tuple(seed_dev.shape) == (B,) and seed_dev.dtype == torch.int64
-        assert seed_dev.is_cuda and seed_dev.is_contiguous()
-        shapes = self._tv_shapes((B, T), mode)
-        o = out if out is not None else self._tv_alloc(shapes, dev)
-        for name, shape in shapes.items():
-            assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
-        assert o["info"].dtype == torch.int32 and o["info"].is_contiguous()
-        need = self.lib.irs_smooth_batch_workspace_bytes(self.model_id, int(mode), T, int(N), B)
-        if need == 0:
-            raise NotImplementedError("smooth_rng_batch: model %d, mode %d is not served" % (self.model_id, mode))
-        key = ("smooth_batch", int(mode), T, int(N))         # one slice layout per buffer: the counters stay where they are
-        before = self._ws.get((key, dev))
-        ws = self._cached_workspace(key, need, dev)
-        if ws is not before:                                 # a fresh allocation: its counters are zeroed once
-            check(self.lib.irs_smooth_batch_workspace_init(ws.data_ptr(), ws.numel(), _stream()),
-                  "irs_smooth_batch_workspace_init")
-        xs = X.stride(0) if B > 1 else X.shape[1] * self.n
-        us = U.stride(0) if B > 1 else U.shape[1] * self.m
-        check(self.lib.irs_smooth_rng_batch(self.model_id, self._p, self._np, int(mode), T, int(N), B, X.data_ptr(), xs,
-                                            U.data_ptr(), us, _ptr(std_u_dev, F64), seed_dev.data_ptr(), int(it),
-                                            _ptr(o["sums"], F64), _ptr(o["At"], F64), _ptr(o["Bt"], F64),
-                                            _ptr(o["ct"], F64), o["info"].data_ptr(), ws.data_ptr(), ws.numel(),
-                                            _stream()), "irs_smooth_rng_batch")
-        return o
+        return self._smooth_rng_batch("smooth_batch", mode, X, U, N, None, std_u_dev, seed_dev, it, out)
 
     def tvlqr_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, alpha_R=0.5, out=None):
         """Riccati backward pass + closed-loop rollout + cost in one launch."""
@@ -355,13 +382,10 @@ class DeviceModel(CemModelFree):
         B, T = At.shape[0], At.shape[1]
         dev = At.device
         n, m = self.n, self.m
-        for name, t, shape in (("At", At, (B, T, n, n)), ("Bt", Bt, (B, T, n, m)), ("ct", ct, (B, T, n)),
-                               ("xd_trj", xd_trj, (B, T + 1, n)), ("x0", x0, (B, n))):
-            assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
-        shapes = dict(K=(B, T, m, n), k=(B, T, m), x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B,))
-        o = out if out is not None else self._tv_alloc(shapes, dev)
-        for name, shape in shapes.items():
-            assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
+        _check_shapes((("At", At, (B, T, n, n)), ("Bt", Bt, (B, T, n, m)), ("ct", ct, (B, T, n)),
+                       ("xd_trj", xd_trj, (B, T + 1, n)), ("x0", x0, (B, n))))
+        o = _outputs(out, dict(K=(B, T, m, n), k=(B, T, m), x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B,)),
+                     dev)
         check(self.lib.irs_tvlqr_descent_batch(self.model_id, self._p, self._np, T, B, _ptr(At, F64), _ptr(Bt, F64),
                                                _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
                                                float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(o["K"], F64),
@@ -374,10 +398,9 @@ class DeviceModel(CemModelFree):
         """flag (B) int32: 1 where some tail plan of problem b leaves ITS box xlo, xhi (B,n), ulo, uhi (B,m) -- one
         launch (irs_tvlqr_plan_within_bounds_batch), the single entry's decision per problem."""
         B, T = At.shape[0], At.shape[1]
-        for name, t, shape in (("xlo", xlo, (B, self.n)), ("xhi", xhi, (B, self.n)), ("ulo", ulo, (B, self.m)),
-                               ("uhi", uhi, (B, self.m)), ("x_new", x_new, (B, T + 1, self.n)),
-                               ("K", K, (B, T, self.m, self.n)), ("k", k, (B, T, self.m))):
-            assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+        _check_shapes((("xlo", xlo, (B, self.n)), ("xhi", xhi, (B, self.n)), ("ulo", ulo, (B, self.m)),
+                       ("uhi", uhi, (B, self.m)), ("x_new", x_new, (B, T + 1, self.n)),
+                       ("K", K, (B, T, self.m, self.n)), ("k", k, (B, T, self.m))))
         if flag is None:
             flag = torch.empty((B,), dtype=torch.int32, device=At.device)
         check(self.lib.irs_tvlqr_plan_within_bounds_batch(self.n, self.m, T, B, _ptr(At, F64), _ptr(Bt, F64),
@@ -398,15 +421,11 @@ class DeviceModel(CemModelFree):
         B, T = At.shape[0], At.shape[1]
         dev = At.device
         n, m = self.n, self.m
-        for name, t, shape in (("At", At, (B, T, n, n)), ("Bt", Bt, (B, T, n, m)), ("ct", ct, (B, T, n)),
-                               ("xd_trj", xd_trj, (B, T + 1, n)), ("x0", x0, (B, n)), ("xlo", xlo, (B, n)),
-                               ("xhi", xhi, (B, n)), ("ulo", ulo, (B, m)), ("uhi", uhi, (B, m))):
-            assert tuple(t.shape) == shape, (name, tuple(t.shape), shape)
+        _check_shapes((("At", At, (B, T, n, n)), ("Bt", Bt, (B, T, n, m)), ("ct", ct, (B, T, n)),
+                       ("xd_trj", xd_trj, (B, T + 1, n)), ("x0", x0, (B, n)), ("xlo", xlo, (B, n)), ("xhi", xhi, (B, n)),
+                       ("ulo", ulo, (B, m)), ("uhi", uhi, (B, m))))
         assert run_flag is None or tuple(run_flag.shape) == (B,), tuple(run_flag.shape)
-        shapes = dict(x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B, 3))
-        o = out if out is not None else self._tv_alloc(shapes, dev)
-        for name, shape in shapes.items():
-            assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
+        o = _outputs(out, dict(x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B, 3)), dev)
         ws = None
         if records_in_hbm or self.lib.irs_tvlqr_box_workspace_bytes(self.model_id, T, 0) > 0:
             need = self.lib.irs_tvlqr_box_descent_batch_workspace_bytes(self.model_id, T, B)
@@ -425,45 +444,14 @@ class DeviceModel(CemModelFree):
     def smooth_general_batch_supported(self, mode):
         """Whether smooth_rng_general_batch serves this model in `mode`: the analytic models in the modes that perturb
         x and u (zero-order AB, first order)."""
-        return self.lib.irs_smooth_general_batch_workspace_bytes(self.model_id, int(mode), 1, 1, 1) > 0
+        return self._smooth_batch_served("smooth_general_batch", mode)
 
     def smooth_rng_general_batch(self, mode, X, U, N, std_x_dev, std_u_dev, seed_dev, it, out=None):
         """The sample passes of B problems of an analytic model in one launch (irs_smooth_rng_general_batch): problem b
         sees the draws of smooth_rng(mode, X[b], U[b], N, std_x[b], std_u[b], seed[b], it) and its results agree with
         that call's up to f32 rounding (not bit for bit).  Arguments and result as smooth_rng_batch, plus std_x_dev
         (B,n) f64 on the device."""
-        B = U.shape[0]
-        T = out["info"].shape[1] if out is not None else U.shape[1]
-        dev = U.device
-        for name, t, cols in (("X", X, self.n), ("U", U, self.m)):
-            assert t.is_cuda and t.dtype == F64 and t.dim() == 3 and t.shape[0] == B and t.shape[1] >= T, name
-            assert t.shape[2] == cols and t.stride(2) == 1 and t.stride(1) == cols, (name, t.shape, t.stride())
-            assert B == 1 or t.stride(0) >= T * cols, (name, t.stride())
-        assert tuple(std_x_dev.shape) == (B, self.n) and tuple(std_u_dev.shape) == (B, self.m)
-        assert tuple(seed_dev.shape) == (B,) and seed_dev.dtype == torch.int64 and seed_dev.is_cuda and seed_dev.is_contiguous()
-        shapes = self._tv_shapes((B, T), mode)
-        o = out if out is not None else self._tv_alloc(shapes, dev)
-        for name, shape in shapes.items():
-            assert tuple(o[name].shape) == shape, (name, tuple(o[name].shape), shape)
-        assert o["info"].dtype == torch.int32 and o["info"].is_contiguous()
-        need = self.lib.irs_smooth_general_batch_workspace_bytes(self.model_id, int(mode), T, int(N), B)
-        if need == 0:
-            raise NotImplementedError("smooth_rng_general_batch: model %d, mode %d is not served" % (self.model_id, mode))
-        key = ("smooth_general_batch", int(mode), T, int(N))  # one slice layout per buffer: the counters stay where they are
-        before = self._ws.get((key, dev))
-        ws = self._cached_workspace(key, need, dev)
-        if ws is not before:                                 # a fresh allocation: its counters are zeroed once
-            check(self.lib.irs_smooth_general_batch_workspace_init(ws.data_ptr(), ws.numel(), _stream()),
-                  "irs_smooth_general_batch_workspace_init")
-        xs = X.stride(0) if B > 1 else X.shape[1] * self.n
-        us = U.stride(0) if B > 1 else U.shape[1] * self.m
-        check(self.lib.irs_smooth_rng_general_batch(self.model_id, self._p, self._np, int(mode), T, int(N), B,
-                                                    X.data_ptr(), xs, U.data_ptr(), us, _ptr(std_x_dev, F64),
-                                                    _ptr(std_u_dev, F64), seed_dev.data_ptr(), int(it),
-                                                    _ptr(o["sums"], F64), _ptr(o["At"], F64), _ptr(o["Bt"], F64),
-                                                    _ptr(o["ct"], F64), o["info"].data_ptr(), ws.data_ptr(), ws.numel(),
-                                                    _stream()), "irs_smooth_rng_general_batch")
-        return o
+        return self._smooth_rng_batch("smooth_general_batch", mode, X, U, N, std_x_dev, std_u_dev, seed_dev, it, out)
 
     # ---- box-constrained descent ----------------------------------------------
     # the dynamic-LDS budget of the bounded-descent kernels (IRS_LDS_BUDGET in csrc/irs_common.hpp), for callers that
@@ -643,18 +631,10 @@ class DeviceModel(CemModelFree):
         info (B,3)); pass `out` to write into tensors of those shapes (e.g. a slot of a history)."""
         B, T = At.shape[0], At.shape[1]
         dev = At.device
-        o = out
-        if o is None:
-            o = dict(x_new=torch.empty((B, T + 1, self.n), dtype=F64, device=dev),
-                     u_new=torch.empty((B, T, self.m), dtype=F64, device=dev),
-                     cost=torch.empty((B,), dtype=F64, device=dev),
-                     info=torch.empty((B, 3), dtype=torch.int32, device=dev))
-        shapes = dict(At=(B, T, self.n, self.n), Bt=(B, T, self.n, self.m), ct=(B, T, self.n),
-                      xd_trj=(B, T + 1, self.n), x0=(B, self.n), x_new=(B, T + 1, self.n), u_new=(B, T, self.m),
-                      cost=(B,), info=(B, 3))
-        given = dict(At=At, Bt=Bt, ct=ct, xd_trj=xd_trj, x0=x0, **o)
-        for name, shape in shapes.items():
-            assert tuple(given[name].shape) == shape, (name, tuple(given[name].shape), shape)
+        n, m = self.n, self.m
+        _check_shapes((("At", At, (B, T, n, n)), ("Bt", Bt, (B, T, n, m)), ("ct", ct, (B, T, n)),
+                       ("xd_trj", xd_trj, (B, T + 1, n)), ("x0", x0, (B, n))))
+        o = _outputs(out, dict(x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B, 3)), dev)
         for b in (u_lo, u_hi, du_lo, du_hi, act):
             assert b is None or tuple(b.shape) == (B, T, self.m), (tuple(b.shape), (B, T, self.m))
         assert o["info"].dtype == torch.int32 and o["info"].is_contiguous()

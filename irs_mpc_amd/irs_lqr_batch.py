@@ -32,6 +32,7 @@ import torch
 from . import device as dev
 from . import distributed as dist_util
 from ._lib import SMOOTH_FIRST_ORDER, SMOOTH_ZERO_ORDER_AB
+from .batch_common import StackedResults, seed_bits
 from .irs_lqr import IrsLqr
 from .sampling import GaussianSmoothing
 from .torch_system import TorchDynamicalSystem
@@ -60,7 +61,7 @@ QP_SETTINGS = (("qp_rho", 10.0), ("qp_max_iter", 5000), ("qp_eps", 1e-8))
 QP_RELAX = 1.6
 
 
-class IrsLqrBatch:
+class IrsLqrBatch(StackedResults):
     def __init__(self, system, params_list, order, sampling_list=None, bounded=False):
         ps = list(params_list)
         if not ps:
@@ -139,22 +140,9 @@ class IrsLqrBatch:
                 raise NotImplementedError(_horizon_beyond_limit(T, self._dm.box_horizon_limit()))
             self._box = tuple(dev.to_dev(np.stack([box[i] for box in boxes])) for i in range(4))
         if smps is not None:
-            seeds = np.array([int(s.seed) & 0xFFFFFFFFFFFFFFFF for s in smps], dtype=np.uint64)
-            self._seeds = torch.as_tensor(seeds.view(np.int64)).to(self._Q.device)      # the uint64 bits, uploaded once
+            self._seeds = seed_bits([s.seed for s in smps], self._Q.device)      # uploaded once
 
-    # ---- results, per problem ---------------------------------------------------------------------
-    @property
-    def x_trj(self):
-        return np.stack([np.asarray(pr.x_trj, float) for pr in self.problems])
-
-    @property
-    def u_trj(self):
-        return np.stack([np.asarray(pr.u_trj, float) for pr in self.problems])
-
-    @property
-    def cost(self):
-        return np.array([pr.cost for pr in self.problems])
-
+    # ---- results, per problem (x_trj, u_trj, cost: StackedResults) ---------------------------------
     @property
     def x_trj_lst(self):
         return [pr.x_trj_lst for pr in self.problems]

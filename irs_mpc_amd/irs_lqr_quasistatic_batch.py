@@ -21,6 +21,7 @@ import torch
 
 from . import device as dev
 from . import distributed as dist_util
+from .batch_common import StackedResults, seed_bits
 from .irs_lqr_quasistatic import QP_FIELDS, SAMPLED_MODE, decouple_AB_dev, descent_failure, qp_settings
 from .quasistatic_base import COST_TERMS, QuasistaticOptimizerBase
 
@@ -53,7 +54,7 @@ class _Problem(QuasistaticOptimizerBase):
         self.verbose = False
 
 
-class IrsLqrQuasistaticBatch:
+class IrsLqrQuasistaticBatch(StackedResults):
     def __init__(self, q_dynamics, params_list, batched_sample_pass=True):
         ps = list(params_list)
         if not ps:
@@ -131,23 +132,10 @@ class IrsLqrQuasistaticBatch:
         mode = SAMPLED_MODE.get(self.gradient_mode)
         self.batched_sample_pass = bool(batched_sample_pass) and mode is not None and dm.smooth_batch_supported(mode)
         if self.batched_sample_pass:
-            seeds = np.array([int(p.device_rng_seed) & 0xFFFFFFFFFFFFFFFF for p in ps], dtype=np.uint64)
-            self._seeds = torch.as_tensor(seeds.view(np.int64)).to(device)          # the uint64 bits, uploaded once
+            self._seeds = seed_bits([p.device_rng_seed for p in ps], device)    # uploaded once
         self._std_u = None
 
-    # ---- results, per problem ---------------------------------------------------------------------
-    @property
-    def x_trj(self):
-        return np.stack([np.asarray(pr.x_trj, float) for pr in self.problems])
-
-    @property
-    def u_trj(self):
-        return np.stack([np.asarray(pr.u_trj, float) for pr in self.problems])
-
-    @property
-    def cost(self):
-        return np.array([pr.cost for pr in self.problems])
-
+    # ---- results, per problem (x_trj, u_trj, cost: StackedResults) ---------------------------------
     @property
     def x_trj_best(self):
         return [pr.x_trj_best for pr in self.problems]

@@ -1,9 +1,9 @@
-"""Calls into the thirteen sample-pass entries of the C ABI (csrc/smooth_api.hip) that must be refused BEFORE any
+"""Calls into the fifteen sample-pass entries of the C ABI (csrc/smooth_api.hip) that must be refused BEFORE any
 launch: every argument check, in every entry, and -- where two checks would fire -- which of them wins.  Pointers are
 fake non-null addresses: a refused call dereferences nothing, and no GPU is opened.
 
 cases() is the table, run(lib) its (return code, irs_last_error text) per (entry, case); size_cases() / sizes(lib) are
-the three size queries on a few dozen (model, mode, T, N, B).  The results of the library as it stood while these
+the four size queries on a few dozen (model, mode, T, N, B).  The results of the library as it stood while these
 entries still marshalled and checked by hand in csrc/smooth.hip are tests/golden/smooth_entry_errors.json;
 tests/test_smooth_entries_cpu.py holds every later library to them.
 `python -m tests.helpers.smooth_entry_cases OUT.json` records both tables from the library in the tree (or IRS_HIP_LIB).
@@ -39,12 +39,15 @@ ENTRIES = {
     "irs_smooth_run": ["call", "stream"],
     "irs_smooth_rng_batch": HEAD[:6] + ["B", "x_trj", "x_stride", "u_trj", "u_stride", "std_u_dev", "seed_dev", "iter",
                                         "sums"] + OUTS + TAIL,
+    "irs_smooth_rng_general_batch": HEAD[:6] + ["B", "x_trj", "x_stride", "u_trj", "u_stride", "std_x_dev", "std_u_dev",
+                                                "seed_dev", "iter", "sums"] + OUTS + TAIL,
     "irs_smooth_finalize": HEAD[:5] + ["n_total", "x_trj", "u_trj", "sums"] + OUTS + ["stream"],
     "irs_smooth_finalize_ws": HEAD[:5] + ["n_total", "x_trj", "u_trj", "sums"] + OUTS + TAIL,
     "irs_rng_samples": ["n", "m", "T", "N", "std_x", "std_u", "seed", "iter", "sample_offset", "dx", "du", "stream"],
     "irs_exact_linearize": ["model", "params", "n_params", "T", "x_trj", "u_trj", "At", "Bt", "ct", "stream"],
     "irs_workspace_init": TAIL,
     "irs_smooth_batch_workspace_init": TAIL,
+    "irs_smooth_general_batch_workspace_init": TAIL,
     "irs_smooth_geometry": ["model", "mode", "T", "N", "rng", "geometry_out"],
 }
 SINGLE = ("irs_smooth", "irs_smooth_rng", "irs_smooth_accumulate", "irs_smooth_accumulate_rng", "irs_smooth_run")
@@ -52,11 +55,13 @@ SINGLE = ("irs_smooth", "irs_smooth_rng", "irs_smooth_accumulate", "irs_smooth_a
 # what a call that would run looks like (never made): every case below overrides at least one of these so that it
 # is refused.  "model" stands for (model, params, n_params); std_x / std_u True = an array, None = a null pointer
 BASE = dict(model=PEND, mode=AB, T=10, N=100, B=3, n=2, m=1, rng=0, x_trj=PTR, u_trj=PTR, dx=PTR, du=PTR, std_x=True,
-            std_u=True, std_u_dev=PTR, seed_dev=PTR, seed=7, iter=1, sample_offset=0, sums=PTR, At=PTR, Bt=PTR, ct=PTR,
+            std_u=True, std_x_dev=PTR, std_u_dev=PTR, seed_dev=PTR, seed=7, iter=1, sample_offset=0, sums=PTR, At=PTR, Bt=PTR, ct=PTR,
             info=PTR, n_total=100, workspace=WS, workspace_bytes=BIG, stream=None, x_stride=BIG, u_stride=BIG,
             use_rng=0, fuse=True, geometry_out=True, env={})
 U_ONLY = dict(model=HAND, mode=ZB)             # a mode that never reads dx / std_x
 SERVED = dict(model=HAND_EXACT, mode=ZB, T=3, N=64)     # what the batch entry serves; one workgroup on any machine
+SERVED_GENERAL = dict(model=PEND, mode=AB, T=3, N=64)   # what the general batch entry serves (n = 2, m = 1)
+GENERAL_SLICE = 5120      # that shape's workspace slice: round256(irs_smooth_workspace_bytes) (sizes() records it, B = 1)
 
 
 def _single_cases(entry):
@@ -164,6 +169,45 @@ def _batch_cases():
         ("null_and_small_workspace", dict(s, workspace=None, workspace_bytes=8))]
 
 
+def _general_batch_cases():
+    s = SERVED_GENERAL
+    nulls = [("null_" + k, dict(s, **{k: None})) for k in ("x_trj", "u_trj", "std_x_dev", "std_u_dev", "seed_dev", "sums",
+                                                            "At", "Bt", "ct", "info")]
+    return nulls + [
+        ("B_zero", dict(s, B=0)), ("T_zero", dict(s, T=0)), ("N_zero", dict(s, N=0)),
+        ("T_beyond_counters", dict(s, T=1025)), ("rows_beyond_grid", dict(s, B=100, T=700)),
+        ("rows_at_grid_small_workspace", dict(s, B=21845, T=3, workspace_bytes=8)),
+        ("mode_three", dict(s, mode=3)), ("mode_negative", dict(s, mode=-1)),
+        ("unknown_model", dict(s, model=UNKNOWN)), ("swept_contact_model", dict(s, model=HAND)),
+        ("swept_contact_model_first_order", dict(s, model=HAND, mode=FIRST)),
+        ("planar_hand_exact", dict(s, model=HAND_EXACT)), ("planar_hand_exact_u_only", dict(s, model=HAND_EXACT, mode=ZB)),
+        ("planar_hand_exact_general_kernel", dict(s, model=HAND_EXACT, mode=ZB, env=GENERAL)),
+        ("zero_order_b", dict(s, mode=ZB)), ("zero_order_b_quadrotor", dict(s, model=QUAD, mode=ZB)),
+        ("first_order_small_workspace", dict(s, mode=FIRST, workspace_bytes=8)),
+        ("quadrotor_small_workspace", dict(s, model=QUAD, workspace_bytes=8)),
+        ("param_count", dict(s, n_params=3)), ("null_params", dict(s, params=None)),
+        ("short_x_stride", dict(s, x_stride=5)), ("short_u_stride", dict(s, u_stride=2)),
+        ("x_stride_exact_small_workspace", dict(s, x_stride=6, u_stride=3, workspace_bytes=8)),
+        ("null_workspace", dict(s, workspace=None)), ("small_workspace", dict(s, workspace_bytes=8)),
+        ("small_workspace_one_slice", dict(s, B=1, workspace_bytes=4096)),
+        ("workspace_one_slice_short", dict(s, workspace_bytes=2 * GENERAL_SLICE)),
+        ("workspace_one_byte_short", dict(s, workspace_bytes=3 * GENERAL_SLICE - 1)),
+        ("misaligned_workspace", dict(s, workspace=WS_OFF)),
+        # which of two faults is reported
+        ("B_zero_and_T_beyond_counters", dict(s, B=0, T=1025)),
+        ("B_zero_and_null_sums", dict(s, B=0, sums=None)),
+        ("T_beyond_counters_and_rows_beyond_grid", dict(s, T=1025, B=100)),
+        ("rows_beyond_grid_and_null_std_x_dev", dict(s, B=100, T=700, std_x_dev=None)),
+        ("null_info_and_mode_three", dict(s, info=None, mode=3)),
+        ("mode_three_and_unknown_model", dict(s, mode=3, model=UNKNOWN)),
+        ("swept_contact_model_and_param_count", dict(s, model=HAND, n_params=3)),
+        ("zero_order_b_and_null_params", dict(s, mode=ZB, params=None)),
+        ("param_count_and_short_x_stride", dict(s, n_params=3, x_stride=5)),
+        ("short_u_stride_and_null_workspace", dict(s, u_stride=2, workspace=None)),
+        ("small_and_misaligned_workspace", dict(s, workspace=WS_OFF, workspace_bytes=8)),
+        ("null_and_small_workspace", dict(s, workspace=None, workspace_bytes=8))]
+
+
 def _finalize_cases(entry):
     out = [("T_zero", dict(T=0)), ("n_total_zero", dict(n_total=0)), ("n_total_negative", dict(n_total=-3)),
            ("mode_three", dict(mode=3)), ("mode_negative", dict(mode=-1)), ("unknown_model", dict(model=UNKNOWN)),
@@ -189,6 +233,8 @@ def entry_cases(entry):
         return _single_cases(entry)
     if entry == "irs_smooth_rng_batch":
         return _batch_cases()
+    if entry == "irs_smooth_rng_general_batch":
+        return _general_batch_cases()
     if "finalize" in entry:
         return _finalize_cases(entry)
     if entry == "irs_rng_samples":
@@ -205,7 +251,7 @@ def entry_cases(entry):
     if entry == "irs_workspace_init":
         return [("null_workspace", dict(workspace=None)), ("no_bytes", dict(workspace_bytes=0)),
                 ("one_byte_short", dict(workspace_bytes=4095)), ("null_and_short", dict(workspace=None, workspace_bytes=8))]
-    if entry == "irs_smooth_batch_workspace_init":
+    if entry in ("irs_smooth_batch_workspace_init", "irs_smooth_general_batch_workspace_init"):
         return [("null_workspace", dict(workspace=None)), ("no_bytes", dict(workspace_bytes=0)),
                 ("null_and_no_bytes", dict(workspace=None, workspace_bytes=0))]
     assert entry == "irs_smooth_geometry"
@@ -303,6 +349,9 @@ def size_cases():
             (PEND, 3, 3, 100, 1, {}), (HAND_EXACT, -1, 3, 100, 1, {}), (PEND, AB, 0, 100, 1, {}), (PEND, AB, 3, 0, 1, {}),
             (HAND_EXACT, ZB, 3, 64, 0, {}), (HAND_EXACT, ZB, 0, 64, 3, {}), (HAND_EXACT, ZB, 3, -1, 3, {}),
             (HAND_EXACT, FIRST, 3, 64, -2, {})]
+    # what the general batch entry serves, and does not
+    out += [(PEND, FIRST, 3, 64, 1, {}), (PEND, AB, 3, 64, 1, {}), (QUAD, FIRST, 50, 448, 7, {}), (PEND, AB, 3, 64, 0, {}),
+            (QUAD, FIRST, 3, 64, -2, {}), (PEND, ZB, 3, 64, 3, {})]
     return out
 
 
@@ -312,13 +361,15 @@ def size_key(case):
 
 
 def sizes(lib):
-    """{key: [irs_sums_len, irs_smooth_workspace_bytes, irs_smooth_batch_workspace_bytes]}."""
+    """{key: [irs_sums_len, irs_smooth_workspace_bytes, irs_smooth_batch_workspace_bytes,
+    irs_smooth_general_batch_workspace_bytes]}."""
     out = {}
     for case in size_cases():
         model, mode, T, N, B, env = case
         with _environment(env):
             out[size_key(case)] = [lib.irs_sums_len(model, mode), lib.irs_smooth_workspace_bytes(model, mode, T, N),
-                                   lib.irs_smooth_batch_workspace_bytes(model, mode, T, N, B)]
+                                   lib.irs_smooth_batch_workspace_bytes(model, mode, T, N, B),
+                                   lib.irs_smooth_general_batch_workspace_bytes(model, mode, T, N, B)]
     return out
 
 

@@ -1,8 +1,8 @@
-"""The argument checks of the thirteen sample-pass entries (csrc/smooth_api.hip): every refused call of
+"""The argument checks of the fifteen sample-pass entries (csrc/smooth_api.hip): every refused call of
 tests/helpers/smooth_entry_cases.py returns the code and the exact irs_last_error text recorded in
 tests/golden/smooth_entry_errors.json -- from the library as it stood when each entry still marshalled and checked by
 hand.  Which check fires, in what order, under what name and with what numbers is thereby pinned for all of them, and
-so is what the three size queries answer.  No GPU is touched: every call of the table is refused before any HIP call.
+so is what the four size queries answer.  No GPU is touched: every call of the table is refused before any HIP call.
 (The sweep of irs_smooth_geometry over every model, mode and shape is tests/test_smooth_geometry_cpu.py, unchanged.)"""
 import json
 import os
@@ -36,7 +36,7 @@ def test_the_table_and_the_record_hold_the_same_cases(golden):
     keys = ["%s/%s" % (entry, name) for entry, name, _ in sc.cases()]
     assert len(keys) == len(set(keys))
     assert sorted(keys) == sorted(golden["refusals"])
-    assert {k.split("/")[0] for k in keys} == set(sc.ENTRIES) and len(sc.ENTRIES) == 13
+    assert {k.split("/")[0] for k in keys} == set(sc.ENTRIES) and len(sc.ENTRIES) == 15
     sizes = [sc.size_key(c) for c in sc.size_cases()]
     assert len(sizes) == len(set(sizes)) >= 36 and sorted(sizes) == sorted(golden["sizes"])
 
