@@ -24,6 +24,28 @@
  *    a thread-local message.  Numerical failures inside kernels (non-SPD Gram or
  *    Hessian) are reported through the DEV `info` arrays, LAPACK style.
  *  - `params` HOST: model constants, params[0] = h (step size); see irs_model_info.
+ *  - The verdict of a TV-LQR entry is its `info`, and the host classes trust that word alone.  Two rules hold at every
+ *    descent entry and at irs_tvlqr_riccati (tests/test_descent_verdicts_gpu.py):
+ *    V1, the step.  If exactly one step t* has a control Hessian that is not positive definite in the backward sweep --
+ *      the Hessians being those of the P computed from the steps after t*, in the form the kernel factors (alpha R +
+ *      B'PB; with the ADMM's rho/2 on the bounded components; [x; u_prev] for the position-controlled form) -- then
+ *      info[0] == t* + 1: for every position of t*, every position of the failing pivot, every problem of a batch; a
+ *      failing problem's neighbours keep their bits.  The first failure of the sweep is the one reported.
+ *    V2, non-finite data.  A call that is handed a NaN or +-Inf in an element of At, Bt, ct, xd_trj or x0 that reaches
+ *      one of its outputs never returns an all-clear.  Unbounded entries (irs_tvlqr_riccati, irs_tvlqr_descent,
+ *      irs_tvlqr_descent_batch): 1 <= info[0] <= T + 1 -- t + 1 where a pivot caught it, T + 1 ("no such step:
+ *      non-finite data", as irs_least_squares uses n + m + 1) where the pivots were fine but a stored gain or the
+ *      realised cost is not finite.  Bounded entries (the ADMM, active-set, batch, lazy, adaptive and box_values
+ *      descents): info[0] != 0 or info[2] != 0, the two words the host classes read -- a tail whose first control is not
+ *      finite counts as not converged in info[2] (a clipped control can make the realised trajectory finite again; what
+ *      never happens is three zero words), and a realised cost that is not finite gives info[0] = T + 1.  (Row 0 of
+ *      xd_trj reaches the cost only: irs_tvlqr_riccati, which returns no cost, does not see it.  NOT covered: a bounded
+ *      descent in which every tail that reads the poisoned step has its FIRST control pinned before the poison can reach
+ *      it -- a caller-supplied active set (act_io) or enforced set that pins step 0 of those tails: the first control is
+ *      then a finite bound, the multiplier tests are ordered compares a NaN fails, the tail reads as converged, and if
+ *      the plant keeps the realised trajectory and cost finite the three words are zero.  The tests are made on the
+ *      tail's first control and on the cost, not on its whole plan or its multipliers.)  Every test is made on
+ *      bit patterns, in integer arithmetic: it does not depend on how a floating-point compare treats a NaN.
  */
 #ifndef IRS_HIP_H
 #define IRS_HIP_H
@@ -329,7 +351,9 @@ int irs_exact_linearize(int model, const double *params, int n_params, int T,
  *   s.t. x_{t+1} = A_t x_t + B_t u_t + c_t
  * alpha_R = 0.5 reproduces Drake's AddQuadraticCost (tv_lqr.py:110).
  * Any n <= 32, m <= 16.  K (T,m,n), k (T,m) DEV f64 out: u_t = K_t x_t + k_t.
- * info (1) DEV int32: 0 ok, t+1 = Hessian not positive definite at step t.       */
+ * info (1) DEV int32: 0 ok, t+1 = Hessian not positive definite at step t -- the FIRST such step of the sweep, which
+ * runs from T-1 down (rule V1 above) -- or T+1: every pivot was fine but a stored gain is not finite (rule V2: a NaN or
+ * Inf in ct or xd_trj never meets a pivot).                                                                         */
 int irs_tvlqr_riccati(int n, int m, int T, const double *At, const double *Bt,
                       const double *ct, const double *Q, const double *Qd,
                       const double *R, double alpha_R, const double *xd_trj,
@@ -352,7 +376,9 @@ int irs_closed_loop_rollout(int model, const double *params, int n_params, int T
 
 /* irs_tvlqr_riccati + irs_closed_loop_rollout in ONE launch: everything
  * IrsLqr.local_descent does after get_TV_matrices (irs_lqr/irs_lqr.py:169-184) plus
- * evaluate_cost (:121-137) of the new trajectory.  x0 (n) DEV.                    */
+ * evaluate_cost (:121-137) of the new trajectory.  x0 (n) DEV.
+ * info (1): as irs_tvlqr_riccati (V1: t+1 of the first Hessian that is not positive definite); T+1 also when the
+ * pivots and gains were fine but the realised cost is not finite (V2: x0, a rollout that left the range of f64).  */
 int irs_tvlqr_descent(int model, const double *params, int n_params, int T,
                       const double *At, const double *Bt, const double *ct,
                       const double *Q, const double *Qd, const double *R, double alpha_R,
@@ -364,7 +390,8 @@ int irs_tvlqr_descent(int model, const double *params, int n_params, int T,
  * every Riccati path (the model and T choose it as in the single call).
  * In (DEV f64, B contiguous blocks): At (B,T,n,n), Bt (B,T,n,m), ct (B,T,n), xd_trj (B,T+1,n), x0 (B,n); shared by
  *      the problems: the model and its params, T, Q, Qd, R, alpha_R.
- * Out: K (B,T,m,n), k (B,T,m), x_new (B,T+1,n), u_new (B,T,m), cost (B) DEV f64, info (B) DEV int.
+ * Out: K (B,T,m,n), k (B,T,m), x_new (B,T+1,n), u_new (B,T,m), cost (B) DEV f64, info (B) DEV int: problem b's
+ *      verdict, by the rules V1 and V2 of the single entry; a failing or poisoned problem changes no bit of another's.
  * Every argument error is decided before the first HIP call:
  *   IRS_ERR_INVALID_ARG  B <= 0, T <= 0, a null pointer, wrong n_params
  *   IRS_ERR_UNSUPPORTED  an unknown model; a contact model (irs_quasistatic_box_descent_batch is its batched descent) */
@@ -381,8 +408,11 @@ int irs_tvlqr_descent_batch(int model, const double *params, int n_params, int T
  * factorisation, warm started from tail to tail.  xlo,xhi (n), ulo,uhi (m) DEV f64, +-inf =
  * unbounded, applied to x_1..x_T and u_0..u_{T-1}.  rho > 0 ADMM penalty, 0 < relax < 2
  * over-relaxation, stop at max(primal, dual residual) < eps or max_iter.
- * info (3) DEV int32: [0] t+1 of a non-PD Hessian (0 ok), [1] most ADMM iterations any tail
- * needed, [2] number of tails that stopped at max_iter.  One launch; the factorisation lives
+ * info (3) DEV int32: [0] t+1 of a non-PD Hessian (0 ok; V1: the first one of the sweep, the Hessians carrying the
+ * rho/2 of the bounded components; T+1: the realised cost is not finite), [1] most ADMM iterations any tail
+ * needed, [2] number of tails that stopped at max_iter or whose first control is not finite (V2: the residuals are
+ * maxima, which drop a NaN -- a poisoned tail is never "converged").  The lazy, adaptive, workspace and batch entries
+ * and irs_tvlqr_box_solve report by the same rules.  One launch; the factorisation lives
  * in LDS, so T is limited (irs_tvlqr_box_lds_bytes(model,T) <= ~160 KB); irs_tvlqr_box_descent_wsx
  * runs longer horizons with the factor records in a workspace in HBM.                      */
 int irs_tvlqr_box_descent(int model, const double *params, int n_params, int T,
@@ -464,8 +494,11 @@ int irs_tvlqr_box_descent_wsx(int model, const double *params, int n_params, int
  *   hand T <= 53, box pivoting T <= 123) and
  *   otherwise live in the workspace of irs_quasistatic_box_descent_wsx;
  *   0 = 3 where it applies (on chip, or a workspace was given), else 2 where it fits LDS, else 1.
- * cost (1) DEV (may be NULL); info (3): [0] t+1 of a non-PD Hessian, [1] most iterations any tail
- * needed, [2] number of tails that did not converge.                                          */
+ * cost (1) DEV (may be NULL); info (3): [0] t+1 of a non-PD Hessian (V1: the first one of the first backward sweep,
+ * which starts from the empty active set and factors the full Hessian of every step; T+1: the realised cost is not
+ * finite), [1] most iterations any tail needed, [2] number of tails that did not converge -- a tail whose first
+ * control is not finite has not (V2), whichever solver ran.  The verdict of solver 3, whose translation unit is
+ * compiled with -fno-honor-nans, is decided on bit patterns like every other.  _ws, _wsx, _set, _lazy, _batch: the same.  */
 int irs_quasistatic_box_descent(int model, const double *params, int n_params, int T,
                                 const double *At, const double *Bt, const double *ct,
                                 const double *Q, const double *Qd, const double *R,
@@ -688,9 +721,11 @@ int irs_smooth_values(int n, int m, int T, int N, const double *x_trj, const dou
  *   workspace: DEV, 256-byte aligned, >= irs_box_values_workspace_bytes(n, m, T).  It holds the state of a descent --
  *   a header, the masks, the T factor records, the warm start (w, y) -- from `begin` to the last `tail`; one descent
  *   at a time per workspace.  It need not be initialised: `begin` writes all of it, the header last.
- *   info (3) DEV: begin writes [t+1 of a non-PD Hessian or 0, 0, 0]; each tail updates [1] = most ADMM iterations of
- *   any tail so far, [2] += 1 if it stopped at max_iter.  A tail whose workspace header does not match (n, m, T,
- *   begun) writes info[0] = -1 and nothing else.
+ *   info (3) DEV: begin writes [t+1 of a non-PD Hessian or 0, 0, 0] -- V1: the first such step of the sweep; V2: T+1
+ *   where the pivots were fine but an entry of a factor record is not finite (c_t and xd_t reach the records, never a
+ *   pivot); each tail updates [1] = most ADMM iterations of any tail so far, [2] += 1 if it stopped at max_iter or its
+ *   first control is not finite (V2: x_t).  A tail whose workspace header does not match (n, m, T, begun) writes
+ *   info[0] = -1 and nothing else.
  * Every argument error is decided before the first HIP call:
  *   IRS_ERR_INVALID_ARG  n, m, T or t out of range; a null pointer; x_rows / u_rows not as above; rho <= 0; relax
  *                        outside (0, 2); max_iter <= 0; eps <= 0

@@ -418,6 +418,16 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
                 }
             }
         }
+        // A tail whose first control is not finite has not converged, whatever the residuals say: fmin / fmax drop a
+        // NaN, so the projection of a poisoned plan lands on a bound and both residuals can read zero.  A NaN or Inf in
+        // the data of steps >= tau reaches this control through the backward sweep.  (Bit test, wave.hpp; every lane
+        // reads the same M values.)
+        {
+            unsigned nf = 0;
+#pragma unroll
+            for (int j = 0; j < M; ++j) nf = max(nf, expo_bits(zu[(size_t)tau * M + j]));
+            if (nf == kExpoOnes) conv = false;
+        }
         it_max = max(it_max, it);
         if constexpr (ADAPT) n_iter += it;
         n_fail += conv ? 0 : 1;
@@ -480,7 +490,9 @@ __global__ __launch_bounds__(64) void box_descent_kernel(BoxArgs a, double* recs
         cost += quad(DU ? a.Qd : a.Q, e, NR);       // terminal: Qd (quasistatic :160-168) vs Q (irs_lqr.py:135-136)
     }
     if (lane == 0) {
-        a.info[0] = bad; a.info[1] = it_max; a.info[2] = n_fail;
+        // pivots fine but the realised cost not finite (it sums over every x_t, u_t and xd_t): T + 1, "no such step"
+        a.info[0] = bad != 0 ? bad : (nonfinite_bits(cost) ? T + 1 : 0);
+        a.info[1] = it_max; a.info[2] = n_fail;
         if (a.cost) a.cost[0] = cost;
     }
     if constexpr (ADAPT) {

@@ -115,6 +115,7 @@ __global__ __launch_bounds__(64) void box_values_begin_kernel(BeginArgs a) {
     const double hr = 0.5 * a.rho;
     auto qs = [&](const double* Qm, int i, int j) -> double { return 0.5 * (Qm[i * n + j] + Qm[j * n + i]); };
     int bad = 0;
+    unsigned nf = 0;                                  // exponent bits of what this lane stores for the tails (wave.hpp)
     // P_T = Qd + rho/2 Mx ; qx_T = Qd xd_T
     for (int q = lane; q < n * n; q += 64) {
         const int i = q / n, j = q % n;
@@ -124,6 +125,7 @@ __global__ __launch_bounds__(64) void box_values_begin_kernel(BeginArgs a) {
         double s = 0.0;
         for (int j = 0; j < n; ++j) s += qs(a.Qd, lane, j) * a.xd[(size_t)T * n + j];
         ws[W.oQxT + lane] = s;
+        nf = max(nf, expo_bits(s));
     }
     wave_sync();
     // ---- backward Riccati with Q^ = Q + rho/2 Mx, R^ = alpha R + rho/2 Mu (boxqp_factor.inc, runtime sizes) ----
@@ -245,14 +247,20 @@ __global__ __launch_bounds__(64) void box_values_begin_kernel(BeginArgs a) {
         {                                             // the finished record, once, to the workspace
             const v2d* src = reinterpret_cast<const v2d*>(rec);
             gv2d* dst = (gv2d*)(a.ws + W.oRec + (size_t)t * L.SP);
-            for (int c = lane; c < L.SP / 2; c += 64) dst[c] = src[c];
+            for (int c = lane; c < L.SP / 2; c += 64) {
+                const v2d v = src[c];
+                dst[c] = v;
+                nf = max(nf, max(expo_bits(v[0]), expo_bits(v[1])));
+            }
         }
         wave_sync();
     }
+    // pivots fine but a record entry not finite (c_t and xd_t reach d_t and Q xd_t, never a pivot): T + 1
+    const bool nfw = __any(nf == kExpoOnes);
     if (lane == 0) {
         ws[1] = (double)n; ws[2] = (double)m; ws[3] = (double)T; ws[4] = a.rho; ws[5] = a.relax; ws[6] = 0.0; ws[7] = 0.0;
         ws[0] = kBegun;
-        a.info[0] = bad; a.info[1] = 0; a.info[2] = 0;
+        a.info[0] = bad != 0 ? bad : (nfw ? T + 1 : 0); a.info[1] = 0; a.info[2] = 0;
     }
 }
 
@@ -443,6 +451,10 @@ __global__ __launch_bounds__(64) void box_values_tail_kernel(TailArgs a) {
         for (int q = lane; q < (T + 1 - tau) * n; q += 64) a.x_plan[q] = zx[(size_t)tau * n + q];
     if (a.u_plan != nullptr)
         for (int q = lane; q < (T - tau) * m; q += 64) a.u_plan[q] = zu[(size_t)tau * m + q];
+    // a first control that is not finite: the tail has not converged, whatever the residuals say (fmin / fmax drop a
+    // NaN, so a poisoned plan projects onto a bound and both residuals can read zero); bit test, wave.hpp
+    const bool nfw = __any(lane < m && nonfinite_bits(zu[(size_t)tau * m + (lane < m ? lane : 0)]));
+    if (nfw) conv = false;
     if (lane == 0) {
         a.info[1] = max(a.info[1], it);
         a.info[2] += conv ? 0 : 1;

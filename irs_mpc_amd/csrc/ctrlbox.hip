@@ -74,6 +74,7 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
     double* sstart = Rsym + M * M;                     // NS   (plant -> solver)
     double* uctl = sstart + NS;                        // M: the tail's first control, clipped (solver -> plant)
     int* tri = reinterpret_cast<int*>(uctl + M);       // (i << 8 | j), i <= j, of the upper triangle
+    double* cflag = uctl + M + (L::NTRI + 1) / 2;      // 1: the cost is not finite (plant -> solver; in the layout's slack)
 
     auto rec_ = [&](int t) -> double* { return F + (size_t)t * L::S; };
     // problem data of the LQR in s = [x; w]
@@ -160,6 +161,9 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
             cost += quad(Qdsym, e, NR);
         }
         if (lane == 0 && a.cost) a.cost[0] = cost;
+        // the verdict on the cost (it sums over every x_t, u_t, xd_t of the descent), for the solver wave's info
+        if (lane == 0) cflag[0] = nonfinite_bits(cost) ? 1.0 : 0.0;
+        wg_barrier();                                       // C: the cost is judged
         return;
     }
 
@@ -580,6 +584,10 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
                 }
             }
         }
+        // A tail whose first control is not finite has not converged: every test above is an ordered compare, which a
+        // NaN fails, so a poisoned plan changes no active set and looks settled -- and the clip below (fmin / fmax
+        // drop a NaN) would hand the plant a bound.  Decided on the bit pattern (wave.hpp), before the clip.
+        if (__any(lane < M && nonfinite_bits(rec_(tau)[L::ou + (lane < M ? lane : 0)]))) conv = false;
         it_max = max(it_max, iters);
         n_fail += conv ? 0 : 1;
         full = !conv;
@@ -593,8 +601,11 @@ __global__ __launch_bounds__(128) void ctrlbox_descent_kernel(BoxArgs a) {
         }
         wg_barrier();                                  // B(tau)
     }
+    wg_barrier();                                      // C: the plant has judged the cost (cflag)
     if (lane == 0) {
-        a.info[0] = bad; a.info[1] = it_max; a.info[2] = n_fail;
+        // pivots fine but the realised cost not finite: T + 1, "no such step: non-finite data"
+        a.info[0] = bad != 0 ? bad : (cflag[0] != 0.0 ? T + 1 : 0);
+        a.info[1] = it_max; a.info[2] = n_fail;
     }
 }
 

@@ -264,6 +264,10 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
             cost += quad(Qdsym, e, NR);
         }
         if (lane == 0 && a.cost) a.cost[0] = cost;
+        // the verdict on the cost (it sums over every x_t, u_t, xd_t of the descent), for the solver wave's info: a bit
+        // test, this file is compiled with -fno-honor-nans.  Through the first slack double behind uctl.
+        if (lane == 0) uctl[M] = nonfinite_bits(cost) ? 1.0 : 0.0;
+        wg_barrier();                                       // C: the cost is judged
         return;
     }
 
@@ -629,16 +633,20 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                         rhs[i] = fma(hsel, hb0 + hb1, gc[i]) * mf[i];
                     }
                 }
-                bool spd = true;
+                // Positive definite <=> every leading pivot is positive -- and finite: decided on the bit patterns
+                // (pivot_word, wave.hpp: one integer maximum over the step's pivots, one compare).  This file is compiled
+                // with -fno-honor-nans, under which an ordered compare may be folded as if its operands were numbers:
+                // `p > 0.0` proves nothing about a NaN.
+                unsigned pw = 0;
                 auto inv2 = [&](double p, double q, double r, double& ip, double& iq, double& ir) {
                     // [p q; q r]^-1 = [r -q; -q p] / (p r - q^2)
                     const double det = fma(p, r, -q * q);
-                    spd = spd && p > 0.0 && det > 0.0;
+                    pw = max(pw, max(pivot_word(p), pivot_word(det)));
                     const double id = fast_rcp(det);
                     ip = r * id; iq = -q * id; ir = p * id;
                 };
                 if constexpr (M == 1) {
-                    spd = Hm[0][0] > 0.0;
+                    pw = pivot_word(Hm[0][0]);
                     Hi[0][0] = fast_rcp(Hm[0][0]);
                 } else if constexpr (M == 2) {
                     inv2(Hm[0][0], Hm[0][1], Hm[1][1], Hi[0][0], Hi[0][1], Hi[1][1]);
@@ -666,7 +674,7 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                     y[0] = t0 - fma(w00, y[2], w01 * y[3]);
                     y[1] = t1 - fma(w10, y[2], w11 * y[3]);
                 }
-                if (!spd && bad == 0) bad = t + 1;
+                if (pw >= kPivotBad && bad == 0) bad = t + 1;
                 if constexpr (M != 4) {
     #pragma unroll
                     for (int i = 0; i < M; ++i) {
@@ -1074,8 +1082,12 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                 const double wm = wave_max(rworst);
                 if (wm > 0.0) {
                     const int qw = wave_min(rworst == wm ? rq : 0x7fffffff);      // first index among equals
-                    if (lane == 0) { act_[qw] = 0.0; sig_[qw / M] = -1.0; }
-                    chg = max(chg, qw / M);
+                    // (the integer guard: with a NaN among the multipliers no lane need own `wm`, and under
+                    // -fno-honor-nans the compare above may pass all the same -- the sentinel is never an index)
+                    if (qw < T * M) {
+                        if (lane == 0) { act_[qw] = 0.0; sig_[qw / M] = -1.0; }
+                        chg = max(chg, qw / M);
+                    }
                 }
             }
             rsync();
@@ -1145,6 +1157,7 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                 const double alpha = wave_min(best);
                 if (alpha < 1.0) {
                     const int qb = wave_min(best == alpha ? bq : 0x7fffffff);
+                    if (qb >= T * M) break;            // no lane owns the step (non-finite data): the sentinel is no index
                     for (int q = t0 * M + lane; q < T * M; q += 64) {
                         const double u = uu_[q], d = us_[q] - u;
                         if (q == qb) {
@@ -1175,6 +1188,7 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
                     conv = true;
                 } else {
                     const int qw = wave_min(worst == wmax ? wq : 0x7fffffff);
+                    if (qw >= T * M) break;            // likewise
                     if (lane == 0) { act_[qw] = 0.0; sig_[qw / M] = -1.0; }
                     rsync();
                     t_dirty = qw / M;
@@ -1184,21 +1198,31 @@ __global__ __launch_bounds__(128) void ctrlbox_mfma_kernel(BoxArgs a, double* gw
 #ifdef IRS_CBM_STAMPS
         st_acc[17] += iters;
 #endif
-        it_max = max(it_max, iters);
-        n_fail += conv ? 0 : 1;
-        full = !conv;
+        // A tail whose first control is not finite has not converged: a NaN changes no active set above, whichever
+        // way its compares fall, and the clip below would hand the plant a bound in its place.  Decided on the bit
+        // pattern, before the clip -- on the value the clip reads anyway.
         if (tau == 0 && a.act_io != nullptr) {
             for (int q = lane; q < T * M; q += 64) a.act_io[q] = act_[q];
         }
         // first control of the tail solution (clipped) -> the plant
+        bool nfu = false;
         if (lane < M) {
             const size_t q = (size_t)tau * M + lane;
-            uctl[lane] = fmin(fmax(uu_[q], lo_[q]), hi_[q]);
+            const double u0 = uu_[q];
+            nfu = nonfinite_bits(u0);
+            uctl[lane] = fmin(fmax(u0, lo_[q]), hi_[q]);
         }
+        if (__any(nfu)) conv = false;
+        it_max = max(it_max, iters);
+        n_fail += conv ? 0 : 1;
+        full = !conv;
         wg_barrier();                                  // B(tau)
     }
+    wg_barrier();                                      // C: the plant has judged the cost (uctl[M])
     if (lane == 0) {
-        a.info[0] = bad; a.info[1] = it_max; a.info[2] = n_fail;
+        // pivots fine but the realised cost not finite: T + 1, "no such step: non-finite data"
+        a.info[0] = bad != 0 ? bad : (uctl[M] != 0.0 ? T + 1 : 0);
+        a.info[1] = it_max; a.info[2] = n_fail;
     }
 #ifdef IRS_CBM_STAMPS
     if (lane == 0 && stamps != nullptr) {

@@ -57,6 +57,11 @@ __device__ __forceinline__ void riccati_backward(const RiccatiArgs& a, int lane,
         }
     }
     if (lane == 0) S.bad = 0;
+    // exponent bits of the gains this lane stores at the LAST step of the sweep, t = 0 (wave.hpp).  They speak for every
+    // step: +, x and the rcp-free solves never turn a NaN or Inf back into a number (Inf - Inf, 0 x Inf are NaN), so a
+    // k_t that is not finite stays in p and reaches k_0, and a K_t that is not finite makes P_t and with it H_{t-1} not
+    // finite -- a NaN pivot is caught there, a +Inf pivot gives gains Inf x 0 = NaN one step on.  One test per launch.
+    unsigned nf = 0;
     // step T-1 operands
     {
         const double* At = a.At + (size_t)(T - 1) * NN;
@@ -179,6 +184,7 @@ __device__ __forceinline__ void riccati_backward(const RiccatiArgs& a, int lane,
                         S.kt[i] = -y[i];
                         a.k[(size_t)t * M + i] = -y[i];
                     }
+                    if (t == 0) nf = max(nf, expo_bits(y[i]));
                 }
             }
         }
@@ -238,7 +244,9 @@ __device__ __forceinline__ void riccati_backward(const RiccatiArgs& a, int lane,
         if (lane < N) { S.c[lane] = rc; S.xd[lane] = rxd; }
         wave_sync();
     }
-    if (lane == 0) a.info[0] = S.bad;
+    // pivots fine but a stored gain not finite (a NaN or Inf in ct or xd_trj never meets a pivot): T + 1
+    const bool nfw = __any(nf == kExpoOnes);
+    if (lane == 0) a.info[0] = S.bad != 0 ? S.bad : (nfw ? T + 1 : 0);
 }
 
 // Tiny systems (N <= 4): the whole recursion lives in registers, every lane carrying
@@ -281,6 +289,7 @@ __device__ __forceinline__ void riccati_backward_reg(const RiccatiArgs& a, int l
     };
     fetch(T - 1);
     int bad = 0;
+    unsigned nf = 0;                                 // exponent bits of the stored gains (every lane the same)
     for (int t = T - 1; t >= 0; --t) {
         double A[N][N], B[N][M], c[N], xd[N];
 #pragma unroll
@@ -369,6 +378,7 @@ __device__ __forceinline__ void riccati_backward_reg(const RiccatiArgs& a, int l
             for (int i = 0; i < M; ++i) {
                 if (col < N) K[i][col < N ? col : 0] = -y[i];
                 else kk[i] = -y[i];
+                if (t == 0) nf = max(nf, expo_bits(y[i]));
             }
         }
         if (lane == 0) {
@@ -415,7 +425,7 @@ __device__ __forceinline__ void riccati_backward_reg(const RiccatiArgs& a, int l
             p[i] = pn[i];
         }
     }
-    if (lane == 0) a.info[0] = bad;
+    if (lane == 0) a.info[0] = bad != 0 ? bad : (nf == kExpoOnes ? T + 1 : 0);
 }
 
 // ------------------------------------------------------------------ matrix-core path
@@ -534,6 +544,7 @@ __device__ __forceinline__ void riccati_backward_mfma(const RiccatiArgs& a, int 
     for (int r = 0; r < 4; ++r) qn[r] = qx[(T - 1) * N + qidx[r]];
     bool ok = true;
     int bad_t = 0;
+    unsigned nf = 0;                                 // exponent bits of the gain elements this lane stores
 #ifdef IRS_RIC_STAMPS
     long long rs_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rm_ = __builtin_amdgcn_s_memtime();
 #endif
@@ -617,6 +628,7 @@ __device__ __forceinline__ void riccati_backward_mfma(const RiccatiArgs& a, int 
         for (int i = 0; i < M; ++i) Kb = (i == rg) ? -y[i] : Kb;
         if (rg >= M || col > N) Kb = 0.0;
         if (kst != nullptr) kst[(size_t)t * kstr] = Kb;
+        if (t == 0) nf = max(nf, expo_bits(Kb));      // (the last step's gains: see riccati_backward)
         asm volatile("" :: "v"(Kb));
         RIC_MARK(2);                                  // column gather, substitutions, gain, store
         // A~cl = A~ + B~ K~ ; W = P~ A~cl ; Joseph form  P~ <- Q~_t + K~'(aR)K~ + A~cl' W.
@@ -649,7 +661,8 @@ __device__ __forceinline__ void riccati_backward_mfma(const RiccatiArgs& a, int 
         ric_stamps[4] = T;
     }
 #endif
-    if (lane == 0) a.info[0] = bad_t;
+    const bool nfw = __any(nf == kExpoOnes);
+    if (lane == 0) a.info[0] = bad_t != 0 ? bad_t : (nfw ? T + 1 : 0);
 }
 
 template <int N, int M>
@@ -696,6 +709,7 @@ __global__ __launch_bounds__(64) void riccati_kernel(RiccatiArgs a) {
     sym_part(Qs, a.Q, n, 0.5, lane);
     sym_part(Rs, a.R, m, 0.5, lane);
     if (lane == 0) bad = 0;
+    unsigned nf = 0;                                 // exponent bits of the gains this lane stores
     wave_sync();
     if (lane < n) {
         double s = 0.0;
@@ -777,8 +791,14 @@ __global__ __launch_bounds__(64) void riccati_kernel(RiccatiArgs a) {
             }
         }
         wave_sync();
-        for (int q = lane; q < m * n; q += 64) a.K[(size_t)t * m * n + q] = Kt[q];
-        if (lane < m) a.k[(size_t)t * m + lane] = kt[lane];
+        for (int q = lane; q < m * n; q += 64) {
+            a.K[(size_t)t * m * n + q] = Kt[q];
+            if (t == 0) nf = max(nf, expo_bits(Kt[q]));
+        }
+        if (lane < m) {
+            a.k[(size_t)t * m + lane] = kt[lane];
+            if (t == 0) nf = max(nf, expo_bits(kt[lane]));
+        }
         for (int q = lane; q < n * n; q += 64) {
             int i = q / n, j = q % n;
             double s = A[q];
@@ -810,7 +830,8 @@ __global__ __launch_bounds__(64) void riccati_kernel(RiccatiArgs a) {
         if (lane < n) pv[lane] = pnew;
         wave_sync();
     }
-    if (lane == 0) a.info[0] = bad;
+    const bool nfw = __any(nf == kExpoOnes);
+    if (lane == 0) a.info[0] = bad != 0 ? bad : (nfw ? T + 1 : 0);
 }
 
 __global__ __launch_bounds__(64) void linear_rollout_kernel(int n, int m, int T, const double* At,
@@ -872,8 +893,10 @@ struct RolloutLds {
 // dynamics + evaluate_cost.  Sequential in t: every lane of the single wave carries
 // the same state in registers (no divergence, no broadcasts); lane 0 stores.  The
 // next step's gains / references are prefetched into registers, staged through LDS.
+// Returns the cost (every lane).  It sums over every x_t, u_t and xd_t of the rollout, and a NaN or Inf in any of them
+// makes it NaN or Inf (0 * NaN and Inf - Inf are NaN): its bit pattern is the descent's test for non-finite data.
 template <class Model>
-__device__ __forceinline__ void rollout_device(const ModelParams& p, int T, const double* K, const double* k,
+__device__ __forceinline__ double rollout_device(const ModelParams& p, int T, const double* K, const double* k,
                                                const double* u_in, const double* x0, const double* Q,
                                                const double* R, const double* xd_trj, double* x_out,
                                                double* u_out, double* cost_out, int lane,
@@ -970,7 +993,7 @@ __device__ __forceinline__ void rollout_device(const ModelParams& p, int T, cons
             cost += eT[i] * r;
         }
         if (lane == 0) cost_out[0] = cost;
-        return;
+        return cost;
     }
     for (int q = lane; q < n * n; q += 64) S.Q[q] = Q[q];
     for (int q = lane; q < m * m; q += 64) S.R[q] = R[q];
@@ -1061,6 +1084,7 @@ __device__ __forceinline__ void rollout_device(const ModelParams& p, int T, cons
 #pragma unroll
     for (int sft = 32; sft >= 1; sft >>= 1) cost += __shfl_xor(cost, sft, 64);
     if (lane == 0) cost_out[0] = cost;
+    return cost;
 }
 
 template <class Model>
@@ -1071,6 +1095,13 @@ __global__ __launch_bounds__(64) void rollout_kernel(ModelParams p, int T, const
                                                      double* x_out, double* u_out, double* cost_out) {
     __shared__ RolloutLds<Model> S;
     rollout_device<Model>(p, T, K, k, u_in, x0, Q, R, xd_trj, x_out, u_out, cost_out, threadIdx.x, S);
+}
+
+// The verdict of a descent after its rollout: the backward pass has written info[0] (a bad pivot's t + 1, T + 1 for a
+// gain that is not finite, else 0); a clean word becomes T + 1 when the rollout's cost is not finite (x0, a state that
+// diverged).  Lane 0 wrote that word and reads it back: one thread, one address, program order.
+__device__ __forceinline__ void descent_verdict(const RiccatiArgs& a, double cost, int lane) {
+    if (lane == 0 && nonfinite_bits(cost) && a.info[0] == 0) a.info[0] = a.T + 1;
 }
 
 // One launch for the whole of IrsLqr.local_descent after get_TV_matrices
@@ -1088,7 +1119,9 @@ __global__ __launch_bounds__(64) void descent_kernel(ModelParams p, RiccatiArgs 
     // the gains were stored by this very wave: drain the stores, then re-read them
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    rollout_device<Model>(p, a.T, a.K, a.k, nullptr, x0, a.Q, a.R, a.xd, x_new, u_new, cost_out, lane, S2);
+    const double cost = rollout_device<Model>(p, a.T, a.K, a.k, nullptr, x0, a.Q, a.R, a.xd, x_new, u_new, cost_out,
+                                              lane, S2);
+    descent_verdict(a, cost, lane);
     // fused iterate (iterate.hip), no bounds: this descent's row of the info history -- [0] Riccati info,
     // [1] timesteps whose smoothing solve failed, the rest zero -- without a launch of its own
     if (row != nullptr) {
@@ -1125,8 +1158,9 @@ __global__ __launch_bounds__(64) void descent_batch_kernel(ModelParams p, Riccat
     // the gains were stored by this very wave: drain the stores, then re-read them
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    rollout_device<Model>(p, a.T, a.K, a.k, nullptr, x0 + b * n, a.Q, a.R, a.xd, x_new + b * (T + 1) * n,
-                          u_new + b * T * m, cost_out + b, lane, S2);
+    const double cost = rollout_device<Model>(p, a.T, a.K, a.k, nullptr, x0 + b * n, a.Q, a.R, a.xd,
+                                              x_new + b * (T + 1) * n, u_new + b * T * m, cost_out + b, lane, S2);
+    descent_verdict(a, cost, lane);
 }
 
 // evaluate_cost of a given trajectory pair: lanes stride over t, f64 wave reduction.

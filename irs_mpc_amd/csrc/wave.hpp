@@ -32,6 +32,36 @@ __device__ __forceinline__ double fast_rcp(double d) {
     return r;
 }
 
+// The verdicts of the descents (`info`) must not depend on how a floating-point compare treats a NaN -- one of these
+// translation units is compiled with -fno-honor-nans, where `!(x > 0.0)` may be folded as if x were a number -- so
+// they are decided on the bit pattern, in integer arithmetic.
+// expo_bits: the exponent field of v in place (bits 20..30 of its high word); all ones <=> v is +-Inf or a NaN.
+// An accumulator `e = max(e, expo_bits(v))` over the values a kernel stores is all ones at the end iff one of them
+// was not finite: two integer operations per value, no compare, no branch.
+// (expo_bits is for the units compiled with IEEE semantics -- tvlqr, boxqp, boxqp_values: it sits in their step loops
+// and stays transparent to the scheduler.  Under -fno-honor-nans the compiler knows a double "is no NaN", sees through
+// the cast and folds the test to "is infinite"; the two predicates below therefore pass the bits through an opaque
+// register move first, as the sample pass does under -ffinite-math-only (smooth_common.hpp), and hold in every unit.)
+constexpr unsigned kExpoOnes = 0x7ff00000u;
+__device__ __forceinline__ unsigned expo_bits(double v) { return (unsigned)__double2hiint(v) & kExpoOnes; }
+__device__ __forceinline__ bool nonfinite_bits(double v) {
+    unsigned hi = (unsigned)__double2hiint(v);
+    asm("" : "+v"(hi));
+    return (hi & kExpoOnes) == kExpoOnes;
+}
+
+// The same test for SEVERAL pivots at one compare (the matrix-core active-set kernel tests two to four per backward
+// step, on a lone wave that pays for every instruction): pivot_word(v) < kPivotBad <=> v is a positive, finite, NORMAL
+// number -- the high word minus the smallest normal exponent wraps zero and denormals (a pivot below 2.2e-308 is no
+// pivot) to the top of the unsigned range, where the negative numbers, the infinities and the NaNs already are -- so
+// max over the pivots' words < kPivotBad <=> all of them are good: a subtraction and a maximum per pivot.
+constexpr unsigned kPivotBad = 0x7fe00000u;
+__device__ __forceinline__ unsigned pivot_word(double v) {
+    unsigned hi = (unsigned)__double2hiint(v);
+    asm("" : "+v"(hi));
+    return hi - 0x00100000u;
+}
+
 // lane `src_lane` (wave-uniform) to every lane
 __device__ __forceinline__ double readlane_f64(double v, int src_lane) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane);

@@ -83,6 +83,80 @@ def tvlqr_riccati(At, Bt, ct, Q, Qd, R, xd_trj, alpha_R=0.5):
     return K, k
 
 
+def pivot_trace(At, Bt, Q, Qd, R, alpha_R=0.5, cross=None, half_rho=0.0, pen_x=None, pen_u=None):
+    """The control Hessians of the backward sweep, in extended precision, up to the first one that is not positive
+    definite -- the reference of the descents' `info[0]` (include/irs_hip.h, rule V1).
+
+    Stage cost z'Q^z + 2 z'S v + v'R^v, terminal z'Qd^z (the linear terms do not enter a Hessian):
+        H_t = R^ + B_t'P_{t+1}B_t,   G_t = S' + B_t'P_{t+1}A_t,   P_t = Q^ + A_t'P_{t+1}A_t - G_t'H_t^-1 G_t,   P_T = Qd^.
+      cross     S (n,m), None = 0: the position-controlled QP written on the absolute command (position_controlled_form)
+      half_rho, pen_x (n), pen_u (m): the ADMM's penalised weights as csrc/boxqp_factor.inc states them,
+                Q^ = sym(Q) + rho/2 Mx,  Qd^ = sym(Qd) + rho/2 Mx,  R^ = alpha_R sym(R) + rho/2 Mu,
+                Mx / Mu = diag of the 0/1 masks of the finitely bounded components (None = no penalty).
+    Returns (t_bad, H): H[t] = H_t (m,m) for t = T-1 down to t_bad, where the Cholesky factorisation of H_{t_bad}
+    fails and the sweep stops -- the Hessians are those of the P computed from the steps after t_bad; t_bad = None
+    (and H holds every step) when all of them are positive definite."""
+    At, Bt = np.asarray(At, dtype=LD), np.asarray(Bt, dtype=LD)
+    T, n, m = At.shape[0], At.shape[1], Bt.shape[2]
+    Mx = np.diag(np.asarray(pen_x if pen_x is not None else np.zeros(n), dtype=LD)) * LD(half_rho)
+    Mu = np.diag(np.asarray(pen_u if pen_u is not None else np.zeros(m), dtype=LD)) * LD(half_rho)
+    Qh, Rh = sym(Q) + Mx, LD(alpha_R) * sym(R) + Mu
+    S = np.zeros((n, m), dtype=LD) if cross is None else np.asarray(cross, dtype=LD)
+    P = sym(Qd) + Mx
+    H = {}
+    for t in range(T - 1, -1, -1):
+        A, B = At[t], Bt[t]
+        PB = P.dot(B)
+        H[t] = sym(Rh + B.T.dot(PB))
+        try:
+            L = cholesky(H[t])
+        except np.linalg.LinAlgError:
+            return t, H
+        G = S.T + PB.T.dot(A)
+        P = sym(Qh + A.T.dot(P).dot(A) - G.T.dot(cho_solve(L, G)))
+    return None, H
+
+
+def position_controlled_form(At, Bt, Q, Qd, R, control="du"):
+    """The QP of the position-controlled descents (irs_quasistatic_box_descent; irs_lqr/tv_lqr.py:96-108: input cost
+    du_t'R du_t, du_t = u_t - u_{t-1}) on the augmented state z = [x; u_prev], as pivot_trace takes it.  Two spellings
+    of the same problem, whose control Hessians agree (u = u_prev + du is a shift of the control):
+      "du"   control du: A~ = [A B; 0 I], B~ = [B; I], cost x'Qx + du'R du            (the ADMM, the rate-limited boxes)
+      "abs"  control u:  A~ = [A 0; 0 0], B~ = [B; I], cost x'Qx + (u - w)'R(u - w)   (the trust-region boxes)
+             = z'diag(Q, R)z - 2 w'R u + u'Ru: a stage cross term S = [0; -R].
+    Returns dict(At, Bt, Q, Qd, R, cross) for pivot_trace(..., alpha_R=1)."""
+    At, Bt = np.asarray(At, dtype=LD), np.asarray(Bt, dtype=LD)
+    T, n, m = At.shape[0], At.shape[1], Bt.shape[2]
+    Q, Qd, R = sym(Q), sym(Qd), sym(R)
+    Aa = np.zeros((T, n + m, n + m), dtype=LD)
+    Ba = np.zeros((T, n + m, m), dtype=LD)
+    Aa[:, :n, :n] = At
+    Ba[:, :n, :] = Bt
+    Ba[:, n:, :] = np.eye(m, dtype=LD)
+    Qa = np.zeros((n + m, n + m), dtype=LD)
+    Qa[:n, :n] = Q
+    Qda = np.zeros((n + m, n + m), dtype=LD)
+    Qda[:n, :n] = Qd
+    cross = None
+    if control == "du":
+        Aa[:, :n, n:] = Bt
+        Aa[:, n:, n:] = np.eye(m, dtype=LD)
+    elif control == "abs":
+        Qa[n:, n:] = R
+        cross = np.zeros((n + m, m), dtype=LD)
+        cross[n:, :] = -R
+    else:
+        raise ValueError(control)
+    return dict(At=Aa, Bt=Ba, Q=Qa, Qd=Qda, R=R, cross=cross)
+
+
+def definiteness_margin(H):
+    """lambda_min(H) / max|H|: f64 eigvalsh of the extended-precision H (the margins asked of it are ten decades above
+    f64 rounding)."""
+    H = np.asarray(H, dtype=float)
+    return float(np.linalg.eigvalsh(0.5 * (H + H.T)).min() / np.abs(H).max())
+
+
 def linear_rollout(At, Bt, ct, K, k, x0):
     """u_t = K_t x_t + k_t, x_{t+1} = A_t x_t + B_t u_t + c_t in extended precision: x (T+1,n), u (T,m)."""
     At, Bt, ct, K, k = (np.asarray(a, dtype=LD) for a in (At, Bt, ct, K, k))

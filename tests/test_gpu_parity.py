@@ -1230,7 +1230,8 @@ def test_quasistatic_active_set_descent_reports_a_bad_hessian(amd):
     nan = dm.quasistatic_box_descent(*[dev.to_dev(a) for a in (At, Bn, ct, Q, Qd, R, xd, x0)], *rows_d, solver=0,
                                      max_iter=50, eps=1e-10)
     i3 = nan["info"].cpu().numpy()
-    assert i3[0] != 0 or i3[2] != 0 or not np.isfinite(float(nan["cost"].item())), i3
+    # the two words the host classes read (include/irs_hip.h, rule V2): a NaN cost alone is no verdict
+    assert i3[0] != 0 or i3[2] != 0, i3
 
 
 def test_peer_exchange_two_ranks_on_one_gpu():
