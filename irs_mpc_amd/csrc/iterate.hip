@@ -82,27 +82,24 @@ __device__ __forceinline__ void plan_check_body(int n, int m, int T, const doubl
     }
 }
 
+// BATCH: B problems, one workgroup each: problem b's contiguous blocks, its box, its flag (and no info row: the fused
+// iterate is a single-problem loop)
+template <bool BATCH>
 __global__ void plan_check_kernel(int n, int m, int T, const double* __restrict__ At, const double* __restrict__ Bt,
                                   const double* __restrict__ ct, const double* __restrict__ K,
                                   const double* __restrict__ k, const double* __restrict__ x_new,
                                   const double* __restrict__ xlo, const double* __restrict__ xhi,
                                   const double* __restrict__ ulo, const double* __restrict__ uhi, int* flag,
                                   const int* descent_info, const int* smooth_info, int box_unsupported, int* row) {
-    plan_check_body(n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, descent_info, smooth_info, box_unsupported,
-                    row);
-}
-
-// B problems, one workgroup each: problem b's contiguous blocks, its box, its flag (no info row: the fused iterate is
-// a single-problem loop)
-__global__ void plan_check_batch_kernel(int n, int m, int T, const double* __restrict__ At, const double* __restrict__ Bt,
-                                        const double* __restrict__ ct, const double* __restrict__ K,
-                                        const double* __restrict__ k, const double* __restrict__ x_new,
-                                        const double* __restrict__ xlo, const double* __restrict__ xhi,
-                                        const double* __restrict__ ulo, const double* __restrict__ uhi, int* flag) {
-    const size_t b = blockIdx.x, Ts = (size_t)T;
-    plan_check_body(n, m, T, At + b * Ts * n * n, Bt + b * Ts * n * m, ct + b * Ts * n, K + b * Ts * m * n, k + b * Ts * m,
-                    x_new + b * (Ts + 1) * n, xlo + b * n, xhi + b * n, ulo + b * m, uhi + b * m, flag + b, nullptr, nullptr,
-                    0, nullptr);
+    if constexpr (BATCH) {
+        const size_t b = blockIdx.x, Ts = (size_t)T;
+        plan_check_body(n, m, T, At + b * Ts * n * n, Bt + b * Ts * n * m, ct + b * Ts * n, K + b * Ts * m * n,
+                        k + b * Ts * m, x_new + b * (Ts + 1) * n, xlo + b * n, xhi + b * n, ulo + b * m, uhi + b * m,
+                        flag + b, nullptr, nullptr, 0, nullptr);
+    } else {
+        plan_check_body(n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, descent_info, smooth_info,
+                        box_unsupported, row);
+    }
 }
 
 // one unrolled step of the walk: x_l to its 16-lane group by DPP, two partial sums per output (half the FMA chain)
@@ -214,7 +211,7 @@ __device__ __forceinline__ void plan_check16_body(int m, int T, const double* __
     }
 }
 
-template <int NN>
+template <int NN, bool BATCH>
 __global__ __launch_bounds__(1024) void plan_check16_kernel(int m, int T, const double* __restrict__ At,
                                                             const double* __restrict__ Bt, const double* __restrict__ ct,
                                                             const double* __restrict__ K, const double* __restrict__ k,
@@ -223,54 +220,48 @@ __global__ __launch_bounds__(1024) void plan_check16_kernel(int m, int T, const 
                                                             const double* __restrict__ ulo, const double* __restrict__ uhi,
                                                             int* flag, const int* descent_info, const int* smooth_info,
                                                             int box_unsupported, int* row) {
-    plan_check16_body<NN>(m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, descent_info, smooth_info,
-                          box_unsupported, row);
+    if constexpr (BATCH) {
+        const size_t b = blockIdx.x, Ts = (size_t)T, n = NN;
+        plan_check16_body<NN>(m, T, At + b * Ts * n * n, Bt + b * Ts * n * m, ct + b * Ts * n, K + b * Ts * m * n,
+                              k + b * Ts * m, x_new + b * (Ts + 1) * n, xlo + b * n, xhi + b * n, ulo + b * m,
+                              uhi + b * m, flag + b, nullptr, nullptr, 0, nullptr);
+    } else {
+        plan_check16_body<NN>(m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, descent_info, smooth_info,
+                              box_unsupported, row);
+    }
 }
 
-template <int NN>
-__global__ __launch_bounds__(1024) void plan_check16_batch_kernel(int m, int T, const double* __restrict__ At,
-                                                                  const double* __restrict__ Bt,
-                                                                  const double* __restrict__ ct,
-                                                                  const double* __restrict__ K,
-                                                                  const double* __restrict__ k,
-                                                                  const double* __restrict__ x_new,
-                                                                  const double* __restrict__ xlo,
-                                                                  const double* __restrict__ xhi,
-                                                                  const double* __restrict__ ulo,
-                                                                  const double* __restrict__ uhi, int* flag) {
-    const size_t b = blockIdx.x, Ts = (size_t)T, n = NN;
-    plan_check16_body<NN>(m, T, At + b * Ts * n * n, Bt + b * Ts * n * m, ct + b * Ts * n, K + b * Ts * m * n,
-                          k + b * Ts * m, x_new + b * (Ts + 1) * n, xlo + b * n, xhi + b * n, ulo + b * m, uhi + b * m,
-                          flag + b, nullptr, nullptr, 0, nullptr);
-}
+// what a plan test reads and writes; the last four are the fused iterate's (null / 0 elsewhere)
+struct PlanArgs {
+    const double *At, *Bt, *ct, *K, *k, *x_new, *xlo, *xhi, *ulo, *uhi;
+    int* flag;
+    const int *descent_info, *smooth_info;
+    int box_unsupported;
+    int* row;
+};
 
+// B = 0: the single problem; B > 0: that many, one workgroup each
 template <int NN>
-static int plan_check16_launch(int m, int T, size_t bytes, const double* At, const double* Bt, const double* ct,
-                               const double* K, const double* k, const double* x_new, const double* xlo,
-                               const double* xhi, const double* ulo, const double* uhi, int* flag,
-                               const int* descent_info, const int* smooth_info, int box_unsupported, int* row,
-                               hipStream_t st) {
-    constexpr auto kern = plan_check16_kernel<NN>;
-    const int rc = irs_raise_lds_limit<kern>(150 * 1024, "plan check");
+static int plan_check16_launch(int m, int T, int B, size_t bytes, const PlanArgs& a, hipStream_t st) {
+    constexpr auto one = plan_check16_kernel<NN, false>;
+    constexpr auto many = plan_check16_kernel<NN, true>;
+    const int rc = B > 0 ? irs_raise_lds_limit<many>(150 * 1024, "plan check")
+                         : irs_raise_lds_limit<one>(150 * 1024, "plan check");
     if (rc != IRS_OK) return rc;
     // as many 64-lane waves as there are groups of four tails, at most 16
     const int waves = (T + 3) / 4 < 16 ? (T + 3) / 4 : 16;
-    hipLaunchKernelGGL(kern, dim3(1), dim3(64 * waves), bytes, st, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag,
-                       descent_info, smooth_info, box_unsupported, row);
+    hipLaunchKernelGGL(B > 0 ? many : one, dim3(B > 0 ? B : 1), dim3(64 * waves), bytes, st, m, T, a.At, a.Bt, a.ct, a.K,
+                       a.k, a.x_new, a.xlo, a.xhi, a.ulo, a.uhi, a.flag, a.descent_info, a.smooth_info, a.box_unsupported,
+                       a.row);
     return IRS_OK;
 }
 
-// launches the fast kernel when the closed loops fit LDS and n, m <= 16 (else the serial one)
-static int plan_check_launch(int n, int m, int T, const double* At, const double* Bt, const double* ct, const double* K,
-                             const double* k, const double* x_new, const double* xlo, const double* xhi,
-                             const double* ulo, const double* uhi, int* flag, const int* descent_info,
-                             const int* smooth_info, int box_unsupported, int* row, hipStream_t st) {
+// launches the fast kernel when the closed loops fit LDS and n, m <= 16 (else the serial one), per problem
+static int plan_check_launch(int n, int m, int T, int B, const PlanArgs& a, hipStream_t st) {
     const size_t bytes = (size_t)T * ((size_t)n * n + n + (size_t)n * m + m) * sizeof(double);
     if (n >= 1 && n <= 16 && m <= 16 && bytes <= (size_t)(150 * 1024)) {
-#define PC_CASE(NN_)                                                                                                    \
-    case NN_:                                                                                                           \
-        return plan_check16_launch<NN_>(m, T, bytes, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, descent_info,   \
-                                        smooth_info, box_unsupported, row, st);
+#define PC_CASE(NN_) \
+    case NN_: return plan_check16_launch<NN_>(m, T, B, bytes, a, st);
         switch (n) {
             PC_CASE(1) PC_CASE(2) PC_CASE(3) PC_CASE(4) PC_CASE(5) PC_CASE(6) PC_CASE(7) PC_CASE(8)
             PC_CASE(9) PC_CASE(10) PC_CASE(11) PC_CASE(12) PC_CASE(13) PC_CASE(14) PC_CASE(15) PC_CASE(16)
@@ -278,41 +269,9 @@ static int plan_check_launch(int n, int m, int T, const double* At, const double
 #undef PC_CASE
     }
     const int block = T < 256 ? ((T + 63) / 64 * 64) : 256;
-    hipLaunchKernelGGL(plan_check_kernel, dim3(1), dim3(block), 0, st, n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi,
-                       flag, descent_info, smooth_info, box_unsupported, row);
-    return IRS_OK;
-}
-
-// the same choice of kernel per problem, B workgroups
-template <int NN>
-static int plan_check16_batch_launch(int m, int T, int B, size_t bytes, const double* At, const double* Bt, const double* ct,
-                                     const double* K, const double* k, const double* x_new, const double* xlo,
-                                     const double* xhi, const double* ulo, const double* uhi, int* flag, hipStream_t st) {
-    constexpr auto kern = plan_check16_batch_kernel<NN>;
-    const int rc = irs_raise_lds_limit<kern>(150 * 1024, "plan check");
-    if (rc != IRS_OK) return rc;
-    const int waves = (T + 3) / 4 < 16 ? (T + 3) / 4 : 16;
-    hipLaunchKernelGGL(kern, dim3(B), dim3(64 * waves), bytes, st, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag);
-    return IRS_OK;
-}
-
-static int plan_check_batch_launch(int n, int m, int T, int B, const double* At, const double* Bt, const double* ct,
-                                   const double* K, const double* k, const double* x_new, const double* xlo,
-                                   const double* xhi, const double* ulo, const double* uhi, int* flag, hipStream_t st) {
-    const size_t bytes = (size_t)T * ((size_t)n * n + n + (size_t)n * m + m) * sizeof(double);
-    if (n >= 1 && n <= 16 && m <= 16 && bytes <= (size_t)(150 * 1024)) {
-#define PC_CASE(NN_)                                                                                                    \
-    case NN_:                                                                                                           \
-        return plan_check16_batch_launch<NN_>(m, T, B, bytes, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, st);
-        switch (n) {
-            PC_CASE(1) PC_CASE(2) PC_CASE(3) PC_CASE(4) PC_CASE(5) PC_CASE(6) PC_CASE(7) PC_CASE(8)
-            PC_CASE(9) PC_CASE(10) PC_CASE(11) PC_CASE(12) PC_CASE(13) PC_CASE(14) PC_CASE(15) PC_CASE(16)
-        }
-#undef PC_CASE
-    }
-    const int block = T < 256 ? ((T + 63) / 64 * 64) : 256;
-    hipLaunchKernelGGL(plan_check_batch_kernel, dim3(B), dim3(block), 0, st, n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo,
-                       uhi, flag);
+    hipLaunchKernelGGL(B > 0 ? plan_check_kernel<true> : plan_check_kernel<false>, dim3(B > 0 ? B : 1), dim3(block), 0, st,
+                       n, m, T, a.At, a.Bt, a.ct, a.K, a.k, a.x_new, a.xlo, a.xhi, a.ulo, a.uhi, a.flag, a.descent_info,
+                       a.smooth_info, a.box_unsupported, a.row);
     return IRS_OK;
 }
 
@@ -361,7 +320,7 @@ int irs_tvlqr_plan_within_bounds(int n, int m, int T, const double* At, const do
                                  const double* xhi, const double* ulo, const double* uhi, int* flag, void* stream) {
     IRS_CHECK_ARG(n > 0 && n <= 32 && m > 0 && m <= 16 && T > 0, "sizes out of range (n <= 32, m <= 16)");
     IRS_CHECK_ARG(At && Bt && ct && K && k && x_new && xlo && xhi && ulo && uhi && flag, "null pointer");
-    const int rc = plan_check_launch(n, m, T, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, nullptr, nullptr, 0, nullptr,
+    const int rc = plan_check_launch(n, m, T, 0, {At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, nullptr, nullptr, 0, nullptr},
                                      static_cast<hipStream_t>(stream));
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
@@ -374,8 +333,8 @@ int irs_tvlqr_plan_within_bounds_batch(int n, int m, int T, int B, const double*
     IRS_CHECK_ARG(n > 0 && n <= 32 && m > 0 && m <= 16 && T > 0, "sizes out of range (n <= 32, m <= 16)");
     IRS_CHECK_ARG(B > 0, "B must be positive");
     IRS_CHECK_ARG(At && Bt && ct && K && k && x_new && xlo && xhi && ulo && uhi && flag, "null pointer");
-    const int rc = plan_check_batch_launch(n, m, T, B, At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag,
-                                           static_cast<hipStream_t>(stream));
+    const int rc = plan_check_launch(n, m, T, B, {At, Bt, ct, K, k, x_new, xlo, xhi, ulo, uhi, flag, nullptr, nullptr, 0, nullptr},
+                                     static_cast<hipStream_t>(stream));
     if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
@@ -485,8 +444,9 @@ int irs_iterate(const irs_iterate_call* c, irs_timing* timing, void* stream) {
         if (rc != IRS_OK) return rc;
         tm.mark(2);
         if (bounded) {
-            rc = plan_check_launch(n, m, T, At, Bt, ct, K, k, x_new, c->xlo, c->xhi, c->ulo, c->uhi, box_flag, descent_info,
-                                   exact ? nullptr : smooth_info, box_fits ? 0 : 1, c->info_hist + (size_t)it * 8, st);
+            rc = plan_check_launch(n, m, T, 0,
+                                   {At, Bt, ct, K, k, x_new, c->xlo, c->xhi, c->ulo, c->uhi, box_flag, descent_info,
+                                    exact ? nullptr : smooth_info, box_fits ? 0 : 1, c->info_hist + (size_t)it * 8}, st);
             if (rc != IRS_OK) return rc;
             if (box_fits) {     // its info lands in the row (zeroed above) if it runs
                 ba.x0 = x_nom; ba.x_new = x_new; ba.u_new = u_new;

@@ -439,6 +439,10 @@ __device__ __forceinline__ void riccati_backward_reg(const RiccatiArgs& a, int l
 // and the A-operand layout of the TRANSPOSE -- so P~ (symmetric), A~' and B~' need no
 // data movement at all.  No LDS traffic, no waits inside a step except the 4x4 solve.
 constexpr int kQxMax = 4096;          // doubles of LDS for Q xd_t, t = 0..T
+// "this size runs the backward pass here": what riccati_backward_any dispatches on and what sizes a kernel's qx, so
+// a size that takes this path always has the full array (the small sizes, N <= 4 and M <= 2, run in registers)
+template <int N, int M>
+constexpr bool kRiccatiOnMatrixCores = !(N <= 4 && M <= 2) && N + 1 <= 16 && M <= 4;
 
 // -DIRS_RIC_STAMPS (tuning builds only): s_memtime totals per phase of the matrix-core recursion
 #ifdef IRS_RIC_STAMPS
@@ -670,7 +674,7 @@ __device__ __forceinline__ void riccati_backward_any(const RiccatiArgs& a, int l
                                                      double* qx) {
     if constexpr (N <= 4 && M <= 2) {
         riccati_backward_reg<N, M>(a, lane);
-    } else if constexpr (N + 1 <= 16 && M <= 4) {
+    } else if constexpr (kRiccatiOnMatrixCores<N, M>) {
         if ((a.T + 1) * N <= kQxMax) riccati_backward_mfma<N, M>(a, lane, qx);
         else riccati_backward<N, M>(a, lane, S);
     } else {
@@ -681,7 +685,7 @@ __device__ __forceinline__ void riccati_backward_any(const RiccatiArgs& a, int l
 template <int N, int M>
 __global__ __launch_bounds__(64) void riccati_kernel_t(RiccatiArgs a) {
     __shared__ RiccatiLds<N, M> S;
-    __shared__ double qx[(N > 4 && N + 1 <= 16 && M <= 4) ? kQxMax : 1];
+    __shared__ double qx[kRiccatiOnMatrixCores<N, M> ? kQxMax : 1];
     riccati_backward_any<N, M>(a, threadIdx.x, S, qx);
 }
 
@@ -1107,14 +1111,25 @@ __device__ __forceinline__ void descent_verdict(const RiccatiArgs& a, double cos
 // One launch for the whole of IrsLqr.local_descent after get_TV_matrices
 // (irs_lqr/irs_lqr.py:169-184) + evaluate_cost: backward Riccati, then the closed-loop
 // rollout of the policy it just wrote.
-template <class Model>
+// BATCH: grid B, workgroup b runs the same program on problem b's blocks.  `a`, x0 and the outputs describe problem 0;
+// Q, Qd, R, the model and T are shared.  (No info row: the fused iterate is a single-problem loop.)
+template <class Model, bool BATCH>
 __global__ __launch_bounds__(64) void descent_kernel(ModelParams p, RiccatiArgs a, const double* x0,
                                                      double* x_new, double* u_new, double* cost_out,
                                                      const int* smooth_info, int* row) {
     __shared__ RiccatiLds<Model::NX, Model::NU> S;
     __shared__ RolloutLds<Model> S2;
     const int lane = threadIdx.x;
-    __shared__ double qx[(Model::NX > 4 && Model::NX + 1 <= 16 && Model::NU <= 4) ? kQxMax : 1];
+    __shared__ double qx[kRiccatiOnMatrixCores<Model::NX, Model::NU> ? kQxMax : 1];
+    if constexpr (BATCH) {
+        constexpr size_t n = Model::NX, m = Model::NU;
+        const size_t b = blockIdx.x, T = (size_t)a.T;
+        a.At += b * T * n * n; a.Bt += b * T * n * m; a.ct += b * T * n;
+        a.xd += b * (T + 1) * n;
+        a.K += b * T * m * n; a.k += b * T * m;
+        a.info += b;
+        x0 += b * n; x_new += b * (T + 1) * n; u_new += b * T * m; cost_out += b;
+    }
     riccati_backward_any<Model::NX, Model::NU>(a, lane, S, qx);
     // the gains were stored by this very wave: drain the stores, then re-read them
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
@@ -1124,43 +1139,21 @@ __global__ __launch_bounds__(64) void descent_kernel(ModelParams p, RiccatiArgs 
     descent_verdict(a, cost, lane);
     // fused iterate (iterate.hip), no bounds: this descent's row of the info history -- [0] Riccati info,
     // [1] timesteps whose smoothing solve failed, the rest zero -- without a launch of its own
-    if (row != nullptr) {
-        int bad = 0;
-        if (smooth_info != nullptr)
-            for (int t = lane; t < a.T; t += 64) bad += smooth_info[t] != 0 ? 1 : 0;
+    if constexpr (!BATCH) {
+        if (row != nullptr) {
+            int bad = 0;
+            if (smooth_info != nullptr)
+                for (int t = lane; t < a.T; t += 64) bad += smooth_info[t] != 0 ? 1 : 0;
 #pragma unroll
-        for (int sft = 32; sft >= 1; sft >>= 1) bad += __shfl_xor(bad, sft, 64);
-        if (lane == 0) {
-            row[0] = a.info[0];
-            row[1] = bad;
+            for (int sft = 32; sft >= 1; sft >>= 1) bad += __shfl_xor(bad, sft, 64);
+            if (lane == 0) {
+                row[0] = a.info[0];
+                row[1] = bad;
 #pragma unroll
-            for (int i = 2; i < 8; ++i) row[i] = 0;
+                for (int i = 2; i < 8; ++i) row[i] = 0;
+            }
         }
     }
-}
-
-// descent_kernel with a problem index: grid B, workgroup b runs the same program -- backward pass, fence, closed-loop
-// rollout -- on problem b's blocks.  `a`, x0 and the outputs describe problem 0; Q, Qd, R, the model and T are shared.
-template <class Model>
-__global__ __launch_bounds__(64) void descent_batch_kernel(ModelParams p, RiccatiArgs a, const double* x0,
-                                                           double* x_new, double* u_new, double* cost_out) {
-    constexpr size_t n = Model::NX, m = Model::NU;
-    __shared__ RiccatiLds<Model::NX, Model::NU> S;
-    __shared__ RolloutLds<Model> S2;
-    const int lane = threadIdx.x;
-    __shared__ double qx[(Model::NX > 4 && Model::NX + 1 <= 16 && Model::NU <= 4) ? kQxMax : 1];
-    const size_t b = blockIdx.x, T = (size_t)a.T;
-    a.At += b * T * n * n; a.Bt += b * T * n * m; a.ct += b * T * n;
-    a.xd += b * (T + 1) * n;
-    a.K += b * T * m * n; a.k += b * T * m;
-    a.info += b;
-    riccati_backward_any<Model::NX, Model::NU>(a, lane, S, qx);
-    // the gains were stored by this very wave: drain the stores, then re-read them
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const double cost = rollout_device<Model>(p, a.T, a.K, a.k, nullptr, x0 + b * n, a.Q, a.R, a.xd,
-                                              x_new + b * (T + 1) * n, u_new + b * T * m, cost_out + b, lane, S2);
-    descent_verdict(a, cost, lane);
 }
 
 // evaluate_cost of a given trajectory pair: lanes stride over t, f64 wave reduction.
@@ -1275,6 +1268,22 @@ __global__ __launch_bounds__(256) void lstsq_kernel(int n, int m, int N, const d
     for (int q = lane; q < n * n; q += 64) A[q] = H[q % n][q / n] * sc[q % n];                 // ABhat[k][i] = X[i][k]
     for (int q = lane; q < n * m; q += 64) B[q] = H[n + q % m][q / m] * sc[n + q % m];
     if (lane == 0) info[0] = bad;
+}
+
+// The one launch of a descent, after its entry's argument checks: B = 0 the single problem (row, when not null, takes
+// the fused iterate's info row), B > 0 that many problems, one workgroup each.  Only the analytic models have a
+// batched kernel; irs_tvlqr_descent_batch refuses the others.
+static int descent_launch(int model, const ModelParams& p, RiccatiArgs a, int B, const double* x0, double* x_new,
+                          double* u_new, double* cost, const int* smooth_info, int* row, hipStream_t st) {
+    IRS_DISPATCH_MODEL(model, {
+        a.n = Model::NX;
+        a.m = Model::NU;
+        auto kern = descent_kernel<Model, false>;
+        if constexpr (Model::HAS_JACOBIAN)
+            if (B > 0) kern = descent_kernel<Model, true>;
+        hipLaunchKernelGGL(kern, dim3(B > 0 ? B : 1), dim3(64), 0, st, p, a, x0, x_new, u_new, cost, smooth_info, row);
+    });
+    return IRS_OK;
 }
 
 extern "C" {
@@ -1405,19 +1414,9 @@ int irs_tvlqr_descent_batch(int model, const double* params, int n_params, int T
     ModelParams p;
     rc = irs_load_params(model, params, n_params, &p);
     if (rc != IRS_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-#define IRS_DESCENT_BATCH(Model_)                                                                                       \
-    {                                                                                                                   \
-        RiccatiArgs a{At, Bt, ct, Q, Qd, R, xd_trj, K, k, info, alpha_R, Model_::NX, Model_::NU, T};                    \
-        hipLaunchKernelGGL((descent_batch_kernel<Model_>), dim3(B), dim3(64), 0, st, p, a, x0, x_new, u_new, cost);    \
-    }
-    switch (model) {
-        case IRS_MODEL_PENDULUM: IRS_DESCENT_BATCH(PendulumModel) break;
-        case IRS_MODEL_QUADROTOR: IRS_DESCENT_BATCH(QuadrotorModel) break;
-        case IRS_MODEL_BICYCLE: IRS_DESCENT_BATCH(BicycleModel) break;
-        default: IRS_DESCENT_BATCH(ThreeCartModel) break;
-    }
-#undef IRS_DESCENT_BATCH
+    rc = descent_launch(model, p, RiccatiArgs{At, Bt, ct, Q, Qd, R, xd_trj, K, k, info, alpha_R, n, m, T}, B, x0, x_new,
+                        u_new, cost, nullptr, nullptr, static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
 }
@@ -1435,12 +1434,9 @@ int irs_tvlqr_descent_row(int model, const double* params, int n_params, int T, 
     ModelParams p;
     int rc = irs_load_params(model, params, n_params, &p);
     if (rc != IRS_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    IRS_DISPATCH_MODEL(model, {
-        RiccatiArgs a{At, Bt, ct, Q, Qd, R, xd_trj, K, k, info, alpha_R, Model::NX, Model::NU, T};
-        hipLaunchKernelGGL((descent_kernel<Model>), dim3(1), dim3(64), 0, st, p, a, x0, x_new, u_new, cost, smooth_info,
-                           row);
-    });
+    rc = descent_launch(model, p, RiccatiArgs{At, Bt, ct, Q, Qd, R, xd_trj, K, k, info, alpha_R, 0, 0, T}, 0, x0, x_new,
+                        u_new, cost, smooth_info, row, static_cast<hipStream_t>(stream));
+    if (rc != IRS_OK) return rc;
     IRS_CHECK_LAUNCH();
     return IRS_OK;
 }

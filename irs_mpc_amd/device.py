@@ -52,6 +52,19 @@ def _outputs(out, shapes, device):
     return o
 
 
+def _descent_outputs(dm, T, lead, device, out=None, **given):
+    """The outputs K, k, x_new, u_new, cost, info of a Riccati descent over T steps, of one problem (lead = ()) or of B
+    (lead = (B,)): `out`, or fresh tensors with the `given` ones (x_new=, u_new=; None = fresh) in their places."""
+    n, m = dm.n, dm.m
+    shapes = dict(K=lead + (T, m, n), k=lead + (T, m), x_new=lead + (T + 1, n), u_new=lead + (T, m), cost=lead or (1,),
+                  info=lead or (1,))
+    given = {name: t for name, t in given.items() if t is not None}
+    if out is None and given:
+        out = DeviceModel._tv_alloc({name: shape for name, shape in shapes.items() if name not in given}, device)
+        out.update(given)
+    return _outputs(out, shapes, device)
+
+
 def to_dev(a, dtype=F64):
     """numpy / tensor -> contiguous device tensor of `dtype`."""
     dev = require_gpu()
@@ -356,15 +369,7 @@ class DeviceModel(CemModelFree):
     def tvlqr_descent(self, At, Bt, ct, Q, Qd, R, xd_trj, x0, alpha_R=0.5, out=None):
         """Riccati backward pass + closed-loop rollout + cost in one launch."""
         T = At.shape[0]
-        dev = At.device
-        o = out
-        if o is None:
-            o = dict(K=torch.empty((T, self.m, self.n), dtype=F64, device=dev),
-                     k=torch.empty((T, self.m), dtype=F64, device=dev),
-                     x_new=torch.empty((T + 1, self.n), dtype=F64, device=dev),
-                     u_new=torch.empty((T, self.m), dtype=F64, device=dev),
-                     cost=torch.empty((1,), dtype=F64, device=dev),
-                     info=torch.empty((1,), dtype=torch.int32, device=dev))
+        o = _descent_outputs(self, T, (), At.device, out)
         check(self.lib.irs_tvlqr_descent(self.model_id, self._p, self._np, T, _ptr(At, F64), _ptr(Bt, F64),
                                          _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
                                          float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(o["K"], F64),
@@ -380,12 +385,10 @@ class DeviceModel(CemModelFree):
         ct (B,T,n), xd_trj (B,T+1,n), x0 (B,n).  Returns dict(K (B,T,m,n), k (B,T,m), x_new (B,T+1,n), u_new (B,T,m),
         cost (B), info (B)); pass `out` to write into tensors of those shapes."""
         B, T = At.shape[0], At.shape[1]
-        dev = At.device
         n, m = self.n, self.m
         _check_shapes((("At", At, (B, T, n, n)), ("Bt", Bt, (B, T, n, m)), ("ct", ct, (B, T, n)),
                        ("xd_trj", xd_trj, (B, T + 1, n)), ("x0", x0, (B, n))))
-        o = _outputs(out, dict(K=(B, T, m, n), k=(B, T, m), x_new=(B, T + 1, n), u_new=(B, T, m), cost=(B,), info=(B,)),
-                     dev)
+        o = _descent_outputs(self, T, (B,), At.device, out)
         check(self.lib.irs_tvlqr_descent_batch(self.model_id, self._p, self._np, T, B, _ptr(At, F64), _ptr(Bt, F64),
                                                _ptr(ct, F64), _ptr(Q, F64), _ptr(Qd, F64), _ptr(R, F64),
                                                float(alpha_R), _ptr(xd_trj, F64), _ptr(x0, F64), _ptr(o["K"], F64),
@@ -811,13 +814,7 @@ class DescentPlan:
 
     def __init__(self, dm, At, Bt, ct, Q, Qd, R, xd_trj, x0, alpha_R=0.5, x_new=None, u_new=None):
         T = At.shape[0]
-        device = At.device
-        self.out = dict(K=torch.empty((T, dm.m, dm.n), dtype=F64, device=device),
-                        k=torch.empty((T, dm.m), dtype=F64, device=device),
-                        x_new=x_new if x_new is not None else torch.empty((T + 1, dm.n), dtype=F64, device=device),
-                        u_new=u_new if u_new is not None else torch.empty((T, dm.m), dtype=F64, device=device),
-                        cost=torch.empty((1,), dtype=F64, device=device),
-                        info=torch.empty((1,), dtype=torch.int32, device=device))
+        self.out = _descent_outputs(dm, T, (), At.device, x_new=x_new, u_new=u_new)
         c = _lib.DescentCall()
         dm.fill_call(c)
         c.T, c.alpha_R = T, float(alpha_R)

@@ -32,6 +32,15 @@ from ._lib import SMOOTH_FIRST_ORDER, SMOOTH_ZERO_ORDER_AB
 from .sampling import GaussianSmoothing
 from .tv_lqr import get_solver
 
+# what a failed descent raises, in the single classes and (as `status` texts) in IrsLqrBatch
+RICCATI_FAILED = "TV_LQR failed. Optimization problem is not solved."       # also: a bounded QP that did not converge
+SMOOTHING_FAILED = ("randomized-smoothing least squares is rank deficient (Gram matrix not positive definite; need more "
+                    "samples or a non-zero std)")
+SMOOTHING_FAILED_AT = ("randomized-smoothing least squares is rank deficient at t=%d (Gram matrix not positive definite; "
+                       "need more samples or a non-zero std)")
+HORIZON_BEYOND_LIMIT = ("a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
+                        "(factor records in HBM, ADMM vectors in LDS; tv_lqr.py:112-123)")
+
 
 class IrsLqrParameters:
     """irs_lqr/irs_lqr.py:7-31."""
@@ -167,9 +176,7 @@ class IrsLqr:
                     raise NotImplementedError("params.%s needs a compiled device model: the stepped bounded descent "
                                               "(qp_model_free) has the fixed penalty and enforces every bound" % flag)
         if not self._dm.box_descent_supported(self.T):
-            raise NotImplementedError(
-                "a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
-                "(factor records in HBM, ADMM vectors in LDS; tv_lqr.py:112-123)" % (self.T, self._dm.box_horizon_limit()))
+            raise NotImplementedError(HORIZON_BEYOND_LIMIT % (self.T, self._dm.box_horizon_limit()))
         # genuine bounds (tv_lqr.py:112-123): T warm-started tail QPs, one launch
         ob = self._dm.tvlqr_box_descent(At, Bt, ct, self._Q, self._Qd, self._R, self._xd,
                                         x_trj[0].contiguous(), *box, alpha_R=0.5,
@@ -251,19 +258,54 @@ class IrsLqr:
         info = getattr(self, "_smooth_info", None)
         if info is not None and bool((info != 0).any().item()):
             t = int(torch.nonzero(info)[0].item())
-            raise ValueError("randomized-smoothing least squares is rank deficient at t=%d "
-                             "(Gram matrix not positive definite; need more samples or a non-zero std)" % t)
+            raise ValueError(SMOOTHING_FAILED_AT % t)
 
     def _check_box_solved(self):
         """Like OSQP hitting its iteration limit (tv_lqr.py:139-140): an unconverged bounded tail QP is a
         failure."""
         if getattr(self, "_box_used", False) and int(self._last["box_info"][2].item()) != 0:
-            raise ValueError("TV_LQR failed. Optimization problem is not solved.")
+            raise ValueError(RICCATI_FAILED)
 
     # ---- irs_lqr/irs_lqr.py:188-218 ----------------------------------------
     def _fused_spec(self):
         """(mode, N, sampling) if the whole loop can run inside the library (irs_iterate): the linearisation needs no
         host closure per time step -- exact, or a GaussianSmoothing drawn on the device -- on one GPU; else None."""
+        return None
+
+    def _adopt(self, x_new, u_new, cost_new, max_iterations):
+        """One descent's bookkeeping (irs_lqr/irs_lqr.py:203-216): logged, then adopted and counted unless it is the
+        loop's last.  Returns whether the loop goes on."""
+        self.x_trj_lst.append(x_new)
+        self.u_trj_lst.append(u_new)
+        self.cost_lst.append(cost_new)
+        if self.iter > max_iterations:
+            return False
+        self.cost, self.x_trj, self.u_trj = cost_new, x_new, u_new
+        self.iter += 1
+        return True
+
+    def _replay(self, xs, us, costs, failures, max_iterations):
+        """The loop of `iterate` for descents that have already run, in order: xs[i], us[i], costs[i] are descent i's
+        host results, failures[i] is None or the exception to raise (IrsLqrBatch: its status text).  Stops at the first
+        failure and returns it -- the lists then hold everything before it -- else logs, adopts and counts as `iterate`
+        does, and returns None."""
+        for x_new, u_new, cost_new, failure in zip(xs, us, costs, failures):
+            if failure is not None:
+                return failure
+            if not self._adopt(x_new, u_new, float(cost_new), max_iterations):
+                break
+        return None
+
+    def _fused_failure(self, row):
+        """What the loop raises for a descent whose row of irs_iterate's info history is `row`, or None."""
+        if row[0] != 0:
+            return ValueError(RICCATI_FAILED)
+        if row[1] != 0:
+            return ValueError(SMOOTHING_FAILED)
+        if row[6] != 0:
+            return NotImplementedError(HORIZON_BEYOND_LIMIT % (self.T, self._dm.box_horizon_limit()))
+        if row[2] != 0 and row[5] != 0:
+            return ValueError(RICCATI_FAILED)
         return None
 
     def _iterate_fused(self, max_iterations, spec, timing=None):
@@ -315,26 +357,9 @@ class IrsLqr:
             timing.update({k: getattr(tm, k) for k, _ in _lib.Timing._fields_})
         xs, us, cs, infos = xh.cpu().numpy(), uh.cpu().numpy(), ch.cpu().numpy(), ih.cpu().numpy()     # the ONE read-back
         self._last = dict(At=None, Bt=None, ct=None, K=None, k=None, info=ih[-1, :1])
-        for i in range(n_desc):
-            row = infos[i]
-            if row[0] != 0:
-                raise ValueError("TV_LQR failed. Optimization problem is not solved.")
-            if row[1] != 0:
-                raise ValueError("randomized-smoothing least squares is rank deficient (Gram matrix not positive "
-                                 "definite; need more samples or a non-zero std)")
-            if row[6] != 0:
-                raise NotImplementedError(
-                    "a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
-                    "(factor records in HBM, ADMM vectors in LDS; tv_lqr.py:112-123)" % (self.T, self._dm.box_horizon_limit()))
-            if row[2] != 0 and row[5] != 0:
-                raise ValueError("TV_LQR failed. Optimization problem is not solved.")
-            self.x_trj_lst.append(xs[i])
-            self.u_trj_lst.append(us[i])
-            self.cost_lst.append(float(cs[i]))
-            if self.iter > max_iterations:
-                break
-            self.cost, self.x_trj, self.u_trj = float(cs[i]), xs[i], us[i]
-            self.iter += 1
+        failure = self._replay(xs, us, cs, [self._fused_failure(row) for row in infos], max_iterations)
+        if failure is not None:
+            raise failure
         return self.x_trj, self.u_trj, self.cost
 
     def iterate(self, max_iterations, timing=None):
@@ -355,7 +380,7 @@ class IrsLqr:
             u_trj_new = u_new_d.cpu().numpy()
             cost_new = float(cost_d.item())
             if int(self._last["info"].item()) != 0:
-                raise ValueError("TV_LQR failed. Optimization problem is not solved.")
+                raise ValueError(RICCATI_FAILED)
             self._check_smooth_info()
             self._check_box_solved()
 
@@ -364,18 +389,9 @@ class IrsLqr:
                       "Current Cost: {0:05f} ".format(cost_new) + " || " +
                       "Elapsed time: {0:05f} ".format(time.time() - self.start_time))
 
-            self.x_trj_lst.append(x_trj_new)
-            self.u_trj_lst.append(u_trj_new)
-            self.cost_lst.append(cost_new)
-
-            if self.iter > max_iterations:
+            if not self._adopt(x_trj_new, u_trj_new, cost_new, max_iterations):
                 break
-
-            self.cost = cost_new
-            self.x_trj = x_trj_new
-            self.u_trj = u_trj_new
             x_dev, u_dev = x_new_d, u_new_d
-            self.iter += 1
 
         return self.x_trj, self.u_trj, self.cost
 

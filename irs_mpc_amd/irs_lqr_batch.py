@@ -33,27 +33,17 @@ from . import device as dev
 from . import distributed as dist_util
 from ._lib import SMOOTH_FIRST_ORDER, SMOOTH_ZERO_ORDER_AB
 from .batch_common import StackedResults, seed_bits
-from .irs_lqr import IrsLqr
+from .irs_lqr import HORIZON_BEYOND_LIMIT, RICCATI_FAILED, SMOOTHING_FAILED, IrsLqr
 from .sampling import GaussianSmoothing
 from .torch_system import TorchDynamicalSystem
 
 ORDERS = {"zero_order": (SMOOTH_ZERO_ORDER_AB, "IrsLqrZeroOrder"), "first_order": (SMOOTH_FIRST_ORDER, "IrsLqrFirstOrder"),
           "exact": (None, "IrsLqrExact")}
 
-RICCATI_FAILED = "TV_LQR failed. Optimization problem is not solved."
-SMOOTHING_FAILED = ("randomized-smoothing least squares is rank deficient (Gram matrix not positive definite; need more "
-                    "samples or a non-zero std)")
-
 
 def _bound_active(single):
     return ("a box bound is active at this descent: the batch runs unbounded (Riccati) descents only; run this problem "
             "with %s, whose bounded descent (irs_tvlqr_box_descent) enforces it" % single)
-
-
-def _horizon_beyond_limit(T, limit):
-    # IrsLqr.local_descent's text (irs_lqr.py)
-    return ("a box bound is active and horizon T=%d is beyond the bounded TV-LQR kernel's limit T <= %d "
-            "(factor records in HBM, ADMM vectors in LDS; tv_lqr.py:112-123)" % (T, limit))
 
 
 # the bounded QPs' ADMM settings, shared by the problems of a launch: the field and the single class's default
@@ -137,7 +127,7 @@ class IrsLqrBatch(StackedResults):
         self._box = None
         if any(np.isfinite(v).any() for box in boxes for v in box):
             if self.bounded and not self._dm.box_descent_supported(T):
-                raise NotImplementedError(_horizon_beyond_limit(T, self._dm.box_horizon_limit()))
+                raise NotImplementedError(HORIZON_BEYOND_LIMIT % (T, self._dm.box_horizon_limit()))
             self._box = tuple(dev.to_dev(np.stack([box[i] for box in boxes])) for i in range(4))
         if smps is not None:
             self._seeds = seed_bits([s.seed for s in smps], self._Q.device)      # uploaded once
@@ -235,23 +225,16 @@ class IrsLqrBatch(StackedResults):
             if self.status[b] is not None:
                 continue                                     # stopped in an earlier call: frozen at its last adopted state
             pr.iter = it0
+            failures = [None] * D
             for i in range(D):
                 if dinfo_h[i, b] != 0:
-                    self.status[b] = RICCATI_FAILED
+                    failures[i] = RICCATI_FAILED
                 elif sbad_h[i, b]:
-                    self.status[b] = SMOOTHING_FAILED
+                    failures[i] = SMOOTHING_FAILED
                 elif flags_h[i, b] != 0 and not bounded:
-                    self.status[b] = _bound_active(self._single)
+                    failures[i] = _bound_active(self._single)
                 elif flags_h[i, b] != 0 and (binfo_h[i, b, 0] != 0 or binfo_h[i, b, 2] != 0):
-                    self.status[b] = RICCATI_FAILED          # the single class's message for an unsolved bounded QP
-                if self.status[b] is not None:
-                    break
-                pr.x_trj_lst.append(xs_h[i, b])
-                pr.u_trj_lst.append(us_h[i, b])
-                pr.cost_lst.append(float(cs_h[i, b]))
-                if pr.iter > max_iterations:
-                    break
-                pr.cost, pr.x_trj, pr.u_trj = float(cs_h[i, b]), xs_h[i, b], us_h[i, b]
-                pr.iter += 1
+                    failures[i] = RICCATI_FAILED             # the single class's message for an unsolved bounded QP
+            self.status[b] = pr._replay(xs_h[:, b], us_h[:, b], cs_h[:, b], failures, max_iterations)
         self.iter = it0 + D - 1
         return self.x_trj, self.u_trj, self.cost
